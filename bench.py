@@ -13,8 +13,10 @@ remove k<=5 + add j<=50} ('replace 1' is swapped for the mixed act
 because the reference itself throws on most such scenarios, see generator.BENCH_ACTIONS — the literal
 SURVEY mix is measured too and reported as config.literal_c3_mix).
 
-The timed region (exactly --steps steps between barriers) is run --repeats times inside one
-invocation; `value` and `ms_per_step` are the MEDIAN repeat's, the spread is in `repeats`.
+A plain run sets up, warms up, times the region of exactly --steps steps between barriers ONCE, writes
+what the last step computed if --dump-outputs is given, and prints the line.  --full runs the region
+--repeats times (5) inside one invocation, `value` and `ms_per_step` then being the MEDIAN repeat's with
+the spread in `repeats`, and adds every leg below.
 
 Multi-GPU: `python bench.py --gpus N` launches its own N ranks (one process per GPU, re-exec under
 torch.distributed.run on 127.0.0.1) unless it already runs under a launcher (WORLD_SIZE set), and
@@ -25,9 +27,10 @@ an RCCL all-gather of the 32-byte per-scenario result records; its time alone is
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline      — algorithmic HBM bytes per launch against the 8 TB/s HBM3E peak, at the whole-job
-                  rate (bytes / ms_per_step) and per kernel with ONE batch on the GPU (HIP events
-                  on the launch stream); kernel names come from the plan (kas_plan_describe);
+                  rate (bytes / ms_per_step) and (--full) per kernel with ONE batch on the GPU (HIP
+                  events on the launch stream); kernel names come from the plan (kas_plan_describe);
                   `traffic` only from a committed PMC profile of the same kernels AND sources
+and with --full
   cpu_baseline  — B1 the CPU oracle (C restatement of the reference Java; no JVM exists here) and
                   B2 the flat-array CPU solver, each on one core (bounded sample) and scenario-
                   parallel on every host core inside one C call
@@ -77,8 +80,17 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="times the timed region (exactly --steps steps) is run; value = the median repeat")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: five repeats, the parity check of every slot against the CPU "
+                         "solvers, the CPU baselines, the longer region, the other cell layout, one batch alone, the literal "
+                         "mix, end_to_end and other_configs.  Without it a run sets up, warms up, times --steps steps once "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64 records, a seeded sample "
+                         "of the output cells as float32)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="times the timed region (exactly --steps steps) is run; value = the median repeat "
+                         "(default 1, with --full 5)")
     ap.add_argument("--scenarios", type=int, default=1000,
                     help="scenarios per GPU per step (--scaling weak) or in total (--scaling strong)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
@@ -89,13 +101,14 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=2026)
     ap.add_argument("--actions", default="", help="comma list overriding the per-scenario action mix "
                     "(remove1,remove_k,add_k,mixed,replace1,add50); default generator.BENCH_ACTIONS")
-    ap.add_argument("--check", type=int, default=-1,
+    ap.add_argument("--check", type=int, default=None,
                     help="scenarios of slot 0 list-compared against the oracle (-1 = all); the records of every "
-                         "slot are compared either way unless this is 0")
+                         "slot are compared either way unless this is 0 (default 0, with --full -1)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="single-core CPU-baseline sample budget (each)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the one-batch-alone, literal-mix, end-to-end and other-config legs")
+                    help="with --full: skip the longer-region, other-cells, one-batch-alone, literal-mix, end-to-end and "
+                         "other-config legs")
     ap.add_argument("--in-flight", type=int, default=12,
                     help="batches in flight: steps are issued round-robin on this many HIP streams, "
                          "each slot with its own tables, broker sets, plan scratch and outputs (round 5: 12 — with every "
@@ -129,6 +142,10 @@ def parse_args(argv=None):
                          "per GPU as replicas (--scaling weak)")
     args = ap.parse_args(argv)
     apply_config_preset(args, ap, argv if argv is not None else sys.argv[1:])
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.check is None:
+        args.check = -1 if args.full else 0
     return args
 
 
@@ -147,7 +164,7 @@ def apply_config_preset(args, ap, argv):
         return
     named = {a.split("=")[0] for a in argv if a.startswith("--")}
     for key, val in CONFIG_PRESETS[args.config].items():
-        if "--" + key.replace("_", "-") not in named:
+        if "--" + key.replace("_", "-") not in named and (key != "check" or args.full):     # (a plain run checks nothing)
             setattr(args, key, val)
     if args.config == 3 and "--in-flight" not in named and args.gpus < 2:
         args.in_flight = 1                          # (64k scenarios on ONE GPU: 154 GB of tables per batch in flight)
@@ -602,14 +619,18 @@ def run_rank(args) -> int:
     med = order[(n_rep - 1) // 2]
     elapsed = reps[med]
     fill_us, order_us, kern_n = rep_kernel_times[med]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run, run.slots[(run.step_no - 1) % run.n_slots], coll)
+    # (the legs below are --full's: a plain run reports the timed region above and nothing else)
+    extras = args.full and not args.no_extras and not args.stub
     # the same region twice as long (three repeats): the ramp at both ends of a 20-step region is ~3 % of it, so a
     # kernel gain of that size would not show in `value`; reported beside it, never instead of it
     long_steps = 2 * args.steps
-    long_reps = [] if args.stub or args.no_extras else [timed(long_steps, 0) for _ in range(3)]
+    long_reps = [timed(long_steps, 0) for _ in range(3)] if extras else []
     run.phase_times()
     # the same slots with the OTHER cell layout resident in HBM (HipRun.other_cells_rate), reported beside the headline
     other_cells, other_rec0 = None, None
-    if not args.stub and not args.no_extras and world == 1:
+    if extras and world == 1:
         other_cells, other_rec0 = run.other_cells_rate(args.steps)
 
     if args.stats and rank == 0 and not args.stub:
@@ -655,7 +676,7 @@ def run_rank(args) -> int:
 
     # ---- one batch alone on the GPU: per-kernel durations free of other launches -----------------
     alone = None
-    if not args.stub and not args.no_extras:
+    if extras:
         keep, keep_n = run.slots, run.n_slots
         run.slots, run.n_slots = keep[:1], 1
         n_alone = max(3, min(10, args.steps))
@@ -693,7 +714,7 @@ def run_rank(args) -> int:
     # ---- the literal SURVEY 8(d) C3 action mix (with 'replace 1'), same cur tables ---------------
     literal = None
     # (the condition must not depend on the rank: every rank takes part in the timed collectives)
-    if (not args.stub and not args.no_extras and not args.actions and args.scaling == "weak" and
+    if (extras and not args.actions and args.scaling == "weak" and
             (args.scenarios, args.partitions, args.brokers, args.racks, args.rf) == C3_SHAPE):
         run.set_actions(G.ACTIONS)
         n_lit = max(run.n_slots, min(args.steps, 24))
@@ -881,7 +902,7 @@ def run_rank(args) -> int:
                                             "sources as this run)")
             except Exception:
                 pass
-        if not args.stub and not args.no_extras and world == 1:
+        if extras and world == 1:
             try:
                 out_line["end_to_end"] = end_to_end_leg(args, run)
             except Exception as e:                       # (a leg of its own: never costs the headline line)
@@ -896,6 +917,41 @@ def run_rank(args) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_OUT_CELLS = 1 << 22     # output cells sampled by --dump-outputs: 16 MB of values + 32 MB of their positions
+
+
+def dump_outputs(path, run, sl, coll):
+    """--dump-outputs: what a caller of the timed path receives from the step `sl` last took, as .npy files in float64
+    (records: every field, the 64-bit digest as two exact 32-bit halves) and float32 (output cells: all of them, or a sample
+    at fixed seeded positions when there are more than DUMP_OUT_CELLS).  Same arguments, same inputs, same files."""
+    from kafka_assigner_amd import abi
+    os.makedirs(path, exist_ok=True)
+    torch = run.torch
+    recs = {"scenario": (sl["all"] if coll else run.records_tensor(sl)).cpu().numpy().view(abi.SCENARIO_RESULT_DTYPE)}
+    if "tr" in sl:
+        recs["topic"] = sl["tr"].cpu().numpy().view(abi.TOPIC_RESULT_DTYPE)
+    for kind, rec in recs.items():
+        for f in rec.dtype.names:
+            if f == "reserved":
+                continue
+            if f == "digest":
+                np.save(os.path.join(path, f"{kind}_digest_hi.npy"), (rec[f] >> np.uint64(32)).astype(np.float64))
+                np.save(os.path.join(path, f"{kind}_digest_lo.npy"), (rec[f] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+            else:
+                np.save(os.path.join(path, f"{kind}_{f}.npy"), rec[f].astype(np.float64))
+    if "out" in sl:
+        n = sl["out"].numel()
+        if n > DUMP_OUT_CELLS:
+            idx = np.unique(np.random.default_rng(20260).integers(0, n, DUMP_OUT_CELLS))
+            cells = sl["out"].index_select(0, torch.from_numpy(idx).to(sl["out"].device)).cpu().numpy()
+        else:
+            idx, cells = np.arange(n), sl["out"].cpu().numpy()
+        if cells.dtype == np.int16:                                 # 16-bit cells are unsigned node indices (0xFFFF: pad)
+            cells = cells.view(np.uint16)
+        np.save(os.path.join(path, "out_cells.npy"), cells.astype(np.float32))
+        np.save(os.path.join(path, "out_cells_position.npy"), idx.astype(np.float64))
 
 
 def parity_and_cpu_baselines(args, run, slot_records, world):
@@ -936,7 +992,7 @@ def parity_and_cpu_baselines(args, run, slot_records, world):
             walls.append(time.perf_counter() - t1)
         return (sorted(walls)[len(walls) // 2] if walls else None), res
 
-    timed_cpu = not args.no_cpu and world == 1
+    timed_cpu = args.full and not args.no_cpu and world == 1
     b1_all, want = median_wall(oracle_solve, sub, 3 if timed_cpu else 0)      # B1 (and the checker's answers)
     b1_threads = want.threads_used
     ow = RF

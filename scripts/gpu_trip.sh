@@ -3,8 +3,8 @@
 # gpurun_out/NAME/ and prints one summary line, so that a trip's outcome can be read from the tail.
 #   tests      pytest -m gpu (the driver's round-end suite)
 #   smoke      __graft_entry__.smoke()
-#   bench      bench.py at the driver's command line (--gpus 1 --steps 20 --warmup 5)
-#   benchq     bench.py without the CPU / end-to-end / other-config legs (quick headline figure + counters)
+#   bench      bench.py --full at the driver's command line (--gpus 1 --steps 20 --warmup 5): every leg of the line
+#   benchq     bench.py --full without the CPU / end-to-end / other-config legs (quick headline figure, five repeats + counters)
 #   alone      one batch in flight (per-kernel durations free of other launches)
 #   configs    BASELINE configs[1], configs[3]'s share, configs[4] (x1 rack map on / off, x8, x64)
 #   stress     scripts/stress_inflight.py --suite 1000
@@ -38,11 +38,11 @@ for step in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log; tail -2 $O/smoke.log | cut -c1-200 ;;
     bench)
-      timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmdline.log 2>&1; echo "exit $?" >> $O/bench_driver_cmdline.log
+      timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmdline.log 2>&1; echo "exit $?" >> $O/bench_driver_cmdline.log
       echo "bench: value $(val value $O/bench_driver_cmdline.log) $(grep -o '"repeats": {[^}]*' $O/bench_driver_cmdline.log | cut -c1-260)"; tail -1 $O/bench_driver_cmdline.log | cut -c1-120
       grep -v '^{' $O/bench_driver_cmdline.log | tail -5 | cut -c1-300 ;;
     benchq)
-      timeout 600 python bench.py --no-cpu --check 0 --no-extras --stats $O/stats_default.json > $O/bench_quick.log 2>&1; echo "exit $?" >> $O/bench_quick.log
+      timeout 600 python bench.py --full --no-cpu --check 0 --no-extras --stats $O/stats_default.json > $O/bench_quick.log 2>&1; echo "exit $?" >> $O/bench_quick.log
       echo "benchq: value $(val value $O/bench_quick.log) $(grep -o '"values": \[[^]]*' $O/bench_quick.log | cut -c1-200)" ;;
     alone)
       timeout 300 python bench.py --no-cpu --check 0 --no-extras --repeats 1 --steps 10 --in-flight 1 --stats $O/stats_one_batch_in_flight.json > $O/bench_one_batch_in_flight.log 2>&1

@@ -173,3 +173,64 @@ def test_bench_collective_at_one_rank_over_gloo():
     assert "ONE rank" in cfg["collective"] and cfg["gathered_records_ok"] is True and cfg["allgather_alone_us"] > 0
     r = _run(["--stub", "--gpus", "1", "--steps", "2", "--warmup", "1", "--scenarios", "5", "--in-flight", "2"])
     assert r.returncode == 0 and _json_line(r.stdout)["config"]["collective"] == "none (1 GPU)"
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_legs():
+    """A plain run times --steps steps once and checks nothing; --full brings back the five repeats and the parity check of
+    every slot (an explicit flag still wins over either default)."""
+    import bench
+    a = bench.parse_args(["--steps", "7"])
+    assert (a.full, a.repeats, a.check) == (False, 1, 0)
+    a = bench.parse_args(["--full"])
+    assert (a.full, a.repeats, a.check) == (True, 5, -1)
+    a = bench.parse_args(["--repeats", "3", "--check", "2"])
+    assert (a.repeats, a.check) == (3, 2)
+    assert bench.parse_args(["--config", "4"]).check == 0 and bench.parse_args(["--config", "4", "--full"]).check == 2
+    line = _json_line(_run(["--stub", "--steps", "6", "--warmup", "2", "--scenarios", "5"]).stdout)
+    assert line["steps"] == 6 and line["repeats"]["n"] == 1 and line["cpu_baseline"] is None
+    assert abs(line["value"] - 5 * 6 / (line["ms_per_step"] * 6e-3)) < 1e-6 * line["value"]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_dump_outputs_writes_the_records_of_the_last_step(tmp_path, gpus):
+    """--dump-outputs DIR: every field of the records the timed path hands back, as float64 .npy files (the 64-bit digest as
+    two exact 32-bit halves); with two ranks the gathered records of both."""
+    import numpy as np
+    import bench
+    r = _run(["--stub", "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--scenarios", "5", "--in-flight", "2",
+              "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    _json_line(r.stdout)
+    want = bench.StubRun.expected_records(0, 5 * gpus)
+    for f in ("status", "fail_topic", "fail_partition", "moved_replicas", "moved_partitions"):
+        got = np.load(tmp_path / f"scenario_{f}.npy")
+        assert got.dtype == np.float64
+        np.testing.assert_array_equal(got, want[f].astype(np.float64))
+    hi, lo = (np.load(tmp_path / f"scenario_digest_{h}.npy").astype(np.uint64) for h in ("hi", "lo"))
+    np.testing.assert_array_equal((hi << np.uint64(32)) | lo, want["digest"])
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_what_the_checked_run_computes(tmp_path):
+    """On the HIP path at a small shape: a plain run reports the timed region alone, and its --dump-outputs files equal, file for
+    file, those of a second run with the same arguments under --full, whose parity check holds every slot's records against
+    the CPU solvers and slot 0's lists against the oracle (the inputs are seeded: same arguments, same inputs)."""
+    import numpy as np
+    argv = ["--gpus", "1", "--steps", "5", "--warmup", "1", "--scenarios", "64", "--partitions", "4000", "--brokers", "80",
+            "--racks", "8", "--in-flight", "3"]
+    dumps = []
+    for extra in ([], ["--full", "--repeats", "1", "--no-cpu", "--no-extras"]):
+        d = tmp_path / ("full" if extra else "plain")
+        r = _run(argv + extra + ["--dump-outputs", str(d)])
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        line = _json_line(r.stdout)
+        assert line["steps"] == 5 and line["repeats"]["n"] == 1 and line["ms_per_step"] > 0 and line.get("stub") is not True
+        assert line["config"]["parity_checked_slots"] == (3 if extra else 0)
+        dumps.append({p.name: np.load(p) for p in d.iterdir()})
+    plain, full = dumps
+    assert plain.keys() == full.keys() and {"out_cells.npy", "scenario_status.npy", "topic_status.npy"} <= plain.keys()
+    for name, a in plain.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a, full[name], err_msg=name)
+    assert plain["out_cells.npy"].size == 64 * 4000 * 3 and plain["scenario_status.npy"].size == 64

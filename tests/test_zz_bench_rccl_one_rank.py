@@ -22,7 +22,7 @@ def test_bench_steps_with_the_all_gather_on_a_one_rank_rccl_communicator():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--repeats", "2",
                         "--scenarios", "64", "--partitions", "4000", "--brokers", "80", "--racks", "8", "--in-flight", "4",
-                        "--no-extras", "--cpu-seconds", "1", "--rccl-at-1"],
+                        "--full", "--no-extras", "--cpu-seconds", "1", "--rccl-at-1"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
