@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define KAS_ABI_VERSION 5
+#define KAS_ABI_VERSION 6
 
 /* Longest replica list the kernels keep in registers: max(cur_width, rf) <= KAS_MAX_WIDTH. */
 #define KAS_MAX_WIDTH 8
@@ -325,6 +325,58 @@ int kas_solve_host16(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables
  * kas_plan_set_flags: no ticket form (KAS_PLAN_TICKET_ORDER takes the round form); KAS_PLAN_VERIFY_SAMPLE works as on int32 cells (round 6). */
 int kas_plan_create16(kas_ctx* ctx, const kas_batch_desc* batch, kas_plan** out_plan);
 int kas_solve_device16(kas_plan* plan, const kas_tables16* device_tables, void* hip_stream);
+
+/* ---- ABI v6: per-broker movement and leadership impact, computed on the device -------------------------------
+ * One streaming pass over the cur and out tables a solve used reduces every scenario to counters per broker, so that a
+ * what-if caller learns what each variant does to each broker without downloading its rows.  For each scenario, over each
+ * of its topics whose kas_topic_result.status == KAS_OK (failed and skipped topics contribute nothing), and each row p:
+ *   C = the first clen cells of cur[p] (clen = cur_len[p], or cur_width without a cur_len array),
+ *   O = the cells of out[p] up to the first pad (-1 in int32 cells, KAS_CELL16_NONE in 16-bit cells)
+ * (the rows of the movement counts moved_replicas / moved_partitions).  Per node b of the scenario's node table: */
+typedef struct kas_node_impact {
+  int32_t replicas_before;  /* cells c of C with c == b                                       */
+  int32_t replicas_after;   /* cells o of O with o == b                                       */
+  int32_t leaders_before;   /* rows with clen > 0 and C[0] == b                               */
+  int32_t leaders_after;    /* rows with olen > 0 and O[0] == b                               */
+  int32_t inbound;          /* cells o of O with o == b that are not in C (replicas to move in) */
+  int32_t outbound;         /* cells c of C with c == b that are not in O (replicas to give up) */
+  int32_t reserved[2];
+} kas_node_impact;
+
+/* Per scenario (every field 0 when the scenario has no nodes): */
+typedef struct kas_scenario_impact {
+  int32_t departed_replicas;  /* cells of C that name no node of the scenario: a broker outside the set, or
+                                 KAS_CELL16_NONE                                                    */
+  int32_t leaders_moved;      /* rows with olen > 0 and (clen == 0 or O[0] != C[0])                 */
+  int32_t max_inbound, max_outbound;              /* over the scenario's nodes                      */
+  int32_t min_replicas_after, max_replicas_after;
+  int32_t min_leaders_after, max_leaders_after;
+} kas_scenario_impact;
+
+/* Where the records go.  nodes: scenario s owns a block of n_nodes records at offset sum over s' < s of n_nodes(s'), in
+ * scenario order; record i of the block is node i of the scenario's (ascending) node table.  The offset does not depend on
+ * node_off: scenarios that share a node range still get blocks of their own.  scenarios: one record per scenario. */
+typedef struct kas_impact_tables {
+  kas_node_impact*     nodes;
+  kas_scenario_impact* scenarios;
+} kas_impact_tables;
+
+/* The impact of the plan's previous solve, from the tables that solve used (device pointers, device_impact too).
+ * Asynchronous, and ordered after that solve as solves of one plan are ordered (kas_solve_device); it writes every record
+ * of its outputs itself.  The Sigma over nodes of inbound is the scenario record's moved_replicas.  A scenario whose
+ * n_nodes x 24 bytes of counters do not fit the LDS next to the id lookup (about 6,000 brokers) counts in global scratch
+ * instead: same records, up to KAS_N_LIMIT brokers.  kas_impact_device16: the same for a plan of kas_plan_create16. */
+int kas_impact_device(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                      void* hip_stream);
+int kas_impact_device16(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                        void* hip_stream);
+
+/* Exactly kas_solve_host_select / kas_solve_host16 (select, n_select as there; n_select < 0: every row in place), plus the
+ * impact records in host memory.  n_select == 0: the records and the impact only, no rows come back — the what-if call. */
+int kas_solve_host_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                          const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact);
+int kas_solve_host16_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                            const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact);
 
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-KAS_ABI_VERSION = 5
+KAS_ABI_VERSION = 6
 KAS_MAX_WIDTH = 8
 KAS_CELL16_NONE = 0xFFFF      # 16-bit cells (kas_solve_host16): no such broker in cur, pad in out
 
@@ -162,6 +162,19 @@ SCENARIO_DESC_DTYPE = _np.dtype([
     ("n_nodes", "<i4"), ("topic_begin", "<i4"), ("topic_count", "<i4"), ("ctx_width", "<i4"),
     ("node_off", "<i8"), ("ctx_off", "<i8")])
 
+# ABI v6: the impact records (kas_node_impact / kas_scenario_impact) and where they go (kas_impact_tables)
+NODE_IMPACT_FIELDS = ("replicas_before", "replicas_after", "leaders_before", "leaders_after", "inbound", "outbound")
+SCENARIO_IMPACT_FIELDS = ("departed_replicas", "leaders_moved", "max_inbound", "max_outbound",
+                          "min_replicas_after", "max_replicas_after", "min_leaders_after", "max_leaders_after")
+NODE_IMPACT_DTYPE = _np.dtype([(f, "<i4") for f in NODE_IMPACT_FIELDS] + [("reserved", "<i4", (2,))])
+SCENARIO_IMPACT_DTYPE = _np.dtype([(f, "<i4") for f in SCENARIO_IMPACT_FIELDS])
+
+
+class ImpactTables(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("scenarios", C.c_void_p)]
+
+
+assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32
 assert TOPIC_RESULT_DTYPE.itemsize == C.sizeof(TopicResult) == 16
 assert SCENARIO_RESULT_DTYPE.itemsize == C.sizeof(ScenarioResult) == 32
 assert TOPIC_DESC_DTYPE.itemsize == C.sizeof(TopicDesc) == 64

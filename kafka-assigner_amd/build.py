@@ -12,8 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libkas_hip.so")
-SOURCES = ["kas_hip.hip"]
-HEADERS = ["kas_solver_body.h", "kas_order_wide.h", "kas_order_relax.h", "kas_plan_math.h", "kas_wave.h"]
+SOURCES = ["kas_hip.hip", "kas_impact.hip"]
+HEADERS = ["kas_solver_body.h", "kas_order_wide.h", "kas_order_relax.h", "kas_plan_math.h", "kas_wave.h", "kas_impact.h",
+           "kas_impact_body.h"]
 
 
 def hipcc() -> str:

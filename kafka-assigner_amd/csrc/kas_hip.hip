@@ -26,6 +26,7 @@
 #include "kas_abi.h"
 #include "kas_plan_math.h"
 #include "kas_solver_body.h"
+#include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -430,6 +431,7 @@ struct kas_ctx {
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasBuf h_tr_pin, h_sr_pin;            // pinned HOST staging of the result records (see kas_solve_host_locked)
+  KasBuf h_imp_nodes, h_imp_scen;       // the impact records of kas_solve_host_impact / 16 on the device
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
   uint64_t use_clock = 0;
   uint64_t host_calls = 0, host_plan_hits = 0, host_allocs = 0;
@@ -469,6 +471,14 @@ struct kas_plan {
   // kernel timing: event pairs recorded around every launch on the launch stream
   hipEvent_t ev_start[KAS_TIMER_SLOTS], ev_mid[KAS_TIMER_SLOTS], ev_stop[KAS_TIMER_SLOTS];
   int timer_next, timer_count;
+  // impact pass (ABI v6): the work list is built at the plan's first impact call and kept until the plan is rebuilt; plans
+  // that never ask own none of this
+  int impact_ready = 0;
+  KasImpactPlan impact;
+  KasBuf b_imp_items, b_imp_merge, b_imp_base, b_imp_roff, b_imp_region;
+  hipEvent_t ev_impact = nullptr;       // recorded behind the plan's last impact pass
+  hipStream_t impact_stream = nullptr;
+  int impact_pending = 0;               // ev_impact has been recorded
 };
 
 static int kas_buf_reserve(KasBuf* b, size_t bytes, uint64_t* allocs, const char* what) {
@@ -637,6 +647,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
   for (KasBuf* b : {&ctx->h_cur, &ctx->h_out, &ctx->h_aux, &ctx->h_ctx, &ctx->h_tr, &ctx->h_sr, &ctx->h_cur16, &ctx->h_out16}) kas_buf_free(b);
   for (KasBuf* b : {&ctx->h_tr_pin, &ctx->h_sr_pin}) { if (b->p) (void)hipHostFree(b->p); b->p = nullptr; b->cap = 0; }
+  for (KasBuf* b : {&ctx->h_imp_nodes, &ctx->h_imp_scen}) kas_buf_free(b);
   if (ctx->hevent) (void)hipEventDestroy(ctx->hevent);
   for (hipEvent_t ev : ctx->hev_up) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : ctx->hev_done) if (ev) (void)hipEventDestroy(ev);
@@ -665,6 +676,9 @@ void kas_plan_destroy(kas_plan* p) {
   (void)hipSetDevice(p->ctx->device);
   (void)hipStreamSynchronize(p->ctx->stream);
   if (p->last_slot >= 0) (void)hipEventSynchronize(p->ev_stop[p->last_slot]);
+  if (p->impact_pending) (void)hipEventSynchronize(p->ev_impact);
+  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region}) kas_buf_free(b);
+  if (p->ev_impact) (void)hipEventDestroy(p->ev_impact);
   for (KasBuf* b : {&p->b_scen, &p->b_topics, &p->b_node_id, &p->b_node_rack, &p->b_accmask_off, &p->b_accmask,
                     &p->b_orph_off, &p->b_orph, &p->b_perm, &p->b_stats, &p->b_ord_flag, &p->b_sp_hist, &p->b_sp_quota,
                     &p->b_sp_node, &p->b_sp_flag, &p->b_sp_oc, &p->b_p4s})
@@ -826,6 +840,8 @@ static int kas_plan_build(kas_plan* p, const kas_batch_desc* batch) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   // a rebuilt plan may still have its last solve in flight on some stream
   if (p->last_slot >= 0) KAS_HIP_TRY(hipEventSynchronize(p->ev_stop[p->last_slot]));
+  if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));   // (its work list is about to go)
+  p->impact_ready = 0; p->impact_pending = 0;
   p->shape = sh;
   p->Wc = sh.Wc; p->NW = sh.NW; p->G = sh.G;
   p->tickets = sh.tickets_ok; p->fused = sh.fused_ok;
@@ -1154,6 +1170,8 @@ static int kas_solve_device_impl(kas_plan* p, const kas_tables* t, void* hip_str
   // the plan's scratch serves one solve at a time: order this solve behind the previous one
   if (p->last_slot >= 0 && p->last_stream != st)
     KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->impact_pending && p->impact_stream != st)           // (... and behind an impact pass that reads the tables it rewrites)
+    KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
   p->last_stream = st;
   a.n_scenarios = p->n_scenarios; a.n_max = p->shape.n_max;
   a.idmap_entries = p->shape.idmap_entries; a.need_bsearch = p->shape.need_bsearch;
@@ -1282,6 +1300,95 @@ static int kas_solve_device_impl(kas_plan* p, const kas_tables* t, void* hip_str
   p->timer_next = (slot + 1) % KAS_TIMER_SLOTS;
   if (p->timer_count < KAS_TIMER_SLOTS) p->timer_count += 1;
   return KAS_E_OK;
+}
+
+// ---- the impact pass (ABI v6; kernels: kas_impact.hip) ----------------------------------------------------------------
+// The plan's work list: built at its first impact call from the batch in host memory (`hb`, the host path's slice) or, without
+// one, from the descriptors the plan holds on the device (read back once), uploaded, and kept until the plan is rebuilt.
+static int kas_impact_prepare(kas_plan* p, const kas_batch_desc* hb) {
+  if (p->impact_ready) return KAS_E_OK;
+  std::vector<kas_scenario_desc> sc;
+  std::vector<kas_topic_desc> tp;
+  kas_batch_desc b;
+  memset(&b, 0, sizeof(b));
+  if (hb) {
+    b = *hb;
+  } else {
+    sc.resize((size_t)p->n_scenarios); tp.resize((size_t)p->n_topics);
+    if (!sc.empty()) KAS_HIP_TRY(hipMemcpy(sc.data(), p->b_scen.p, sizeof(kas_scenario_desc) * sc.size(), hipMemcpyDeviceToHost));
+    if (!tp.empty()) KAS_HIP_TRY(hipMemcpy(tp.data(), p->b_topics.p, sizeof(kas_topic_desc) * tp.size(), hipMemcpyDeviceToHost));
+    b.n_scenarios = p->n_scenarios; b.n_topics = p->n_topics; b.scenarios = sc.data(); b.topics = tp.data();
+  }
+  KasImpactPlan& ip = p->impact;
+  kas_impact_plan_build(&b, p->shape.n_max, p->shape.idmap_entries, p->shape.need_bsearch, p->cells16, -1, kas_impact_rows_per_item(&b), &ip);
+  struct Up { KasBuf* b; const void* src; size_t bytes; const char* what; };
+  const Up ups[] = {
+      {&p->b_imp_items, ip.items.data(), sizeof(KasImpactItem) * ip.items.size(), "impact work list"},
+      {&p->b_imp_merge, ip.merge_scen.data(), sizeof(int32_t) * ip.merge_scen.size(), "impact merge list"},
+      {&p->b_imp_base, ip.node_base.data(), sizeof(int64_t) * ip.node_base.size(), "impact record offsets"},
+      {&p->b_imp_roff, ip.region_off.data(), sizeof(int64_t) * ip.region_off.size(), "impact counter offsets"},
+  };
+  int rc;
+  for (const Up& u : ups) {
+    if ((rc = kas_buf_reserve(u.b, u.bytes, p->allocs, u.what)) != KAS_E_OK) return rc;
+    if (u.bytes > 0) KAS_HIP_TRY(hipMemcpy(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice));
+  }
+  if ((rc = kas_buf_reserve(&p->b_imp_region, sizeof(int32_t) * (size_t)(ip.region_ints + 1), p->allocs, "impact counters")) != KAS_E_OK)
+    return rc;
+  if (!p->ev_impact) KAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_impact, hipEventDisableTiming));
+  p->impact_ready = 1;
+  return KAS_E_OK;
+}
+
+// The impact of the plan's previous solve, from the tables `t` it used, into `imp` (device pointers), on `st`.
+static int kas_impact_impl(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, hipStream_t st, const kas_batch_desc* hb) {
+  if (p->n_scenarios == 0) return KAS_E_OK;
+  if (!imp->scenarios || !t->out || !t->topic_results || (p->shape.cur_need > 0 && !t->cur) || (p->shape.aux_need > 0 && !t->aux))
+    return set_error(KAS_E_INVALID_ARG, "a table the impact pass reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  int rc = kas_impact_prepare(p, hb);
+  if (rc != KAS_E_OK) return rc;
+  const KasImpactPlan& ip = p->impact;
+  if (ip.nodes_total > 0 && !imp->nodes) return set_error(KAS_E_INVALID_ARG, "kas_impact_tables.nodes == NULL");
+  // ordered behind the plan's previous solve, and behind its previous impact pass (the counters are the plan's)
+  if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->impact_pending && p->impact_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
+  if (ip.region_ints > 0) KAS_HIP_TRY(hipMemsetAsync(p->b_imp_region.p, 0, sizeof(int32_t) * (size_t)ip.region_ints, st));
+  KasImpactLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.scen = (const kas_scenario_desc*)p->b_scen.p; a.topics = (const kas_topic_desc*)p->b_topics.p;
+  a.node_id = (const int32_t*)p->b_node_id.p;
+  a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.topic_results = t->topic_results;
+  a.items = (const KasImpactItem*)p->b_imp_items.p; a.merge_scen = (const int32_t*)p->b_imp_merge.p;
+  a.node_base = (const int64_t*)p->b_imp_base.p; a.region_off = (const int64_t*)p->b_imp_roff.p;
+  a.region = (int32_t*)p->b_imp_region.p;
+  a.nodes = imp->nodes; a.scenarios = imp->scenarios;
+  a.n_items = (int32_t)ip.items.size(); a.n_merge = (int32_t)ip.merge_scen.size();
+  a.node_cap = ip.node_cap; a.idmap_entries = p->shape.idmap_entries;
+  a.off_look = ip.off_look; a.off_red = ip.off_red; a.lds_bytes = ip.lds_bytes;
+  a.cells16 = p->cells16;
+  const int e = kas_impact_launch(&a, p->Wc, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("impact pass: ") + hipGetErrorString((hipError_t)e));
+  KAS_HIP_TRY(hipEventRecord(p->ev_impact, st));
+  p->impact_stream = st;
+  p->impact_pending = 1;
+  return KAS_E_OK;
+}
+
+int kas_impact_device(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, void* hip_stream) {
+  if (!p || !t || !imp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_impact_device16");
+  return kas_impact_impl(p, t, imp, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
+}
+
+int kas_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, void* hip_stream) {
+  if (!p || !t16 || !imp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_impact_device16 needs a plan of kas_plan_create16");
+  kas_tables t;
+  memset(&t, 0, sizeof(t));
+  t.cur = reinterpret_cast<const int32_t*>(t16->cur); t.out = reinterpret_cast<int32_t*>(t16->out);
+  t.aux = t16->aux; t.ctx = t16->ctx; t.topic_results = t16->topic_results; t.scenario_results = t16->scenario_results;
+  return kas_impact_impl(p, &t, imp, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
 }
 
 static int kas_plan_times(kas_plan* p, double* fill_us, double* order_us, int* launches) {
@@ -1680,7 +1787,7 @@ struct KasCells16 {
 #define KAS_HOST_SPLIT_MAX 3
 
 static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select,
-                                 int32_t n_select, const KasCells16* c16 = nullptr) {
+                                 int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   const bool all_rows = n_select < 0;
@@ -1755,6 +1862,17 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
   if ((rc = kas_host_pinned(ctx, &ctx->h_tr_pin, sizeof(kas_topic_result) * (size_t)(T + 1))) != KAS_E_OK) return rc;
   if ((rc = kas_host_pinned(ctx, &ctx->h_sr_pin, sizeof(kas_scenario_result) * (size_t)(S + 1))) != KAS_E_OK) return rc;
+  // impact records (kas_solve_host_impact): scenario s's node block starts at the sum of the n_nodes before it
+  std::vector<int64_t> imp_base;
+  if (himp) {
+    imp_base.assign((size_t)S + 1, 0);
+    for (int64_t s = 0; s < S; ++s) imp_base[(size_t)s + 1] = imp_base[(size_t)s] + (batch->scenarios[s].n_nodes > 0 ? batch->scenarios[s].n_nodes : 0);
+    if ((S > 0 && !himp->scenarios) || (imp_base[(size_t)S] > 0 && !himp->nodes))
+      return set_error(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
+    if ((rc = kas_host_buf(ctx, &ctx->h_imp_nodes, sizeof(kas_node_impact) * (size_t)(imp_base[(size_t)S] + 1))) != KAS_E_OK ||
+        (rc = kas_host_buf(ctx, &ctx->h_imp_scen, sizeof(kas_scenario_impact) * (size_t)(S + 1))) != KAS_E_OK)
+      return rc;
+  }
   kas_topic_result* p_tr = (kas_topic_result*)ctx->h_tr_pin.p;
   kas_scenario_result* p_sr = (kas_scenario_result*)ctx->h_sr_pin.p;
   int32_t* d_cur = need32 ? (int32_t*)ctx->h_cur.p - full.cur_lo : nullptr;
@@ -1878,6 +1996,13 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (native16) { d.cur = reinterpret_cast<const int32_t*>(d_cur16); d.out = reinterpret_cast<int32_t*>(d_out16); }
     const int src = kas_solve_device_impl(c.plan, &d, st);
     if (src != KAS_E_OK) { fail_rc = src; break; }
+    if (himp) {                                                // the impact pass on the range's solve stream, behind its solve
+      kas_impact_tables di;
+      di.nodes = (kas_node_impact*)ctx->h_imp_nodes.p + imp_base[(size_t)c.lo];
+      di.scenarios = (kas_scenario_impact*)ctx->h_imp_scen.p + c.lo;
+      const int irc = kas_impact_impl(c.plan, &d, &di, st, &c.bd);
+      if (irc != KAS_E_OK) { fail_rc = irc; break; }
+    }
     if (c16 && !native16 && all_rows && c.out_hi > c.out_lo) {
       const int64_t n = c.out_hi - c.out_lo;
       // (into the staging buffer, not into the caller's pinned pool: the kernel's stores over the link ran at 20 GB/s —
@@ -1917,6 +2042,12 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
       }
     }
   }
+  if (himp) {
+    if (imp_base[(size_t)S] > 0)
+      hip_ok(hipMemcpyAsync(himp->nodes, ctx->h_imp_nodes.p, sizeof(kas_node_impact) * (size_t)imp_base[(size_t)S], hipMemcpyDeviceToHost, s0), "download node impact");
+    if (S > 0)
+      hip_ok(hipMemcpyAsync(himp->scenarios, ctx->h_imp_scen.p, sizeof(kas_scenario_impact) * (size_t)S, hipMemcpyDeviceToHost, s0), "download scenario impact");
+  }
   hip_ok(hipStreamSynchronize(s0), "hipStreamSynchronize");
   return he == hipSuccess ? KAS_E_OK : fail_rc;
 }
@@ -1941,6 +2072,26 @@ int kas_solve_host16(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables
   c16.cur = h16->cur; c16.out = h16->out;
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16);
+}
+
+int kas_solve_host_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select, int32_t n_select,
+                          const kas_impact_tables* himp) {
+  if (!ctx || !batch || !h || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, select, n_select, nullptr, himp);
+}
+
+int kas_solve_host16_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
+                            const kas_impact_tables* himp) {
+  if (!ctx || !batch || !h16 || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  kas_tables h;                                                // everything but the cells is the int32 call's
+  memset(&h, 0, sizeof(h));
+  h.aux = h16->aux; h.ctx = h16->ctx; h.topic_results = h16->topic_results; h.scenario_results = h16->scenario_results;
+  h.cur_len = h16->cur_len; h.out_len = h16->out_len; h.aux_len = h16->aux_len; h.ctx_len = h16->ctx_len;
+  KasCells16 c16;
+  c16.cur = h16->cur; c16.out = h16->out;
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp);
 }
 
 int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_desc* batch, const kas_tables* h) {

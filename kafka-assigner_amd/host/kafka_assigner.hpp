@@ -63,6 +63,16 @@ struct Context {
   std::map<int, std::map<int, int>> counter;
 };
 
+// What a run's reassignment does to each broker (the CLI's --print_impact; kas_node_impact / kas_scenario_impact of
+// include/kas_abi.h, ABI v6), summed over the run's topics: the per-broker counters of separate solves add up.
+struct BrokerImpact {
+  int64_t replicas_before = 0, replicas_after = 0, leaders_before = 0, leaders_after = 0, inbound = 0, outbound = 0;
+};
+struct RunImpact {
+  std::map<int, BrokerImpact> brokers;
+  int64_t departed_replicas = 0, leaders_moved = 0, moved_replicas = 0;
+};
+
 // One process-wide device context (a HIP stream on device 0), created on first use.
 inline kas_ctx* deviceContext() {
   static kas_ctx* ctx = nullptr;
@@ -79,7 +89,7 @@ class KafkaAssignmentStrategy {
   static std::map<int, std::vector<int>> getRackAwareAssignment(
       const std::string& topicName, const std::map<int, std::vector<int>>& currentAssignment,
       const std::map<int, std::string>& nodeRackAssignment, const std::set<int>& nodes,
-      const std::set<int>& partitions, int replicationFactor, Context* context) {
+      const std::set<int>& partitions, int replicationFactor, Context* context, RunImpact* impact = nullptr) {
     const int32_t N = (int32_t)nodes.size();
     std::vector<int32_t> node_id(nodes.begin(), nodes.end());           // ascending (KAS:78)
     std::vector<int32_t> node_rack(N);
@@ -153,14 +163,20 @@ class KafkaAssignmentStrategy {
     t.cur_len = (int64_t)P * cw; t.out_len = (int64_t)P * ow; t.aux_len = 3 * (int64_t)P;
     t.ctx_len = context ? (int64_t)N * KAS_MAX_WIDTH : 0;
     int rc;
+    // with `impact`: the same call plus the topic's impact records (kas_solve_host_impact / 16)
+    std::vector<kas_node_impact> node_impact(impact ? (size_t)N + 1 : 0);
+    kas_scenario_impact scen_impact{};
+    kas_impact_tables it{};
+    it.nodes = node_impact.data(); it.scenarios = &scen_impact;
     if (cells16) {
       kas_tables16 t16{};
       t16.cur = cur16.data(); t16.out = out16.data(); t16.aux = t.aux; t16.ctx = t.ctx;
       t16.topic_results = &tr; t16.scenario_results = &sr;
       t16.cur_len = t.cur_len; t16.out_len = t.out_len; t16.aux_len = t.aux_len; t16.ctx_len = t.ctx_len;
-      rc = kas_solve_host16(deviceContext(), &bd, &t16, nullptr, -1);
+      rc = impact ? kas_solve_host16_impact(deviceContext(), &bd, &t16, nullptr, -1, &it)
+                  : kas_solve_host16(deviceContext(), &bd, &t16, nullptr, -1);
     } else {
-      rc = kas_solve_host(deviceContext(), &bd, &t);
+      rc = impact ? kas_solve_host_impact(deviceContext(), &bd, &t, nullptr, -1, &it) : kas_solve_host(deviceContext(), &bd, &t);
     }
     if (rc != KAS_E_OK) throw SolverError(std::string(kas_strerror(rc)) + ": " + kas_last_error());
 
@@ -178,6 +194,18 @@ class KafkaAssignmentStrategy {
                                     std::to_string(replicationFactor) + ") than available brokers!");
       default:
         throw SolverError(std::string("solver status ") + kas_status_string(tr.status));
+    }
+    if (impact) {
+      for (int32_t i = 0; i < N; ++i) {
+        BrokerImpact& b = impact->brokers[node_id[i]];
+        const kas_node_impact& r = node_impact[(size_t)i];
+        b.replicas_before += r.replicas_before; b.replicas_after += r.replicas_after;
+        b.leaders_before += r.leaders_before; b.leaders_after += r.leaders_after;
+        b.inbound += r.inbound; b.outbound += r.outbound;
+      }
+      impact->departed_replicas += scen_impact.departed_replicas;
+      impact->leaders_moved += scen_impact.leaders_moved;
+      impact->moved_replicas += tr.moved_replicas;
     }
     std::map<int, std::vector<int>> result;
     {
@@ -215,7 +243,7 @@ class KafkaTopicAssigner {
   std::map<int, std::vector<int>> generateAssignment(
       const std::string& topic, const std::map<int, std::vector<int>>& currentAssignment,
       const std::set<int>& brokers, const std::map<int, std::string>& rackAssignment,
-      int desiredReplicationFactor) {
+      int desiredReplicationFactor, RunImpact* impact = nullptr) {
     int replicationFactor = desiredReplicationFactor;                   // KTA:49
     std::set<int> partitions;
     for (auto& e : currentAssignment) {                                 // KTA:50-62
@@ -234,7 +262,7 @@ class KafkaTopicAssigner {
       throw IllegalStateException("Topic " + topic + " has a higher replication factor (" +
                                   std::to_string(replicationFactor) + ") than available brokers!");
     return KafkaAssignmentStrategy::getRackAwareAssignment(topic, currentAssignment, rackAssignment, brokers,
-                                                           partitions, replicationFactor, &assignmentContext);
+                                                           partitions, replicationFactor, &assignmentContext, impact);
   }
 
   Context assignmentContext;

@@ -133,9 +133,32 @@ std::set<int> hostnamesToIds(const Snapshot& s, const std::set<std::string>& hos
 
 }  // namespace
 
+// --print_impact: one JSON document, per broker its counters (kas_node_impact) summed over the run's topics, and the run's totals
+static std::string impactJson(const kas::RunImpact& imp) {
+  auto arr = mjson::make(mjson::Value::Array);
+  for (auto& e : imp.brokers) {
+    auto o = mjson::make(mjson::Value::Object);
+    o->o.emplace_back("id", mjson::integer(e.first));
+    o->o.emplace_back("replicas_before", mjson::integer(e.second.replicas_before));
+    o->o.emplace_back("replicas_after", mjson::integer(e.second.replicas_after));
+    o->o.emplace_back("leaders_before", mjson::integer(e.second.leaders_before));
+    o->o.emplace_back("leaders_after", mjson::integer(e.second.leaders_after));
+    o->o.emplace_back("inbound", mjson::integer(e.second.inbound));
+    o->o.emplace_back("outbound", mjson::integer(e.second.outbound));
+    arr->a.push_back(o);
+  }
+  auto doc = mjson::make(mjson::Value::Object);
+  doc->o.emplace_back("brokers", arr);
+  doc->o.emplace_back("departed_replicas", mjson::integer(imp.departed_replicas));
+  doc->o.emplace_back("leaders_moved", mjson::integer(imp.leaders_moved));
+  doc->o.emplace_back("moved_replicas", mjson::integer(imp.moved_replicas));
+  return mjson::dump(doc);
+}
+
 int main(int argc, char** argv) {
   std::string snapshot, mode, brokerIds, brokerHosts, hostsToRemove, topicsArg;
   bool haveIds = false, haveHosts = false, haveTopics = false, disableRack = false, haveZk = false;
+  bool printImpact = false;                  // --print_impact (not the reference's): what the reassignment does to each broker
   int desiredRf = -1;
   bool bad = false;
   for (int i = 1; i < argc; ++i) {
@@ -151,6 +174,7 @@ int main(int argc, char** argv) {
     else if (a == "--topics") { val(topicsArg); haveTopics = true; }
     else if (a == "--desired_replication_factor") { val(tmp); try { desiredRf = std::stoi(tmp); } catch (...) { bad = true; } }
     else if (a == "--disable_rack_awareness") disableRack = true;
+    else if (a == "--print_impact") printImpact = true;
     else bad = true;
   }
   (void)haveZk;
@@ -212,13 +236,16 @@ int main(int argc, char** argv) {
 
     std::map<std::string, std::map<int, std::vector<int>>> finalAssignment;
     kas::KafkaTopicAssigner assigner;                                    // ONE Context for the run (KAG:172)
+    kas::RunImpact impact;
+    for (int b : brokers) impact.brokers[b];                             // (every broker of the run, also without topics)
     for (auto& topic : topics) {                                         // KAG:173-184
       auto it = snap.assignment.find(topic);
       static const std::map<int, std::vector<int>> none;
       finalAssignment[topic] = assigner.generateAssignment(topic, it != snap.assignment.end() ? it->second : none,
-                                                           brokers, rackAssignment, desiredRf);
+                                                           brokers, rackAssignment, desiredRf, printImpact ? &impact : nullptr);
     }
     std::cout << "NEW ASSIGNMENT:\n" << reassignmentJson(topics, finalAssignment) << std::endl;       // KAG:185-186
+    if (printImpact) std::cout << "REASSIGNMENT IMPACT:\n" << impactJson(impact) << std::endl;
     return 0;
   } catch (const kas::IllegalStateException& e) {
     fprintf(stderr, "Exception in thread \"main\" java.lang.IllegalStateException: %s\n", e.what());

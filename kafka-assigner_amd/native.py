@@ -26,6 +26,7 @@ SYMBOLS = [
     "kas_plan_describe", "kas_ctx_host_stats", "kas_solve_host_select", "kas_host_alloc", "kas_host_free",
     "kas_shard_range", "kas_batch_slice", "kas_solve_host_sharded", "kas_ctx_lds_lane_order", "kas_solve_host16",
     "kas_plan_create16", "kas_solve_device16", "kas_resolve_replication_factor", "kas_failure_text",
+    "kas_impact_device", "kas_impact_device16", "kas_solve_host_impact", "kas_solve_host16_impact",
 ]
 
 _LIB = None
@@ -110,6 +111,16 @@ def load():
                                                  C.POINTER(abi.RfResult)]
     L.kas_failure_text.restype = C.c_int
     L.kas_failure_text.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int]
+    L.kas_impact_device.restype = C.c_int
+    L.kas_impact_device.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p]
+    L.kas_impact_device16.restype = C.c_int
+    L.kas_impact_device16.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p]
+    L.kas_solve_host_impact.restype = C.c_int
+    L.kas_solve_host_impact.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables),
+                                        C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.ImpactTables)]
+    L.kas_solve_host16_impact.restype = C.c_int
+    L.kas_solve_host16_impact.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables),
+                                          C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.ImpactTables)]
     if L.kas_abi_version() != abi.KAS_ABI_VERSION:
         raise ImportError("libkas_hip.so ABI version mismatch")
     _LIB = L
@@ -209,6 +220,16 @@ class Plan:
         t.topic_results = topic_results or None; t.scenario_results = scenario_results or None
         fn = self._lib.kas_solve_device16 if self.cells16 else self._lib.kas_solve_device
         _check(fn(self._h, C.byref(t), C.c_void_p(stream) if stream else None))
+
+    def impact_device(self, cur: int, out: int, topic_results: int, nodes: int, scenarios: int, aux: int = 0,
+                      stream: int = 0):
+        """kas_impact_device / 16: the impact of this plan's previous solve, from the tables it used, into the device arrays
+        `nodes` (kas_node_impact [sum of n_nodes]) and `scenarios` (kas_scenario_impact [S]).  Raw device pointers (int)."""
+        t = abi.Tables()
+        t.cur = cur or None; t.out = out or None; t.aux = aux or None; t.topic_results = topic_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        fn = self._lib.kas_impact_device16 if self.cells16 else self._lib.kas_impact_device
+        _check(fn(self._h, C.byref(t), C.byref(imp), C.c_void_p(stream) if stream else None))
 
     def set_flags(self, flags: int):
         _check(self._lib.kas_plan_set_flags(self._h, flags))
@@ -318,6 +339,44 @@ def solve_host16(fb: FlatBatch, ctx: Optional[DeviceContext] = None, select=None
                               None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int32)),
                               -1 if sel is None else int(sel.size)))
     return ho
+
+
+def impact_arrays(fb: FlatBatch):
+    """Zeroed host arrays for the impact records of `fb`: (nodes NODE_IMPACT_DTYPE [sum of n_nodes], scenarios
+    SCENARIO_IMPACT_DTYPE [S]); scenario s's block of nodes starts at node_blocks(fb)[s]."""
+    n = int(np.clip(fb.scen["n_nodes"], 0, None).sum())
+    return (np.zeros(max(n, 1), dtype=abi.NODE_IMPACT_DTYPE)[:n],
+            np.zeros(max(fb.n_scenarios, 1), dtype=abi.SCENARIO_IMPACT_DTYPE)[:fb.n_scenarios])
+
+
+def node_blocks(fb: FlatBatch) -> np.ndarray:
+    """int64 [S + 1]: where each scenario's block of node impact records starts (and the total behind the last)."""
+    return np.concatenate([[0], np.cumsum(np.clip(fb.scen["n_nodes"], 0, None).astype(np.int64))]).astype(np.int64)
+
+
+def solve_host_impact(fb: FlatBatch, select=None, cells16: bool = False, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_impact / kas_solve_host16_impact: the host call plus the per-broker impact of every scenario.
+    select=None: every row in place (HostOutputs.out is the whole out pool); a list of scenario indices: their rows, packed
+    (kas_solve_host_select); an empty list: no rows at all, the what-if call.  cells16: 16-bit node-index cells
+    (HostOutputs.out is then uint16).  Returns (HostOutputs, nodes, scenarios) — see impact_arrays."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    out_len = None if sel is None else selected_out_len(fb, sel)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)
+        t, ho = host_tables16(fb, cur16, out_len=out_len)
+    else:
+        t, ho = host_tables(fb, out_len=out_len)
+    nodes, scen = impact_arrays(fb)
+    imp = abi.ImpactTables(nodes.ctypes.data if nodes.size else None, scen.ctypes.data if scen.size else None)
+    fn = L.kas_solve_host16_impact if cells16 else L.kas_solve_host_impact
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
+              -1 if sel is None else int(sel.size), C.byref(imp)))
+    return ho, nodes, scen
 
 
 def solve_host_sharded(fb: FlatBatch, ctxs) -> HostOutputs:

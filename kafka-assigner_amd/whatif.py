@@ -10,6 +10,10 @@ the same rows), so S variants cost S out tables but one cur table.
     plan = WhatIf(brokers={id: rack or None}, topics={"t": {partition: [replicas]}})
     results = plan.solve([Variant(remove=[5]), Variant(add={9: "c"}), Variant(rack_aware=False)])
     results[0].moved_replicas, results[0].assignment("t")
+
+With impact=True the same call also reduces every variant, on the GPU, to what it does to each broker (include/kas_abi.h,
+ABI v6): results[0].broker_impact() -> {broker: {"inbound": ..., ...}}, results[0].max_inbound, ...  rows=False leaves the
+variants' rows on the device (kas_solve_host_impact with n_select = 0): only records come back.
 """
 from __future__ import annotations
 
@@ -41,9 +45,20 @@ class VariantResult:
     moved_replicas: int
     moved_partitions: int
     digest: int
+    # impact=True (kas_scenario_impact); None without it
+    departed_replicas: Optional[int] = None
+    leaders_moved: Optional[int] = None
+    max_inbound: Optional[int] = None
+    max_outbound: Optional[int] = None
+    min_replicas_after: Optional[int] = None
+    max_replicas_after: Optional[int] = None
+    min_leaders_after: Optional[int] = None
+    max_leaders_after: Optional[int] = None
     _plan: "WhatIf" = field(repr=False, default=None)
     _index: int = field(repr=False, default=0)
     _out: np.ndarray = field(repr=False, default=None)
+    _nodes: np.ndarray = field(repr=False, default=None)      # this variant's block of kas_node_impact records
+    _node_ids: np.ndarray = field(repr=False, default=None)
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -54,7 +69,16 @@ class VariantResult:
 
     def assignment(self, topic: str) -> Dict[int, List[int]]:
         """partition -> new replica list of `topic` under this variant."""
+        if self._out is None:
+            raise ValueError("solve(..., rows=False) downloaded no rows: solve with rows=True to read an assignment")
         return self._plan._rows(self._index, topic, self._out)
+
+    def broker_impact(self) -> Dict[int, Dict[str, int]]:
+        """broker id -> {replicas_before, replicas_after, leaders_before, leaders_after, inbound, outbound} under this
+        variant, over every topic that was solved (solve(..., impact=True))."""
+        if self._nodes is None:
+            raise ValueError("no impact records: solve with impact=True")
+        return {int(b): {f: int(r[f]) for f in abi.NODE_IMPACT_FIELDS} for b, r in zip(self._node_ids, self._nodes)}
 
 
 class WhatIf:
@@ -120,25 +144,41 @@ class WhatIf:
                          ctx=np.zeros(0, np.int32), out_len=out_off)
 
     # ---- solve ---------------------------------------------------------------------------------
-    def solve(self, variants: Sequence[Variant], solve_fn=None) -> List[VariantResult]:
-        """Solve every variant in one batch (default: the HIP path through the C ABI)."""
-        if solve_fn is None:
-            from . import native
-            solve_fn = native.solve_host
+    def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True) -> List[VariantResult]:
+        """Solve every variant in one batch (default: the HIP path through the C ABI).
+        impact=True: also the per-broker impact of every variant, computed on the GPU (kas_solve_host_impact).
+        rows=False: no variant's rows come back (kas_solve_host_select / kas_solve_host_impact with n_select = 0) — the
+        records and the impact only; assignment() then raises."""
+        from . import native
         fb = self.flat_batch(variants)
-        ho = solve_fn(fb)
+        nodes = scen_imp = None
+        if impact:
+            if solve_fn is not None:
+                raise ValueError("impact=True takes the library's own host call (no solve_fn)")
+            ho, nodes, scen_imp = native.solve_host_impact(fb, select=None if rows else [])
+        elif not rows:
+            if solve_fn is not None:
+                raise ValueError("rows=False takes the library's own host call (no solve_fn)")
+            ho = native.solve_host_select(fb, [])
+        else:
+            ho = (solve_fn or native.solve_host)(fb)
         self._fb = fb
-        T = len(self.topic_names)
+        base = native.node_blocks(fb)
         res = []
         for s, v in enumerate(variants):
             sr = ho.scenario_results[s]
             ft = int(sr["fail_topic"])
+            extra = {}
+            if impact:
+                extra = {f: int(scen_imp[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
+                off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
+                extra.update(_nodes=nodes[base[s]:base[s + 1]], _node_ids=fb.node_id[off:off + n])
             res.append(VariantResult(label=v.label, status=int(sr["status"]),
                                      fail_topic=self.topic_names[ft] if ft >= 0 else None,
                                      fail_partition=int(sr["fail_partition"]),
                                      moved_replicas=int(sr["moved_replicas"]),
                                      moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]),
-                                     _plan=self, _index=s, _out=ho.out))
+                                     _plan=self, _index=s, _out=ho.out if rows else None, **extra))
         return res
 
     def _rows(self, s: int, topic: str, out: np.ndarray) -> Dict[int, List[int]]:
