@@ -4,6 +4,7 @@
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -13,8 +14,6 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libkas_hip.so")
 SOURCES = ["kas_hip.hip", "kas_impact.hip"]
-HEADERS = ["kas_solver_body.h", "kas_order_wide.h", "kas_order_relax.h", "kas_plan_math.h", "kas_wave.h", "kas_impact.h",
-           "kas_impact_body.h"]
 
 
 def hipcc() -> str:
@@ -27,7 +26,8 @@ def hipcc() -> str:
 def is_stale() -> bool:
     if not os.path.exists(LIB):
         return True
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, "include", "kas_abi.h")]
+    # (every source and header in the directory: a new header cannot be forgotten)
+    deps = glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(ROOT, "include", "kas_abi.h")]
     return os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps)
 
 

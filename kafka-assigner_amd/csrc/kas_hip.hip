@@ -26,6 +26,7 @@
 #include "kas_abi.h"
 #include "kas_plan_math.h"
 #include "kas_solver_body.h"
+#include "kas_launch_plan.h"   // which kernels a solve launches: the resolver the emulator shares
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
 
 // ---------------------------------------------------------------------------------------------
@@ -43,7 +44,7 @@
 // solve) deals them to its workgroups round-robin BY RANK among the flagged ones (kas::fill_block, kas_solver_body.h) — a tenth of
 // 1000 scenarios handed back is a hundred workgroups with one scenario each, not 256 of which some hold three (round 6: 25.9 -> 15 ms
 // for such a batch, scripts/handback_probe.py) — and workgroup 0 leaves their number where the plan sizes its next such launch
-// (KasLaunch::handback, kas_plan_back_grid).
+// (KasLaunch::handback, kas_back_grid in kas_launch_plan.h).
 template <int W, int NW>
 __global__ __launch_bounds__(64 * NW, KAS_FILL_MIN_WAVES) void kas_fill_kernel(KasLaunch a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char kas_lds[];
@@ -70,9 +71,6 @@ __global__ __launch_bounds__(256, KAS_SLIM_MIN_WAVES) void kas_fill_slim_kernel(
   for (int32_t s = (int32_t)blockIdx.x; s < a.n_scenarios; s += (int32_t)gridDim.x)
     kas::fill_scenario<W, 4, true, M32 ? 1 : 0>(a, s, kas_lds);
 }
-static void (*kas_fill_slim_m32())(KasLaunch) { return kas_fill_slim_kernel<3, true>; }
-#define KAS_FILL_BACK_GRID 256u
-#define KAS_FILL_BACK_GRID_STEP 64u
 
 // min waves per SIMD of the ticket-form order kernel (0 = whatever the allocation comes to: 92 VGPRs, 5)
 #ifndef KAS_ORDER_MIN_WAVES
@@ -106,9 +104,6 @@ __global__ __launch_bounds__(64) void kas_order_round_kernel(KasLaunch a) {
 // polls — alone that is slower (fill + first fit 1.39 ms per 1000 scenarios against 1.07 ms inside the fill workgroup, 1.09 with
 // four wavefronts here), with eight batches in flight it is the fastest (672k scenarios/s in a 20-step region against 617k
 // inside the fill workgroup, 620k with four wavefronts, 646k with two: experiments/README.md)
-#ifndef KAS_P4_KERNEL_WAVES
-#define KAS_P4_KERNEL_WAVES 1
-#endif
 // (M32: the instance for launches with dword mid rows, KAS_FLAG_MID32 — the layout is a constant of either instance)
 template <int W, bool M32 = false>
 __global__ __launch_bounds__(64 * KAS_P4_KERNEL_WAVES) void kas_p4_kernel(KasLaunch a) {
@@ -116,7 +111,6 @@ __global__ __launch_bounds__(64 * KAS_P4_KERNEL_WAVES) void kas_p4_kernel(KasLau
   if constexpr (KAS_P4_PRIO > 0) kasw::set_priority<KAS_P4_PRIO>();
   kas::p4_scenario<W, KAS_P4_KERNEL_WAVES, false, (W == 3 && M32) ? 1 : 0>(a, (int32_t)blockIdx.x, kas_lds);
 }
-static void (*kas_p4_m32())(KasLaunch) { return kas_p4_kernel<3, true>; }
 
 // Self-test of the one hardware property the relaxation form of P5 and the fill's quota draw rely on and the ISA documents do
 // not state: the LDS serves the lanes of ONE ds_add_rtn instruction that name the same word in ascending lane order, so
@@ -178,27 +172,6 @@ __global__ __launch_bounds__(64) void kas_order_relax_kernel(KasLaunch a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char kas_lds[];
   kas::order_relax<W, DUAL, CTX, VERIFY, C16, IDL, false, M32, QUAD>(a, (int32_t)blockIdx.x, kas_lds);
 }
-// (tiles: 0 = 64 rows a step, 1 = double tiles, 2 = quad tiles)
-static void (*kas_order_relax_m32_pick(int Wc, int tiles))(KasLaunch) {
-  if (Wc != 3) return nullptr;
-  if (tiles >= 2) return kas_order_relax_kernel<3, true, false, false, false, true, true, true>;
-  return tiles ? kas_order_relax_kernel<3, true, false, false, false, true, true> : kas_order_relax_kernel<3, false, false, false, false, true, true>;
-}
-template <bool VERIFY, bool C16 = false, bool IDL = false>
-static void (*kas_order_relax_pick(int Wc, int dual, int ctx))(KasLaunch) {
-  if (Wc <= 2) return ctx ? kas_order_relax_kernel<2, false, true, VERIFY, C16, IDL> : kas_order_relax_kernel<2, false, false, VERIFY, C16, IDL>;   // (double tiles are rows of three holders)
-  if (Wc == 3) {
-    if (ctx) return dual ? kas_order_relax_kernel<3, true, true, VERIFY, C16, IDL> : kas_order_relax_kernel<3, false, true, VERIFY, C16, IDL>;
-    return dual ? kas_order_relax_kernel<3, true, false, VERIFY, C16, IDL> : kas_order_relax_kernel<3, false, false, VERIFY, C16, IDL>;
-  }
-  return nullptr;
-}
-// the instance for (verify, 16-bit cells, ids in the LDS)
-static void (*kas_order_relax_any(int Wc, int dual, int ctx, int verify, int c16, int idl))(KasLaunch) {
-  if (c16) return verify ? kas_order_relax_pick<true, true>(Wc, dual, ctx) : kas_order_relax_pick<false, true>(Wc, dual, ctx);
-  if (idl) return verify ? kas_order_relax_pick<true, false, true>(Wc, dual, ctx) : kas_order_relax_pick<false, false, true>(Wc, dual, ctx);
-  return verify ? nullptr : kas_order_relax_pick<false>(Wc, dual, ctx);
-}
 
 // first fit (P4) and the relaxation form of P5 in one workgroup of two wavefronts (kas_order_relax.h, p4_order_scenario): the order
 // wavefront follows first fit's progress instead of waiting behind a kernel boundary — for launches whose latency is a scenario's
@@ -206,20 +179,6 @@ template <int W, bool DUAL, bool C16, bool IDL, bool M32 = false, bool QUAD = fa
 __global__ __launch_bounds__(128) void kas_p4_order_kernel(KasLaunch a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char kas_lds[];
   kas::p4_order_scenario<W, DUAL, C16, IDL, M32, QUAD>(a, (int32_t)blockIdx.x, kas_lds);
-}
-static void (*kas_p4_order_m32_pick(int Wc, int tiles))(KasLaunch) {
-  if (Wc != 3) return nullptr;
-  if (tiles >= 2) return kas_p4_order_kernel<3, true, false, true, true, true>;
-  return tiles ? kas_p4_order_kernel<3, true, false, true, true> : kas_p4_order_kernel<3, false, false, true, true>;
-}
-// (int32 cells with the broker ids in the LDS, or 16-bit cells: the instances that wait for no gather)
-static void (*kas_p4_order_pick(int Wc, int dual, int c16))(KasLaunch) {
-  if (Wc <= 2) return c16 ? kas_p4_order_kernel<2, false, true, false> : kas_p4_order_kernel<2, false, false, true>;
-  if (Wc == 3) {
-    if (c16) return dual ? kas_p4_order_kernel<3, true, true, false> : kas_p4_order_kernel<3, false, true, false>;
-    return dual ? kas_p4_order_kernel<3, true, false, true> : kas_p4_order_kernel<3, false, false, true>;
-  }
-  return nullptr;
 }
 
 // lists 4 and 5 wide, relaxation form: one wavefront (= one workgroup) per scenario (kas_order_relax_wide.h)
@@ -257,126 +216,139 @@ __global__ __launch_bounds__(64 * KAS_SPREAD_P4_WAVES) void kas_spread_p4_kernel
   extern __shared__ __attribute__((aligned(16))) unsigned char kas_lds[];
   kas::spread_p4<W, KAS_SPREAD_P4_WAVES>(a, (int32_t)blockIdx.x, kas_lds);
 }
-struct KasSpreadKernels { void (*a)(KasLaunch); void (*q)(KasLaunch); void (*b)(KasLaunch); void (*p4)(KasLaunch); };
-template <int W>
-static KasSpreadKernels kas_spread_kernels_w() {
-  return KasSpreadKernels{kas_spread_a_kernel<W>, kas_spread_q_kernel<W>, kas_spread_b_kernel<W>, kas_spread_p4_kernel<W>};
+
+typedef void (*kas_kernel_fn)(KasLaunch);
+// Which instances this build holds.  A full build: every one.  The tuning builds (scripts/build_variant.sh, seconds to compile)
+// refuse other shapes in kas_plan_create: KAS_MINIMAL_INSTANCES=5 holds what BASELINE.json configs[4] launches (lists 5 wide,
+// 4 fill waves), any other value what configs[2] launches (lists 3 wide, 4 fill waves, 1 or 2 scenarios per solver wavefront; the
+// relaxation form's instances also 2 wide).  The instances for dword mid rows (M32: lists 3 wide) are in every build.
+#if defined(KAS_MINIMAL_INSTANCES) && KAS_MINIMAL_INSTANCES == 5
+#define KAS_ONLY_WIDTH 5
+#elif defined(KAS_MINIMAL_INSTANCES) && KAS_MINIMAL_INSTANCES != 0
+#define KAS_ONLY_WIDTH 3
+#else
+#define KAS_ONLY_WIDTH 0
+#endif
+static constexpr bool kas_built(int family, int W, int NW = 4, int G = 2) {
+  if (KAS_ONLY_WIDTH == 0) return true;
+  if (family == KAS_K_ORDER_RELAX || family == KAS_K_P4_ORDER) return KAS_ONLY_WIDTH == 3 && W <= 3;
+  if (W != KAS_ONLY_WIDTH || NW != 4) return false;
+  if (KAS_ONLY_WIDTH == 5)
+    return family != KAS_K_FILL_SLIM && family != KAS_K_ORDER_TICKET;
+  return G <= 2 && (family == KAS_K_FILL || family == KAS_K_FILL_SLIM || family == KAS_K_P4 || family == KAS_K_ORDER_TICKET ||
+                    family == KAS_K_ORDER_ROUND);
+}
+static bool kas_minimal_ok(int Wc, int NW, int G) { return kas_built(KAS_K_FILL, Wc, NW, G); }
+
+// relaxation form: the instance for (tiles, Context); double tiles are rows of three holders
+template <int W, bool VERIFY, bool C16, bool IDL>
+static kas_kernel_fn kas_relax_instance(const KasKernelId& k) {
+  if constexpr (W == 3)
+    if (k.tiles == 1) return k.ctx ? kas_order_relax_kernel<3, true, true, VERIFY, C16, IDL> : kas_order_relax_kernel<3, true, false, VERIFY, C16, IDL>;
+  if (k.tiles != 0) return nullptr;
+  return k.ctx ? kas_order_relax_kernel<W, false, true, VERIFY, C16, IDL> : kas_order_relax_kernel<W, false, false, VERIFY, C16, IDL>;
+}
+// first fit beside it: int32 cells with the broker ids in the LDS, or 16-bit cells — the instances that wait for no gather
+template <int W, bool C16>
+static kas_kernel_fn kas_p4_order_instance(const KasKernelId& k) {
+  if constexpr (W == 3)
+    if (k.tiles == 1) return kas_p4_order_kernel<3, true, C16, !C16>;
+  return k.tiles == 0 ? kas_p4_order_kernel<W, false, C16, !C16> : nullptr;
 }
 
-// tuning builds only: extra dynamic LDS per workgroup, to measure how much residency is worth
-#ifndef KAS_TUNE_ORDER_LDS_PAD
-#define KAS_TUNE_ORDER_LDS_PAD 0
-#endif
-#ifndef KAS_TUNE_FILL_LDS_PAD
-#define KAS_TUNE_FILL_LDS_PAD 0
-#endif
-typedef void (*kas_kernel_fn)(KasLaunch);
-#if defined(KAS_MINIMAL_INSTANCES) && KAS_MINIMAL_INSTANCES == 5
-// tuning build for BASELINE.json configs[4] (lists 5 wide, 4 fill waves): seconds to compile
-static bool kas_minimal_ok(int Wc, int NW, int) { return Wc == 5 && NW == 4; }
-static kas_kernel_fn kas_fill_for(int, int) { return kas_fill_kernel<5, 4>; }
-static kas_kernel_fn kas_fill_slim_for(int) { return nullptr; }
-static kas_kernel_fn kas_p4_for(int) { return kas_p4_kernel<5>; }
-static kas_kernel_fn kas_order_ticket_for(int, int, int) { return nullptr; }
-static kas_kernel_fn kas_order_round_for(int) { return kas_order_round_kernel<5>; }
-static kas_kernel_fn kas_order_wide_for(int) { return kas_order_wide_kernel<5>; }
-static kas_kernel_fn kas_order_relaxw_for(int) { return kas_order_relax_wide_kernel<5>; }
-static kas_kernel_fn kas_p4_order_for(int, int, int) { return nullptr; }
-static kas_kernel_fn kas_order_relax_for(int, int, int, int = 0, int = 0, int = 0) { return nullptr; }
-static KasSpreadKernels kas_spread_for(int Wc) { return Wc == 5 ? kas_spread_kernels_w<5>() : KasSpreadKernels{nullptr, nullptr, nullptr, nullptr}; }
-#elif defined(KAS_MINIMAL_INSTANCES) && KAS_MINIMAL_INSTANCES != 0
-// tuning builds (scripts/build_variant.sh): only the kernels BASELINE.json configs[2] launches —
-// lists 3 wide, 4 fill waves, 2 scenarios per solver wavefront — so that a variant compiles in
-// seconds.  Other shapes are refused by kas_plan_create in such a build.
-static bool kas_minimal_ok(int Wc, int NW, int G) { return Wc == 3 && NW == 4 && (G == 2 || G == 1); }
-static kas_kernel_fn kas_fill_for(int, int) { return kas_fill_kernel<3, 4>; }
-static kas_kernel_fn kas_fill_slim_for(int) { return kas_fill_slim_kernel<3>; }
-static kas_kernel_fn kas_p4_for(int) { return kas_p4_kernel<3>; }
-static kas_kernel_fn kas_order_ticket_for(int, int G, int packed) {
-  if (G == 1) return packed ? kas_order_ticket_kernel<3, 1, true> : kas_order_ticket_kernel<3, 1, false>;
-  return packed ? kas_order_ticket_kernel<3, 2, true> : kas_order_ticket_kernel<3, 2, false>;
-}
-static kas_kernel_fn kas_order_round_for(int) { return kas_order_round_kernel<3>; }
-static kas_kernel_fn kas_order_wide_for(int) { return nullptr; }
-static kas_kernel_fn kas_order_relaxw_for(int) { return nullptr; }
-static kas_kernel_fn kas_p4_order_for(int, int dual, int c16) { return kas_p4_order_pick(3, dual, c16); }
-static kas_kernel_fn kas_order_relax_for(int, int dual, int ctx, int verify = 0, int c16 = 0, int idl = 0) {
-  return kas_order_relax_any(3, dual, ctx, verify, c16, idl);
-}
-static KasSpreadKernels kas_spread_for(int) { return KasSpreadKernels{nullptr, nullptr, nullptr, nullptr}; }
-#else
-static bool kas_minimal_ok(int, int, int) { return true; }
-template <int NW>
-static kas_kernel_fn kas_fill_for_w(int Wc) {
-  switch (Wc) {
-    case 2: return kas_fill_kernel<2, NW>;
-    case 3: return kas_fill_kernel<3, NW>;
-    case 4: return kas_fill_kernel<4, NW>;
-    case 5: return kas_fill_kernel<5, NW>;
-    default: return kas_fill_kernel<8, NW>;
+// THE mapping kernel identity -> kernel; nullptr: no such instance (in this build)
+template <int W>
+static kas_kernel_fn kas_kernel_w(const KasKernelId& k) {
+  switch (k.family) {
+    case KAS_K_FILL:   // (8 wavefronts per scenario: only on the CPU emulator — a minute of build time a width, and never the faster choice on the GPU)
+      if constexpr (kas_built(KAS_K_FILL, W, 4)) if (k.NW == 4) return kas_fill_kernel<W, 4>;
+      if constexpr (kas_built(KAS_K_FILL, W, 2)) if (k.NW == 2) return kas_fill_kernel<W, 2>;
+      if constexpr (kas_built(KAS_K_FILL, W, 1)) if (k.NW == 1) return kas_fill_kernel<W, 1>;
+      return nullptr;
+    case KAS_K_FILL_SLIM:
+      if constexpr (W == 3) if (k.m32) return kas_fill_slim_kernel<3, true>;
+      if constexpr (W <= 3 && kas_built(KAS_K_FILL_SLIM, W)) if (!k.m32) return kas_fill_slim_kernel<W>;
+      return nullptr;
+    case KAS_K_P4:
+      if constexpr (W == 3) if (k.m32) return kas_p4_kernel<3, true>;
+      if constexpr (kas_built(KAS_K_P4, W)) if (!k.m32) return kas_p4_kernel<W>;
+      return nullptr;
+    case KAS_K_ORDER_RELAX:
+      if constexpr (W == 3)
+        if (k.m32) {
+          if (!k.idl || k.ctx || k.verify || k.c16) return nullptr;
+          return k.tiles == 2 ? kas_order_relax_kernel<3, true, false, false, false, true, true, true>
+                 : k.tiles == 1 ? kas_order_relax_kernel<3, true, false, false, false, true, true>
+                                : kas_order_relax_kernel<3, false, false, false, false, true, true>;
+        }
+      if constexpr (W <= 3 && kas_built(KAS_K_ORDER_RELAX, W)) {
+        if (k.m32 || (k.c16 && k.idl)) return nullptr;
+        if (k.c16) return k.verify ? kas_relax_instance<W, true, true, false>(k) : kas_relax_instance<W, false, true, false>(k);
+        if (k.idl) return k.verify ? kas_relax_instance<W, true, false, true>(k) : kas_relax_instance<W, false, false, true>(k);
+        return k.verify ? nullptr : kas_relax_instance<W, false, false, false>(k);   // (the gather instances: without the sampled verification only)
+      }
+      return nullptr;
+    case KAS_K_P4_ORDER:
+      if constexpr (W == 3)
+        if (k.m32) {
+          if (!k.idl || k.c16) return nullptr;
+          return k.tiles == 2 ? kas_p4_order_kernel<3, true, false, true, true, true>
+                 : k.tiles == 1 ? kas_p4_order_kernel<3, true, false, true, true> : kas_p4_order_kernel<3, false, false, true, true>;
+        }
+      if constexpr (W <= 3 && kas_built(KAS_K_P4_ORDER, W)) {
+        if (k.m32 || (k.c16 != 0) == (k.idl != 0)) return nullptr;
+        return k.c16 ? kas_p4_order_instance<W, true>(k) : kas_p4_order_instance<W, false>(k);
+      }
+      return nullptr;
+    case KAS_K_ORDER_RELAX_WIDE:
+      if constexpr ((W == 4 || W == 5) && kas_built(KAS_K_ORDER_RELAX_WIDE, W)) return kas_order_relax_wide_kernel<W>;
+      return nullptr;
+    case KAS_K_ORDER_TICKET:
+      if constexpr (W <= 3 && kas_built(KAS_K_ORDER_TICKET, W, 4, 2)) {
+        if (k.G == 1) return k.packed ? kas_order_ticket_kernel<W, 1, true> : kas_order_ticket_kernel<W, 1, false>;
+        if (k.G == 2) return k.packed ? kas_order_ticket_kernel<W, 2, true> : kas_order_ticket_kernel<W, 2, false>;
+      }
+      if constexpr (W <= 3 && kas_built(KAS_K_ORDER_TICKET, W, 4, 4))
+        if (k.G == 4) return k.packed ? kas_order_ticket_kernel<W, 4, true> : kas_order_ticket_kernel<W, 4, false>;
+      return nullptr;
+    case KAS_K_ORDER_WIDE:
+      if constexpr ((W == 4 || W == 5) && kas_built(KAS_K_ORDER_WIDE, W)) return kas_order_wide_kernel<W>;
+      return nullptr;
+    case KAS_K_ORDER_ROUND:
+      if constexpr (kas_built(KAS_K_ORDER_ROUND, W)) return kas_order_round_kernel<W>;
+      return nullptr;
+    default:
+      if constexpr (W >= 3 && W <= 5 && kas_built(KAS_K_SPREAD_A, W)) {
+        if (k.family == KAS_K_SPREAD_A) return kas_spread_a_kernel<W>;
+        if (k.family == KAS_K_SPREAD_Q) return kas_spread_q_kernel<W>;
+        if (k.family == KAS_K_SPREAD_B) return kas_spread_b_kernel<W>;
+        if (k.family == KAS_K_SPREAD_P4) return kas_spread_p4_kernel<W>;
+      }
+      return nullptr;
   }
 }
-static kas_kernel_fn kas_fill_for(int Wc, int NW) {
-  switch (NW) {                            // (8 wavefronts per scenario: only on the CPU emulator — each
-    case 1: return kas_fill_for_w<1>(Wc);   // instantiated width costs a minute of build time and 8 was
-    case 2: return kas_fill_for_w<2>(Wc);   // never the faster choice on the GPU)
-    default: return kas_fill_for_w<4>(Wc);
+static kas_kernel_fn kas_kernel_for(const KasKernelId& k) {
+  if (k.family == KAS_K_PERMUTATION) return kas_order_permutation_kernel;
+  switch (k.W) {
+    case 2: return kas_kernel_w<2>(k);
+    case 3: return kas_kernel_w<3>(k);
+    case 4: return kas_kernel_w<4>(k);
+    case 5: return kas_kernel_w<5>(k);
+    case 8: return kas_kernel_w<8>(k);
+    default: return nullptr;
   }
 }
-static kas_kernel_fn kas_fill_slim_for(int Wc) {
-  return Wc == 2 ? kas_fill_slim_kernel<2> : (Wc == 3 ? kas_fill_slim_kernel<3> : nullptr);
+// the families this build holds at a width class (KasLaunchIn::built)
+static uint32_t kas_built_mask(int Wc, int cells16) {
+  auto have = [&](int family, int c16, int idl) {
+    KasKernelId k;
+    k.family = family; k.W = Wc; k.c16 = c16; k.idl = idl;
+    return kas_kernel_for(k) != nullptr;
+  };
+  return (have(KAS_K_ORDER_RELAX, 0, 0) ? KAS_BUILT_RELAX : 0u) | (have(KAS_K_ORDER_RELAX_WIDE, 0, 0) ? KAS_BUILT_RELAXW : 0u) |
+         (have(KAS_K_ORDER_WIDE, 0, 0) ? KAS_BUILT_WIDE : 0u) | (have(KAS_K_FILL_SLIM, 0, 0) ? KAS_BUILT_SLIM : 0u) |
+         (have(KAS_K_P4_ORDER, cells16, !cells16) ? KAS_BUILT_P4_ORDER : 0u) | (have(KAS_K_SPREAD_A, 0, 0) ? KAS_BUILT_SPREAD : 0u);
 }
-static kas_kernel_fn kas_p4_for(int Wc) {
-  switch (Wc) {
-    case 2: return kas_p4_kernel<2>;
-    case 3: return kas_p4_kernel<3>;
-    case 4: return kas_p4_kernel<4>;
-    case 5: return kas_p4_kernel<5>;
-    default: return kas_p4_kernel<8>;
-  }
-}
-template <int G, bool PK>
-static kas_kernel_fn kas_order_ticket_for_g(int Wc) {
-  switch (Wc) {
-    case 2: return kas_order_ticket_kernel<2, G, PK>;
-    default: return kas_order_ticket_kernel<3, G, PK>;
-  }
-}
-static kas_kernel_fn kas_order_ticket_for(int Wc, int G, int packed) {
-  switch (G) {
-    case 1: return packed ? kas_order_ticket_for_g<1, true>(Wc) : kas_order_ticket_for_g<1, false>(Wc);
-    case 2: return packed ? kas_order_ticket_for_g<2, true>(Wc) : kas_order_ticket_for_g<2, false>(Wc);
-    default: return packed ? kas_order_ticket_for_g<4, true>(Wc) : kas_order_ticket_for_g<4, false>(Wc);
-  }
-}
-static kas_kernel_fn kas_order_round_for(int Wc) {
-  switch (Wc) {
-    case 2: return kas_order_round_kernel<2>;
-    case 3: return kas_order_round_kernel<3>;
-    case 4: return kas_order_round_kernel<4>;
-    case 5: return kas_order_round_kernel<5>;
-    default: return kas_order_round_kernel<8>;
-  }
-}
-static kas_kernel_fn kas_order_wide_for(int Wc) {
-  return Wc == 4 ? kas_order_wide_kernel<4> : kas_order_wide_kernel<5>;
-}
-static kas_kernel_fn kas_order_relaxw_for(int Wc) {
-  return Wc == 4 ? kas_order_relax_wide_kernel<4> : (Wc == 5 ? kas_order_relax_wide_kernel<5> : nullptr);
-}
-static kas_kernel_fn kas_p4_order_for(int Wc, int dual, int c16) { return kas_p4_order_pick(Wc, dual, c16); }
-static kas_kernel_fn kas_order_relax_for(int Wc, int dual, int ctx, int verify = 0, int c16 = 0, int idl = 0) {
-  return kas_order_relax_any(Wc, dual, ctx, verify, c16, idl);
-}
-static KasSpreadKernels kas_spread_for(int Wc) {
-  switch (Wc) {
-    case 3: return kas_spread_kernels_w<3>();
-    case 4: return kas_spread_kernels_w<4>();
-    case 5: return kas_spread_kernels_w<5>();
-    default: return KasSpreadKernels{nullptr, nullptr, nullptr, nullptr};
-  }
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -453,7 +425,7 @@ struct kas_plan {
   int NW;                       // wavefronts per scenario workgroup of the fill kernel
   int G;                        // scenarios per wavefront of the ticket-form order kernel
   int tickets;                  // 1: ticket form of P5, 0: round form
-  int fused;                    // 1: per-chunk histograms in the fill (KasShape::fused_ok), see kas_plan_fused()
+  int fused;                    // 1: per-chunk histograms in the fill (KasShape::fused_ok), see kas_resolve_launch
   uint32_t flags;               // KAS_FLAG_*
   KasLds lds, lds_fused;
   int32_t n_scenarios, n_topics;
@@ -692,125 +664,38 @@ void kas_plan_destroy(kas_plan* p) {
   delete p;
 }
 
-// the relaxation form's instances for this plan keep the broker ids in the LDS (int32 cells; kas_relax_lds_ids)
-static int kas_plan_relax_idl(const kas_plan* p) {
-  return !p->cells16 && kas_relax_lds_ids(p->shape.n_max, p->shape.any_ctx) ? 1 : 0;
+// everything the launch decisions read (kas_launch_plan.h), from the plan as it stands
+static KasLaunchIn kas_plan_launch_in(const kas_plan* p) {
+  KasLaunchIn in;
+  in.shape = &p->shape;
+  in.n_scenarios = p->n_scenarios; in.single_topic = p->single_topic; in.cells16 = p->cells16;
+  in.flags = p->flags; in.index_rows_bits = p->index_rows_bits; in.mid32_bits = p->mid32_bits; in.full_fill = p->full_fill;
+  in.NW = p->NW; in.G = p->G; in.fused = p->fused;
+  in.lds_total = p->lds.total; in.lds_fused_total = p->lds_fused.total;
+  in.lane_order_ok = p->ctx->lds_lane_order_ok; in.lane_order_state = p->ctx->lds_lane_order_state;
+  in.have_p4s = p->b_p4s.p != nullptr; in.have_back_flags = p->b_sp_flag.p != nullptr;
+  in.last_handback = p->h_handback ? *(volatile int32_t*)p->h_handback : 0;
+  in.built = kas_built_mask(p->Wc, p->cells16);
+  return in;
 }
 
-// opt every kernel this plan may launch into its dynamic LDS size
+// opt every kernel this plan may launch into its dynamic LDS size: the stages the resolver can return for it (never on the launch path)
 static int kas_plan_set_kernels(kas_plan* p) {
-  KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_fill_for(p->Wc, p->NW), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (p->fused && p->lds_fused.total > p->lds.total ? p->lds_fused.total : p->lds.total) + KAS_TUNE_FILL_LDS_PAD));
-  if (p->NW == 4 && p->fused && kas_fill_slim_for(p->Wc) != nullptr)
-    KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_fill_slim_for(p->Wc), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kas_fill_slim_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries).total + KAS_TUNE_SLIM_LDS_PAD));
-  if (p->NW == 4 && p->fused && p->Wc == 3 && kas_fill_slim_for(p->Wc) != nullptr)     // (its instance for dword mid rows)
-    KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_fill_slim_m32(), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kas_fill_slim_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries).total + KAS_TUNE_SLIM_LDS_PAD));
-  if (p->Wc <= 3 && p->tickets && kas_order_ticket_for(p->Wc, p->G, 0))   // (beyond 8,191 brokers only the relaxation form applies)
-    for (int pk = 0; pk < 2; ++pk)
-      KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_order_ticket_for(p->Wc, p->G, pk),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kas_order_ticket_lds(p->shape.n_max, p->G, pk) + KAS_TUNE_ORDER_LDS_PAD));
-  for (int dual = 0; dual < 2; ++dual)
-    for (int verify = 0; verify < 2; ++verify)
-      if (p->shape.relax_ok && kas_order_relax_for(p->Wc, dual, p->shape.any_ctx, verify, p->cells16, kas_plan_relax_idl(p)))
-        KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_order_relax_for(p->Wc, dual, p->shape.any_ctx, verify, p->cells16, kas_plan_relax_idl(p)),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kas_order_relax_lds(p->shape.n_max, dual, p->shape.any_ctx, kas_plan_relax_idl(p))));
-  if (p->shape.with_x && kas_p4_lds_layout(p->shape.n_max).total <= KAS_LDS_LIMIT)
-  {
-    KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_p4_for(p->Wc), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kas_p4_lds_layout(p->shape.n_max).total));
-    if (p->Wc == 3)
-      KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_p4_m32(), hipFuncAttributeMaxDynamicSharedMemorySize, kas_p4_lds_layout(p->shape.n_max).total));
-  }
-  if (p->shape.round_fits)
-    KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_order_round_for(p->Wc),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kas_order_round_lds(p->shape.n_max, p->Wc)));
-  for (int dual = 0; dual < 2; ++dual)
-    if (p->shape.relax_ok && !p->shape.any_ctx && (p->cells16 || kas_plan_relax_idl(p)) && kas_p4_order_for(p->Wc, dual, p->cells16) &&
-        kas_p4_order_lds(p->shape.n_max, dual, kas_plan_relax_idl(p)) <= KAS_LDS_LIMIT)
-      KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_p4_order_for(p->Wc, dual, p->cells16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      kas_p4_order_lds(p->shape.n_max, dual, kas_plan_relax_idl(p))));
-  if (p->shape.relax_ok && !p->shape.any_ctx && kas_plan_relax_idl(p) && p->shape.n_max <= KAS_MID32_N_MAX)   // (the instances for dword mid rows)
-    for (int dual = 0; dual < 3; ++dual) {                     // (tiles of 64 rows, double tiles, quad tiles)
-      if (kas_order_relax_lds(p->shape.n_max, dual, 0, 1) > KAS_LDS_LIMIT) continue;
-      if (kas_order_relax_m32_pick(p->Wc, dual))
-        KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_order_relax_m32_pick(p->Wc, dual), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        kas_order_relax_lds(p->shape.n_max, dual, 0, 1)));
-      if (kas_p4_order_m32_pick(p->Wc, dual) && kas_p4_order_lds(p->shape.n_max, dual, 1) <= KAS_LDS_LIMIT)
-        KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_p4_order_m32_pick(p->Wc, dual), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        kas_p4_order_lds(p->shape.n_max, dual, 1)));
-    }
-  if (p->shape.relaxw_ok && kas_order_relaxw_for(p->Wc))
-    KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_order_relaxw_for(p->Wc), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kas_order_relaxw_lds(p->shape.n_max, p->Wc)));
-  if (p->shape.wide_ok && kas_order_wide_for(p->Wc))
-    KAS_HIP_TRY(hipFuncSetAttribute((const void*)kas_order_wide_for(p->Wc),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kas_order_wide_lds(p->shape.n_max)));
-  const KasSpreadKernels sk = kas_spread_for(p->Wc);
-  if (sk.a && p->shape.with_x) {
-    const int l1 = kas_fill_lds_layout(p->shape.n_max, p->Wc, 1, p->shape.idmap_entries, p->shape.need_bsearch, 1).total;
-    const int l4 = kas_fill_lds_layout(p->shape.n_max, p->Wc, 4, p->shape.idmap_entries, p->shape.need_bsearch, 1).total;
-    if (l1 <= KAS_LDS_LIMIT && l4 <= KAS_LDS_LIMIT) {
-      KAS_HIP_TRY(hipFuncSetAttribute((const void*)sk.a, hipFuncAttributeMaxDynamicSharedMemorySize, l1));
-      KAS_HIP_TRY(hipFuncSetAttribute((const void*)sk.b, hipFuncAttributeMaxDynamicSharedMemorySize, l1));
-      KAS_HIP_TRY(hipFuncSetAttribute((const void*)sk.p4, hipFuncAttributeMaxDynamicSharedMemorySize, l4));
-    }
-  }
+  struct Opt { kas_kernel_fn fn; uint32_t lds; };
+  std::vector<Opt> opts;
+  kas_enumerate_launches(kas_plan_launch_in(p), [&opts](const KasStage& st) {
+    const kas_kernel_fn fn = kas_kernel_for(st.k);
+    if (!fn || st.lds == 0u || st.lds > (uint32_t)KAS_LDS_LIMIT) return;   // (not in this build / nothing to opt into / can never be launched)
+    for (Opt& o : opts)
+      if (o.fn == fn) { if (st.lds > o.lds) o.lds = st.lds; return; }
+    opts.push_back(Opt{fn, st.lds});
+  });
+  for (const Opt& o : opts) KAS_HIP_TRY(hipFuncSetAttribute((const void*)o.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)o.lds));
   return KAS_E_OK;
 }
-
-// per-chunk histograms: what the shape allows unless switched off (or the general fill is forced)
-static bool kas_plan_fused(const kas_plan* p) {
-  return p->fused && !(p->flags & (KAS_FLAG_TWO_PASS_HIST | KAS_FLAG_GENERIC_FILL));
-}
-
-// index rows in this plan's next solve (KAS_FLAG_INDEX_ROWS; the kernel still decides per topic: rows of the batch's width, a
-// direct id table): int32 cells, lists up to 3 wide, per-chunk histograms, the quota drawn with the atomic-with-return
-static bool kas_plan_index_rows(const kas_plan* p) {
-  return !p->cells16 && kas_index_rows_wanted(p->index_rows_bits) && p->Wc <= 3 && kas_plan_fused(p) && p->ctx->lds_lane_order_ok &&
-         !(p->flags & KAS_FLAG_NO_RTN_QUOTA) && p->shape.n_max < 0x3fff && p->shape.idmap_entries > 0;
-}
-
-// the slim fill kernel in this plan's next solve (with kas_fill_kernel behind it for the scenarios it hands back): int32 cells,
-// lists up to 3 wide, per-chunk histograms on 4 wavefronts, the quota drawn with the atomic-with-return, a direct id table for
-// every scenario, no index rows, first fit handed over (split_p4: to kas_p4_kernel or to kas_p4_order_kernel), no spread fill
-static bool kas_plan_slim_fill(const kas_plan* p, bool split_p4, int32_t chunks) {
-  return KAS_SLIM_FILL_DEFAULT && !p->full_fill && !p->cells16 && p->Wc <= 3 && p->NW == 4 && kas_fill_slim_for(p->Wc) != nullptr &&
-         kas_plan_fused(p) && p->shape.with_x && p->ctx->lds_lane_order_ok && !(p->flags & KAS_FLAG_NO_RTN_QUOTA) &&
-         !kas_plan_index_rows(p) && split_p4 && chunks == 0 && p->shape.idmap_entries > 0 && !p->shape.need_bsearch &&
-         p->b_sp_flag.p != nullptr;
-}
-
-// workgroups of the kas_fill_kernel launch behind the slim kernel: KAS_FILL_BACK_GRID — each needs a 35 KB / 4 x 128-VGPR slot before it
-// can see that there is nothing to do — unless the plan's last solve handed more scenarios back than that: then one workgroup per
-// such scenario and a quarter more (a batch whose rows are not rack-diverse hands EVERY scenario back, and the general fill of a
-// scenario is one long chain: 1000 of them on 256 workgroups took 53 ms, on 1000 they take 20).  A rebuilt plan starts small again.
-static unsigned kas_plan_back_grid(const kas_plan* p, unsigned fill_grid) {
-  unsigned g = KAS_FILL_BACK_GRID;
-  const int32_t last = p->h_handback ? *(volatile int32_t*)p->h_handback : 0;
-  if (last > 0 && (unsigned)last + (unsigned)last / 4u > g)
-    g = (((unsigned)last + (unsigned)last / 4u + KAS_FILL_BACK_GRID_STEP - 1u) / KAS_FILL_BACK_GRID_STEP) * KAS_FILL_BACK_GRID_STEP;
-  return g < fill_grid ? g : fill_grid;
-}
-
-// chunks per scenario of the spread fill for this plan's next solve, or 0 (one-workgroup fill kernel)
-static int32_t kas_plan_spread_chunks(const kas_plan* p) {
-  if (p->cells16) return 0;                                  // (the spread fill's kernels read int32 cells)
-  if (p->NW != 4 || !kas_spread_for(p->Wc).a || (p->flags & KAS_FLAG_GENERIC_FILL)) return 0;
-  // (the quota kernel puts scenarios on grid.y and nodes on grid.x)
-  if (p->shape.n_max <= 0 || p->n_scenarios > 65535) return 0;
-  if (kas_fill_lds_layout(p->shape.n_max, p->Wc, 4, p->shape.idmap_entries, p->shape.need_bsearch, 1).total > KAS_LDS_LIMIT) return 0;
-  return kas_spread_chunks(p->shape, p->n_scenarios, p->single_topic != 0, (p->flags & KAS_FLAG_SPREAD_FILL) != 0);
-}
-
 // scratch of the spread fill for the plan's current flags (kas_plan_create / kas_plan_set_flags, never a solve)
 static int kas_plan_spread_scratch(kas_plan* p) {
-  const int32_t chunks = kas_plan_spread_chunks(p);
+  const int32_t chunks = kas_resolve_launch(kas_plan_launch_in(p)).spread_chunks;
   if (chunks > 0) {
     const size_t S = (size_t)p->n_scenarios, NM = (size_t)(p->shape.n_max > 0 ? p->shape.n_max : 1), C = (size_t)chunks;
     int rc;
@@ -862,15 +747,11 @@ static int kas_plan_build(kas_plan* p, const kas_batch_desc* batch) {
   // some order kernel must be able to take the batch HERE: beyond 8,191 brokers at lists <= 3 wide that is the relaxation
   // form alone, which needs the LDS lane order the context's self-test looks for (such a plan used to fail at its
   // first solve with a launch error)
-  if (p->cells16) {
-    // 16-bit cells (kas_plan_create16): the kernels with that I/O are the fill kernel (+ kas_p4_kernel), the relaxation form
-    // and the round form — lists up to 3 wide; anything else is the caller's to widen (kas_solve_host16 does)
-    const bool relax16 = sh.relax_ok && ctx->lds_lane_order_ok && kas_order_relax_for(sh.Wc, 0, 0, 0, 1) != nullptr;
-    if (sh.Wc > 3 || !(relax16 || sh.round_fits))
-      return set_error(KAS_E_UNSUPPORTED, "16-bit cells: lists up to 3 wide, and a batch the relaxation form (LDS lane-order self-test passed) or the round form of the order kernel takes");
-  }
+  const uint32_t built = kas_built_mask(sh.Wc, p->cells16);
+  if (p->cells16 && !kas_cells16_ok(sh, ctx->lds_lane_order_ok, built))   // (anything else is the caller's to widen: kas_solve_host16 does)
+    return set_error(KAS_E_UNSUPPORTED, "16-bit cells: lists up to 3 wide, and a batch the relaxation form (LDS lane-order self-test passed) or the round form of the order kernel takes");
   {
-    const bool relax_here = sh.relax_ok && ctx->lds_lane_order_ok && kas_order_relax_for(sh.Wc, 0, 0) != nullptr;
+    const bool relax_here = sh.relax_ok && ctx->lds_lane_order_ok && (built & KAS_BUILT_RELAX);
     if (!sh.round_fits && !sh.tickets_ok && !sh.wide_ok && !relax_here)
       return set_error(KAS_E_UNSUPPORTED,
                        sh.relax_ok ? (ctx->lds_lane_order_state == -1
@@ -995,140 +876,32 @@ int kas_plan_create16(kas_ctx* ctx, const kas_batch_desc* batch, kas_plan** out_
   return kas_plan_new(ctx, &ib, nullptr, out_plan, 1);
 }
 
-// the launch decisions of kas_solve_device, in one place
-struct KasLaunchPlan {
-  bool p4_order;                // first fit inside the order kernel's workgroup (kas_p4_order_kernel; then `relax`, and no kas_p4_kernel)
-  bool relaxw;                  // relaxation form of P5 for lists 4 and 5 wide (then neither tickets nor wide)
-  bool relax;                   // relaxation form of P5 (then neither tickets nor wide)
-  bool tickets, pairing, wide;
-  bool m32;                     // dword mid rows in this solve (KAS_FLAG_MID32)
-  int tiles;                    // relaxation form: 0 = tiles of 64 rows, 1 = double tiles, 2 = quad tiles (dword mid rows only)
-  int packed;
-  unsigned fill_grid, fill_block, order_grid, order_block;
-  size_t fill_lds, order_lds;
-};
-static KasLaunchPlan kas_launch_plan(const kas_plan* p) {
-  KasLaunchPlan lp;
-  lp.relax = p->shape.relax_ok && p->ctx->lds_lane_order_ok && kas_order_relax_for(p->Wc, 0, 0) != nullptr &&
-             !(p->flags & KAS_FLAG_ROUND_ORDER) && !(kas_flags_want_tickets(p->flags) && p->tickets);
-  lp.tickets = !lp.relax && p->tickets && !(p->flags & KAS_FLAG_ROUND_ORDER) && !p->cells16;   // (no ticket form with 16-bit cells: the round form)
-  lp.packed = p->shape.packed_ok && !(p->flags & KAS_FLAG_WIDE_COUNTERS);
-  lp.pairing = lp.tickets && p->G > 1 && p->n_scenarios > p->G;
-  lp.relaxw = !lp.relax && !p->cells16 && p->shape.relaxw_ok && p->ctx->lds_lane_order_ok && kas_order_relaxw_for(p->Wc) != nullptr &&
-              kas_relaxw_wanted(p->flags);
-  lp.wide = !lp.tickets && !lp.relaxw && !p->cells16 && p->shape.wide_ok && !(p->flags & KAS_FLAG_ROUND_ORDER) && kas_order_wide_for(p->Wc) != nullptr;
-  lp.p4_order = false;
-  lp.m32 = kas_mid32_launch(p->shape, p->cells16 != 0, p->mid32_bits, lp.relax, p->flags, kas_plan_relax_idl(p), kas_plan_index_rows(p),
-                            kas_plan_spread_chunks(p)) && kas_order_relax_m32_pick(p->Wc, 0) != nullptr;
-  lp.tiles = 0;
-  lp.fill_grid = (unsigned)p->n_scenarios; lp.fill_block = 64u * (unsigned)p->NW;
-  lp.fill_lds = (size_t)(kas_plan_fused(p) ? p->lds_fused.total : p->lds.total) + KAS_TUNE_FILL_LDS_PAD;
-  if (lp.relax) {
-    int dual = p->Wc == 3 && kas_relax_double_tiles(p->flags, p->n_scenarios);
-    if (dual && lp.m32 && kas_relax_quad_tiles(p->flags, p->n_scenarios) && kas_order_relax_lds(p->shape.n_max, 2, 0, 1) <= KAS_LDS_LIMIT)
-      dual = 2;                                                 // (quad tiles: the instances on dword mid rows)
-    lp.tiles = dual;
-    lp.order_grid = (unsigned)p->n_scenarios; lp.order_block = 64u;
-    lp.order_lds = (size_t)kas_order_relax_lds(p->shape.n_max, dual, p->shape.any_ctx, kas_plan_relax_idl(p));
-    // first fit as a second wavefront of the order kernel's workgroup?
-    const bool relax_plain = !p->shape.any_ctx && (p->flags >> 24) == 0u && (p->cells16 || kas_plan_relax_idl(p)) &&
-                             kas_p4_order_for(p->Wc, dual != 0, p->cells16) != nullptr && p->b_p4s.p != nullptr;
-    if (kas_p4_with_order(p->shape, p->NW, p->flags | (p->shape.with_x ? 0u : KAS_FLAG_GENERIC_FILL), kas_plan_spread_chunks(p), p->n_scenarios,
-                          relax_plain, dual, kas_plan_relax_idl(p))) {
-      lp.p4_order = true;
-      lp.order_block = 128u;
-      lp.order_lds = (size_t)kas_p4_order_lds(p->shape.n_max, dual, kas_plan_relax_idl(p));
-    }
-  } else if (lp.relaxw) {
-    lp.order_grid = (unsigned)p->n_scenarios; lp.order_block = 64u;
-    lp.order_lds = (size_t)kas_order_relaxw_lds(p->shape.n_max, p->Wc);
-  } else if (lp.tickets) {
-    lp.order_grid = (unsigned)((p->n_scenarios + p->G - 1) / p->G); lp.order_block = 192u;
-    lp.order_lds = (size_t)kas_order_ticket_lds(p->shape.n_max, p->G, lp.packed) + KAS_TUNE_ORDER_LDS_PAD;
-  } else if (lp.wide) {
-    lp.order_grid = (unsigned)p->n_scenarios; lp.order_block = (unsigned)KAS_ORDER_WIDE_BLOCK;
-    lp.order_lds = (size_t)kas_order_wide_lds(p->shape.n_max);
-  } else {
-    lp.order_grid = (unsigned)p->n_scenarios; lp.order_block = 64u;
-    lp.order_lds = (size_t)kas_order_round_lds(p->shape.n_max, p->Wc);
-  }
-  return lp;
-}
-
-// first fit in kas_p4_kernel in this plan's next solve (kas_split_p4)
-static bool kas_plan_split_p4(const kas_plan* p) {
-  return p->b_p4s.p != nullptr &&
-         kas_split_p4(p->shape, p->NW, p->flags | (p->shape.with_x ? 0u : KAS_FLAG_GENERIC_FILL), kas_plan_spread_chunks(p), p->n_scenarios);
-}
-
-// dword mid rows in this plan's next solve (KAS_FLAG_MID32, kas_mid32_launch)
-static bool kas_plan_mid32(const kas_plan*, const KasLaunchPlan& lp) { return lp.m32; }
-
 int kas_plan_describe(const kas_plan* p, char* buf, int n) {
   if (!p || !buf || n <= 0) return set_error(KAS_E_INVALID_ARG, "NULL argument");
-  const KasLaunchPlan lp = kas_launch_plan(p);
-  const bool generic = (p->flags & KAS_FLAG_GENERIC_FILL) || !p->shape.with_x;
-  char order[256];
-  const char* ctx_tail = (lp.wide && p->shape.wide_checked)
-                             ? " [count fields checked at the end; kas_fill_kernel + kas_order_round_kernel for scenarios it flags]"
-                             : (p->shape.any_ctx && (lp.tickets || lp.wide || lp.relax)) ? " [Context in/out; kas_order_round_kernel for scenarios it flags]" : "";
-  if (lp.relax && lp.p4_order)
-    snprintf(order, sizeof(order), "kas_p4_order_kernel<%d>[first fit beside kas_order_relax_kernel<%d>[tiles of %d rows%s] in one workgroup] grid=%ux%u lds=%zu",
-             p->Wc, p->Wc, 64 << lp.tiles,
-             kas_plan_relax_idl(p) ? (kas_plan_mid32(p, lp) ? ", ids in LDS, dword mid rows" : ", ids in LDS") : "",
-             lp.order_grid, lp.order_block, lp.order_lds);
-  else if (lp.relax)
-    snprintf(order, sizeof(order), "kas_order_relax_kernel<%d>[tiles of %d rows%s%s] grid=%ux%u lds=%zu%s", p->Wc,
-             64 << lp.tiles,
-             kas_plan_relax_idl(p) ? (kas_plan_mid32(p, lp) ? ", ids in LDS, dword mid rows" : ", ids in LDS") : "",
-             (p->flags >> 24) ? ", sampled verification" : "", lp.order_grid, lp.order_block, lp.order_lds, ctx_tail);
-  else if (lp.relaxw)
-    snprintf(order, sizeof(order), "kas_order_relax_wide_kernel<%d>[tiles of 64 rows, ids in LDS] grid=%ux%u lds=%zu", p->Wc, lp.order_grid,
-             lp.order_block, lp.order_lds);
-  else if (lp.tickets)
-    snprintf(order, sizeof(order), "%skas_order_ticket_kernel<%d,%d,%s> grid=%ux%u lds=%zu%s",
-             lp.pairing ? "kas_order_permutation_kernel + " : "", p->Wc, p->G, lp.packed ? "true" : "false",
-             lp.order_grid, lp.order_block, lp.order_lds, ctx_tail);
-  else if (lp.wide)
-    snprintf(order, sizeof(order), "kas_order_wide_kernel<%d> grid=%ux%u lds=%zu%s", p->Wc, lp.order_grid,
-             lp.order_block, lp.order_lds, ctx_tail);
-  else
-    snprintf(order, sizeof(order), "kas_order_round_kernel<%d> grid=%ux%u lds=%zu", p->Wc, lp.order_grid,
-             lp.order_block, lp.order_lds);
-  const int32_t chunks = kas_plan_spread_chunks(p);
-  char spread[128];
-  spread[0] = 0;
-  if (chunks > 0)
-    snprintf(spread, sizeof(spread), "kas_spread_{a,q,b,p4}_kernel<%d> %d chunks x %d scenarios (rows not rack-diverse: ", p->Wc,
-             chunks, p->n_scenarios);
-  if (p->shape.relax_ok && !lp.relax && !(p->flags & KAS_FLAG_ROUND_ORDER) && !kas_flags_want_tickets(p->flags)) {
-    const int stt = p->ctx->lds_lane_order_state;              // the form the shape allows is not the one launched: say why
-    const size_t ol = strlen(order);
-    snprintf(order + ol, sizeof(order) - ol, " [relaxation form off: LDS lane-order self-test %s]",
-             stt == 0 ? "FAILED" : (stt == -2 ? "switched off (KAS_NO_LANE_ORDER)" : "could not run"));
-  }
-  char p4[96];
-  p4[0] = 0;
-  if (kas_plan_split_p4(p) && !lp.p4_order)                    // first fit (P4) is a launch of its own between the two
-    snprintf(p4, sizeof(p4), " + kas_p4_kernel<%d> grid=%ux%u lds=%zu", p->Wc, (unsigned)p->n_scenarios, 64u * KAS_P4_KERNEL_WAVES,
-             (size_t)kas_p4_lds_layout(p->shape.n_max).total);
-  if (kas_plan_slim_fill(p, kas_plan_split_p4(p) || lp.p4_order, chunks)) {
-    const unsigned back = kas_plan_back_grid(p, lp.fill_grid);
-    const int len = snprintf(buf, (size_t)n, "kas_fill_slim_kernel<%d>[quota, chunk histograms] grid=%ux%u lds=%zu (+ kas_fill_kernel<%d,%d>[quota, chunk histograms] "
-                             "grid=%ux%u lds=%zu for scenarios it hands back)%s + %s", p->Wc, lp.fill_grid, lp.fill_block,
-                             (size_t)kas_fill_slim_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries).total, p->Wc, p->NW, back,
-                             lp.fill_block, lp.fill_lds, p4, order);
-    return len < n ? len : n - 1;
-  }
-  const int len = snprintf(buf, (size_t)n, "%skas_fill_kernel<%d,%d>[%s] grid=%ux%u lds=%zu%s%s + %s%s", spread, p->Wc, p->NW,
-                           generic ? "sweeps" : (kas_plan_fused(p) ? (kas_plan_index_rows(p) && chunks == 0 ? "quota, chunk histograms, index rows" : "quota, chunk histograms") : "quota"), lp.fill_grid,
-                           lp.fill_block, lp.fill_lds, chunks > 0 ? ")" : "", p4, order, p->cells16 ? " [16-bit cells]" : "");
+  const int len = snprintf(buf, (size_t)n, "%s", kas_describe_launch(kas_resolve_launch(kas_plan_launch_in(p))).c_str());
   return len < n ? len : n - 1;
 }
 
 int64_t kas_plan_algorithmic_bytes(const kas_plan* plan) {
   if (!plan) return -1;
   return plan->cells16 ? plan->shape.algorithmic_bytes16 : plan->shape.algorithmic_bytes;   // (the plan's own cell width)
+}
+
+// the 16-bit side of a host call (nullptr members: the int32 call)
+struct KasCells16 {
+  const uint16_t* cur = nullptr;
+  uint16_t* out = nullptr;
+};
+// a kas_tables16 as the kas_tables the kernels and the host path take: everything but the cells is the int32 call's (the kernels
+// take the cell width from KAS_FLAG_CELLS16, the host path from `c16`)
+static kas_tables kas_tables_of16(const kas_tables16* t16, KasCells16* c16) {
+  kas_tables t;
+  memset(&t, 0, sizeof(t));
+  t.aux = t16->aux; t.ctx = t16->ctx; t.topic_results = t16->topic_results; t.scenario_results = t16->scenario_results;
+  t.cur_len = t16->cur_len; t.out_len = t16->out_len; t.aux_len = t16->aux_len; t.ctx_len = t16->ctx_len;
+  if (c16) { c16->cur = t16->cur; c16->out = t16->out; }
+  else { t.cur = reinterpret_cast<const int32_t*>(t16->cur); t.out = reinterpret_cast<int32_t*>(t16->out); }
+  return t;
 }
 
 static int kas_solve_device_impl(kas_plan* p, const kas_tables* t, void* hip_stream);
@@ -1142,11 +915,7 @@ int kas_solve_device(kas_plan* p, const kas_tables* t, void* hip_stream) {
 int kas_solve_device16(kas_plan* p, const kas_tables16* t16, void* hip_stream) {
   if (!p || !t16) return set_error(KAS_E_INVALID_ARG, "NULL argument");
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_solve_device16 needs a plan of kas_plan_create16");
-  kas_tables t;                                              // (the kernels take the cell width from KAS_FLAG_CELLS16)
-  memset(&t, 0, sizeof(t));
-  t.cur = reinterpret_cast<const int32_t*>(t16->cur); t.out = reinterpret_cast<int32_t*>(t16->out);
-  t.aux = t16->aux; t.ctx = t16->ctx; t.topic_results = t16->topic_results; t.scenario_results = t16->scenario_results;
-  t.cur_len = t16->cur_len; t.out_len = t16->out_len; t.aux_len = t16->aux_len; t.ctx_len = t16->ctx_len;
+  const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_solve_device_impl(p, &t, hip_stream);
 }
 
@@ -1175,124 +944,47 @@ static int kas_solve_device_impl(kas_plan* p, const kas_tables* t, void* hip_str
   p->last_stream = st;
   a.n_scenarios = p->n_scenarios; a.n_max = p->shape.n_max;
   a.idmap_entries = p->shape.idmap_entries; a.need_bsearch = p->shape.need_bsearch;
-  a.flags = (p->flags & ~(KAS_FLAG_FUSED_HIST | KAS_FLAG_ORDER_FLAGGED | KAS_FLAG_WIDE_CHECK)) | (p->shape.with_x ? 0u : KAS_FLAG_GENERIC_FILL) |
-            (kas_plan_fused(p) ? KAS_FLAG_FUSED_HIST : 0u) |
-            (kas_relax_double_tiles(p->flags, p->n_scenarios) ? KAS_FLAG_RELAX_DUAL : 0u) |
-            ((p->ctx->lds_lane_order_ok && !(p->flags & KAS_FLAG_NO_RTN_QUOTA)) ? KAS_FLAG_LANE_ORDER : 0u) |
-            (p->cells16 ? KAS_FLAG_CELLS16 : 0u) | (kas_plan_index_rows(p) ? KAS_FLAG_INDEX_ROWS : 0u);
-  const KasLaunchPlan lp = kas_launch_plan(p);
-  const bool m32 = kas_plan_mid32(p, lp);                      // every kernel of this solve moves mid rows as one dword each
-  if (m32) a.flags |= KAS_FLAG_MID32;
-  const bool tickets = lp.tickets;
-  const bool split_p4 = kas_plan_split_p4(p) || lp.p4_order;   // (the fill kernel hands first fit over: to kas_p4_kernel, or to kas_p4_order_kernel)
   a.p4s = (int32_t*)p->b_p4s.p;
-  a.flags = split_p4 ? (a.flags | KAS_FLAG_SPLIT_P4) : (a.flags & ~KAS_FLAG_SPLIT_P4);   // (the kernels' bit: this launch's form)
-  const int slot = p->timer_next;
   a.sp_hist = nullptr; a.sp_quota = nullptr; a.sp_node = nullptr; a.sp_flag = nullptr; a.sp_oc = nullptr; a.sp_chunks = 0;
   a.handback = nullptr;
-  const int32_t chunks = kas_plan_spread_chunks(p);
-  if (chunks != p->sp_alloc_chunks)
+  // which kernels, on which grids, with which launch words: kas_resolve_launch (kas_launch_plan.h); nothing is chosen here
+  const KasResolvedLaunch L = kas_resolve_launch(kas_plan_launch_in(p));
+  const int slot = p->timer_next;
+  if (L.spread_chunks != p->sp_alloc_chunks)
     return set_error(KAS_E_INVALID_ARG, "internal: spread-fill scratch not sized for this plan state");
   KAS_HIP_TRY(hipEventRecord(p->ev_start[slot], st));
-  if (chunks > 0) {
-    const KasSpreadKernels sk = kas_spread_for(p->Wc);
-    a.sp_hist = (int32_t*)p->b_sp_hist.p; a.sp_quota = (int32_t*)p->b_sp_quota.p; a.sp_node = (int32_t*)p->b_sp_node.p;
-    a.sp_flag = (int32_t*)p->b_sp_flag.p; a.sp_oc = (int32_t*)p->b_sp_oc.p; a.sp_chunks = chunks;
-    KAS_HIP_TRY(hipMemsetAsync(a.sp_flag, 0, 4 * ((size_t)p->n_scenarios + 1), st));
-    KAS_HIP_TRY(hipMemsetAsync(a.sp_oc, 0, 4 * (size_t)p->n_scenarios * ((size_t)chunks + 2), st));
-    const size_t la = (size_t)kas_spread_scan_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries, p->shape.need_bsearch, 1).total;
-    const size_t lb = (size_t)kas_spread_scan_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries, p->shape.need_bsearch, 2).total;
-    const size_t l4 = (size_t)kas_spread_scan_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries, p->shape.need_bsearch, 3).total;
-    const dim3 gc((unsigned)chunks, (unsigned)p->n_scenarios);
-    hipLaunchKernelGGL(sk.a, gc, dim3(64), la, st, a);
-    hipLaunchKernelGGL(sk.q, dim3((unsigned)((p->shape.n_max + 255) / 256), (unsigned)p->n_scenarios), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(sk.b, gc, dim3(64), lb, st, a);
-    hipLaunchKernelGGL(sk.p4, dim3((unsigned)p->n_scenarios), dim3(64 * KAS_SPREAD_P4_WAVES), l4, st, a);
-    KAS_HIP_TRY(hipGetLastError());
-    a.flags |= KAS_FLAG_ONLY_FLAGGED;                              // what is left: scenarios handed back (not rack-diverse, ...)
+  if (L.spread_chunks > 0) {
+    KAS_HIP_TRY(hipMemsetAsync(p->b_sp_flag.p, 0, 4 * ((size_t)p->n_scenarios + 1), st));
+    KAS_HIP_TRY(hipMemsetAsync(p->b_sp_oc.p, 0, 4 * (size_t)p->n_scenarios * ((size_t)L.spread_chunks + 2), st));
   }
-  // (tuning builds, scripts/build_variant.sh -- -DKAS_TUNE_...: one of the two kernels alone, to see what each saturates at.
-  // ORDER_ONLY: the fill runs in the plan's first solve only, and KAS_TUNE_NO_ROW_STORES keeps its mid rows in place.)
-  unsigned fill_grid = lp.fill_grid;
-  if (kas_plan_slim_fill(p, split_p4, chunks)) {
-    // the slim kernel takes every scenario (and writes each one's hand-back flag, 0 or 1); the full kernel behind it takes the
-    // flagged ones on a small grid — its workgroups need a slot of 35 KB of LDS each before they can see that there is nothing to do
-    a.sp_flag = (int32_t*)p->b_sp_flag.p;
+  bool order_phase = false;
+  for (int32_t i = 0; i < L.n_stages; ++i) {
+    const KasStage& sg = L.stages[i];
+    if (sg.role >= KAS_STAGE_PERMUTATION && !order_phase) {      // the fill (+ first fit) is on the stream: the order kernels follow
+      order_phase = true;
+      KAS_HIP_TRY(hipEventRecord(p->ev_mid[slot], st));
+      if (L.find(KAS_STAGE_ROUND_FLAGGED)) KAS_HIP_TRY(hipMemsetAsync(a.ord_flag, 0, 4 * ((size_t)p->n_scenarios + 1), st));
+    }
+    // (tuning builds, scripts/build_variant.sh -- -DKAS_TUNE_...: one of the two kernels alone, to see what each saturates at.
+    // ORDER_ONLY: the fill runs in the plan's first solve only, and KAS_TUNE_NO_ROW_STORES keeps its mid rows in place.)
 #if defined(KAS_TUNE_ORDER_ONLY)
-    if (p->last_slot < 0)
+    if ((sg.role == KAS_STAGE_SLIM || sg.role == KAS_STAGE_FILL) && p->last_slot >= 0) continue;
 #endif
-    hipLaunchKernelGGL(m32 ? kas_fill_slim_m32() : kas_fill_slim_for(p->Wc), dim3(lp.fill_grid), dim3(lp.fill_block),
-                       (size_t)kas_fill_slim_lds(p->shape.n_max, p->Wc, p->shape.idmap_entries).total + KAS_TUNE_SLIM_LDS_PAD, st, a);
-    KAS_HIP_TRY(hipGetLastError());
-    a.flags |= KAS_FLAG_ONLY_FLAGGED;
-    fill_grid = kas_plan_back_grid(p, fill_grid);
-    a.handback = p->d_handback;
-  }
-#if defined(KAS_TUNE_ORDER_ONLY)
-  if (p->last_slot < 0)
-#endif
-  hipLaunchKernelGGL(kas_fill_for(p->Wc, p->NW), dim3(fill_grid), dim3(lp.fill_block), lp.fill_lds, st, a);
-  KAS_HIP_TRY(hipGetLastError());
-  a.flags &= ~KAS_FLAG_ONLY_FLAGGED;
-  if (split_p4 && !lp.p4_order) {
-    hipLaunchKernelGGL(m32 ? kas_p4_m32() : kas_p4_for(p->Wc), dim3((unsigned)p->n_scenarios), dim3(64 * KAS_P4_KERNEL_WAVES),
-                       (size_t)kas_p4_lds_layout(p->shape.n_max).total, st, a);
-    KAS_HIP_TRY(hipGetLastError());
-  }
-  KAS_HIP_TRY(hipEventRecord(p->ev_mid[slot], st));
-  const int packed = lp.packed;
-  // a Context handed in: the ticket forms flag the scenarios whose counters do not fit their count
-  // fields, and the round form (launched behind them, taking only those) serves them
-  // lists 4-5 wide and a node that may hold 1023 .. 2039 rows: the wide form checks its 10-bit count fields when
-  // the last row has retired and flags a scenario that outgrew them.  Its rows are finished (on wrong counts) by
-  // then and its mid rows gone, so it is solved again from `cur`: fill kernel, then round form, both taking only
-  // the flagged scenarios.
-  const bool wide_recheck = lp.wide && p->shape.wide_checked;
-  const bool ctx_fallback = (p->shape.any_ctx && (tickets || lp.wide || lp.relax)) || wide_recheck;
-  if (ctx_fallback) KAS_HIP_TRY(hipMemsetAsync(a.ord_flag, 0, 4 * ((size_t)p->n_scenarios + 1), st));
-  if (wide_recheck) a.flags |= KAS_FLAG_WIDE_CHECK;
-  if (lp.pairing) {
-    // scenarios that share a solver wavefront should have P5 chains of similar length
-    a.perm = (int32_t*)p->b_perm.p;
-    hipLaunchKernelGGL(kas_order_permutation_kernel, dim3(1), dim3(64 * KAS_PERM_WAVES),
-                       sizeof(int32_t) * (size_t)(KAS_PERM_BINS + 8), st, a);
-    KAS_HIP_TRY(hipGetLastError());
-  }
 #if defined(KAS_TUNE_SKIP_ORDER)
-  if (true) {}
-  else
+    if (sg.role == KAS_STAGE_ORDER) continue;
 #endif
-  if (lp.relax && lp.p4_order)
-    hipLaunchKernelGGL(m32 ? kas_p4_order_m32_pick(p->Wc, lp.tiles) : kas_p4_order_for(p->Wc, (a.flags & KAS_FLAG_RELAX_DUAL) != 0u, p->cells16),
-                       dim3(lp.order_grid), dim3(lp.order_block), lp.order_lds, st, a);
-  else if (lp.relax && m32)
-    hipLaunchKernelGGL(kas_order_relax_m32_pick(p->Wc, lp.tiles), dim3(lp.order_grid), dim3(lp.order_block), lp.order_lds, st, a);
-  else if (lp.relax)
-    hipLaunchKernelGGL(kas_order_relax_for(p->Wc, (a.flags & KAS_FLAG_RELAX_DUAL) != 0u, p->shape.any_ctx, (a.flags >> 24) != 0u, p->cells16, kas_plan_relax_idl(p)),
-                       dim3(lp.order_grid), dim3(lp.order_block), lp.order_lds, st, a);
-  else if (lp.relaxw)
-    hipLaunchKernelGGL(kas_order_relaxw_for(p->Wc), dim3(lp.order_grid), dim3(lp.order_block), lp.order_lds, st, a);
-  else if (tickets)
-    hipLaunchKernelGGL(kas_order_ticket_for(p->Wc, p->G, packed), dim3(lp.order_grid), dim3(lp.order_block),
-                       lp.order_lds, st, a);
-  else if (lp.wide)
-    hipLaunchKernelGGL(kas_order_wide_for(p->Wc), dim3(lp.order_grid), dim3(lp.order_block), lp.order_lds, st, a);
-  else
-    hipLaunchKernelGGL(kas_order_round_for(p->Wc), dim3(lp.order_grid), dim3(lp.order_block), lp.order_lds, st, a);
-  KAS_HIP_TRY(hipGetLastError());
-  if (wide_recheck) {
-    KasLaunch af = a;
-    af.flags = (af.flags | KAS_FLAG_ONLY_FLAGGED) & ~(KAS_FLAG_WIDE_CHECK | KAS_FLAG_SPLIT_P4);   // (this fill does its own first fit)
-    af.sp_flag = a.ord_flag;                                 // (same meaning: != 0, this kernel takes the scenario)
-    af.handback = nullptr;
-    hipLaunchKernelGGL(kas_fill_for(p->Wc, p->NW), dim3(lp.fill_grid), dim3(lp.fill_block), lp.fill_lds, st, af);
-    KAS_HIP_TRY(hipGetLastError());
-  }
-  if (ctx_fallback) {
-    a.flags |= KAS_FLAG_ORDER_FLAGGED;
-    a.perm = nullptr;
-    hipLaunchKernelGGL(kas_order_round_for(p->Wc), dim3((unsigned)p->n_scenarios), dim3(64),
-                       (size_t)kas_order_round_lds(p->shape.n_max, p->Wc), st, a);
+    const kas_kernel_fn fn = kas_kernel_for(sg.k);
+    if (!fn) return set_error(KAS_E_UNSUPPORTED, "internal: " + kas_kernel_name(sg.k) + " is not an instance of this build");
+    KasLaunch b = a;
+    b.flags = sg.flags;
+    b.perm = sg.perm ? (int32_t*)p->b_perm.p : nullptr;
+    b.sp_flag = sg.sp_flag == KAS_SP_FLAG_PLAN ? (int32_t*)p->b_sp_flag.p : (sg.sp_flag == KAS_SP_FLAG_ORD ? a.ord_flag : nullptr);
+    if (sg.spread) {
+      b.sp_hist = (int32_t*)p->b_sp_hist.p; b.sp_quota = (int32_t*)p->b_sp_quota.p; b.sp_node = (int32_t*)p->b_sp_node.p;
+      b.sp_oc = (int32_t*)p->b_sp_oc.p; b.sp_chunks = L.spread_chunks;
+    }
+    if (sg.handback) b.handback = p->d_handback;
+    hipLaunchKernelGGL(fn, dim3(sg.grid_x, sg.grid_y), dim3(sg.block), (size_t)sg.lds, st, b);
     KAS_HIP_TRY(hipGetLastError());
   }
   KAS_HIP_TRY(hipEventRecord(p->ev_stop[slot], st));
@@ -1384,10 +1076,7 @@ int kas_impact_device(kas_plan* p, const kas_tables* t, const kas_impact_tables*
 int kas_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, void* hip_stream) {
   if (!p || !t16 || !imp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_impact_device16 needs a plan of kas_plan_create16");
-  kas_tables t;
-  memset(&t, 0, sizeof(t));
-  t.cur = reinterpret_cast<const int32_t*>(t16->cur); t.out = reinterpret_cast<int32_t*>(t16->out);
-  t.aux = t16->aux; t.ctx = t16->ctx; t.topic_results = t16->topic_results; t.scenario_results = t16->scenario_results;
+  const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_impact_impl(p, &t, imp, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
 }
 
@@ -1432,12 +1121,7 @@ int kas_plan_set_flags(kas_plan* p, uint32_t flags) {
     return set_error(KAS_E_INVALID_ARG, "KAS_PLAN_WAVES: waves per scenario must be 1, 2 or 4");
   if (g != 0 && g != 1 && g != 2 && g != 4)
     return set_error(KAS_E_INVALID_ARG, "KAS_PLAN_GROUPS: scenarios per wavefront must be 1, 2 or 4");
-  if ((flags & KAS_FLAG_ROUND_ORDER) && !p->shape.round_fits)
-    return set_error(KAS_E_UNSUPPORTED, "KAS_PLAN_ROUND_ORDER: the round form's LDS exceeds 160 KiB at this broker count x width");
-  if ((flags >> 24) != 0u && p->shape.relax_ok && kas_order_relax_for(p->Wc, 0, p->shape.any_ctx, 1, p->cells16, kas_plan_relax_idl(p)) == nullptr)
-    return set_error(KAS_E_UNSUPPORTED, "KAS_PLAN_VERIFY_SAMPLE: not instantiated for the instances that gather the broker ids from the node table (this many brokers)");
-  if (p->cells16 && kas_flags_want_tickets(flags) && !p->shape.round_fits)
-    return set_error(KAS_E_UNSUPPORTED, "16-bit cells: no ticket form; the round form it would take does not fit at this broker count");
+  if (const char* why = kas_flags_refusal(p->shape, p->cells16 != 0, flags, false)) return set_error(KAS_E_UNSUPPORTED, why);
   if (!kas_minimal_ok(p->Wc, nw ? nw : p->NW, g ? g : p->G))
     return set_error(KAS_E_UNSUPPORTED, "tuning build (KAS_MINIMAL_INSTANCES): only 4 fill waves, 1 or 2 groups");
   const KasShape& sh = p->shape;
@@ -1463,14 +1147,11 @@ int kas_plan_set_flags(kas_plan* p, uint32_t flags) {
   KAS_HIP_TRY(hipSetDevice(p->ctx->device));
   int rc = kas_plan_set_kernels(p);
   if (rc != KAS_E_OK) return rc;
-  p->index_rows_bits = flags & (KAS_PLAN_NO_INDEX_ROWS_BIT | KAS_PLAN_INDEX_ROWS_BIT);
-  p->mid32_bits = flags & (KAS_PLAN_NO_MID32_BIT | KAS_PLAN_MID32_BIT);
-  p->full_fill = flags & KAS_PLAN_FULL_FILL_BIT;
-  p->flags = (flags & (0xff0000ffu | KAS_FLAG_TICKET_ORDER | KAS_FLAG_RELAX_TILES_64 | KAS_FLAG_RELAX_TILES_128 | KAS_FLAG_NO_RTN_QUOTA | KAS_FLAG_FILL_WITH_P4 | KAS_FLAG_SPLIT_P4) & ~(KAS_FLAG_FUSED_HIST | KAS_FLAG_ONLY_FLAGGED | KAS_FLAG_ORDER_FLAGGED)) |
-             (g != 0 ? KAS_FLAG_TICKET_ORDER : 0u);      // (scenarios per wavefront only mean something to the ticket form)
+  const KasUserFlags u = kas_user_flags(flags);
+  p->index_rows_bits = u.index_rows_bits; p->mid32_bits = u.mid32_bits; p->full_fill = u.full_fill; p->flags = u.flags;
   // the spread fill's scratch follows the flags (allocated here, never inside a solve); a solve of this
   // plan may still be in flight on the old scratch
-  if (kas_plan_spread_chunks(p) != p->sp_alloc_chunks) {
+  if (kas_resolve_launch(kas_plan_launch_in(p)).spread_chunks != p->sp_alloc_chunks) {
     if (p->last_slot >= 0) KAS_HIP_TRY(hipEventSynchronize(p->ev_stop[p->last_slot]));
     if ((rc = kas_plan_spread_scratch(p)) != KAS_E_OK) return rc;
   }
@@ -1770,11 +1451,6 @@ static unsigned kas_cells_grid(int64_t n) {
   return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
 }
 
-// the 16-bit side of a host call (nullptr members: the int32 call)
-struct KasCells16 {
-  const uint16_t* cur = nullptr;
-  uint16_t* out = nullptr;
-};
 
 #define KAS_HOST_SPLIT_MIN_BYTES (48ll << 20)   // tables smaller than this are moved and solved as one range
 // Scenario ranges of one call.  A range's solve is a chain of ~2.5-3 ms however few scenarios it holds (one workgroup per
@@ -1811,11 +1487,9 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   }
   const int64_t S = batch->n_scenarios, T = batch->n_topics;
   // A 16-bit call is solved on its 16-bit cells where the kernels with that I/O take the batch (what kas_plan_create16
-  // accepts: lists up to 3 wide, relaxation or round form — kas_plan_build's test, made HERE on the shape: a batch the
-  // 16-bit kernels refuse never reaches the plan cache with the 16-bit bit set); any other batch is widened
-  // before and narrowed behind an int32 solve.
-  bool native16 = c16 != nullptr && full.Wc <= 3 &&
-                  ((full.relax_ok && ctx->lds_lane_order_ok && kas_order_relax_for(full.Wc, 0, 0, 0, 1) != nullptr) || full.round_fits);
+  // accepts, asked HERE on the shape: a batch the 16-bit kernels refuse never reaches the plan cache with the 16-bit bit
+  // set); any other batch is widened before and narrowed behind an int32 solve.
+  bool native16 = c16 != nullptr && kas_cells16_ok(full, ctx->lds_lane_order_ok, kas_built_mask(full.Wc, 1));
   const bool need32 = c16 == nullptr || !native16;             // int32 cell pools on the device
   if (h->cur_len < full.cur_need || (all_rows && h->out_len < full.out_need) || h->aux_len < full.aux_need ||
       h->ctx_len < full.ctx_need)
@@ -2064,12 +1738,8 @@ int kas_solve_host(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* 
 
 int kas_solve_host16(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select) {
   if (!ctx || !batch || !h16) return set_error(KAS_E_INVALID_ARG, "NULL argument");
-  kas_tables h;                                                // everything but the cells is the int32 call's
-  memset(&h, 0, sizeof(h));
-  h.aux = h16->aux; h.ctx = h16->ctx; h.topic_results = h16->topic_results; h.scenario_results = h16->scenario_results;
-  h.cur_len = h16->cur_len; h.out_len = h16->out_len; h.aux_len = h16->aux_len; h.ctx_len = h16->ctx_len;
   KasCells16 c16;
-  c16.cur = h16->cur; c16.out = h16->out;
+  const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16);
 }
@@ -2084,12 +1754,8 @@ int kas_solve_host_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_t
 int kas_solve_host16_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
                             const kas_impact_tables* himp) {
   if (!ctx || !batch || !h16 || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
-  kas_tables h;                                                // everything but the cells is the int32 call's
-  memset(&h, 0, sizeof(h));
-  h.aux = h16->aux; h.ctx = h16->ctx; h.topic_results = h16->topic_results; h.scenario_results = h16->scenario_results;
-  h.cur_len = h16->cur_len; h.out_len = h16->out_len; h.aux_len = h16->aux_len; h.ctx_len = h16->ctx_len;
   KasCells16 c16;
-  c16.cur = h16->cur; c16.out = h16->out;
+  const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp);
 }

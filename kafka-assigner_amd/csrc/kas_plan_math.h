@@ -54,7 +54,7 @@ struct KasLaunch {
   int32_t need_bsearch;         // some scenario's id range exceeds idmap_entries
   uint32_t flags;               // KAS_FLAG_*
   int32_t* handback;            // (may be null) where a fill kernel launched for flagged scenarios only leaves their number: host memory the
-                                // device can write (the plan sizes its next such launch by it, kas_hip.hip: kas_plan_back_grid)
+                                // device can write (the plan sizes its next such launch by it, kas_launch_plan.h: kas_back_grid)
 };
 
 #define KAS_FLAG_GENERIC_FILL 1u   // always use the general sticky fill (testing / comparison)

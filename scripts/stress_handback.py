@@ -1,6 +1,6 @@
 """scripts/stress_handback.py SECONDS [SEED]: random batches of MANY small scenarios of which a random share starts from rows that
 are not rack-diverse — the slim fill kernel hands those back, kas_fill_kernel behind it deals them to its workgroups by rank and
-the plan sizes that launch by the count the previous solve left in pinned host memory (kas_plan_back_grid).  Every batch is solved
+the plan sizes that launch by the count the previous solve left in pinned host memory (kas_back_grid).  Every batch is solved
 three times on ONE plan (grid 256, then grown, then grown again or the same) and once more on a fresh plan with
 KAS_PLAN_FULL_FILL, each time compared bit for bit with the CPU oracle; the describe string must show the grid the count implies.
 MEASUREMENT / TEST TOOLING (GPU only; not part of the pytest suites)."""

@@ -9,6 +9,7 @@
 
 #include "emu/kas_wave.h"     // defines KAS_WAVE_H_ first, so the body's own #include "kas_wave.h" is a no-op
 #include "kas_solver_body.h"
+#include "kas_launch_plan.h"   // the launch resolver the product shares: which kernels, grids, LDS and launch words
 
 namespace kasw {
 
@@ -232,16 +233,10 @@ template <int W, bool DUAL, bool C16, bool IDL, bool M32 = false, bool QUAD = fa
   RunArgs* r = (RunArgs*)p;
   if constexpr (W <= 3) kas::p4_order_scenario<W, DUAL, C16, IDL, M32, QUAD>(*r->a, r->s, r->lds);
 }
-// the instances for dword mid rows (KAS_FLAG_MID32; kas_order_relax_m32_pick in kas_hip.hip)
+// the instances for dword mid rows (KAS_FLAG_MID32)
 template <bool DUAL, bool QUAD = false> void run_order_relax_m32(void* p) {
   RunArgs* r = (RunArgs*)p;
   kas::order_relax<3, DUAL, false, false, false, true, false, true, QUAD>(*r->a, r->s, r->lds);
-}
-typedef void (*relax_fn)(void*);
-template <bool VERIFY, bool C16, bool IDL> relax_fn relax_pick(int Wc, bool dual, bool ctx) {   // as kas_order_relax_pick (kas_hip.hip)
-  if (Wc <= 2) return ctx ? run_order_relax<2, false, true, VERIFY, C16, IDL> : run_order_relax<2, false, false, VERIFY, C16, IDL>;
-  if (ctx) return dual ? run_order_relax<3, true, true, VERIFY, C16, IDL> : run_order_relax<3, false, true, VERIFY, C16, IDL>;
-  return dual ? run_order_relax<3, true, false, VERIFY, C16, IDL> : run_order_relax<3, false, false, VERIFY, C16, IDL>;
 }
 template <int W> void run_order_rounds(void* p) {
   RunArgs* r = (RunArgs*)p;
@@ -252,7 +247,8 @@ struct SpreadArgs { const KasLaunch* a; int32_t s, c; unsigned char* lds; };
 template <int W> void run_spread_a(void* p) { SpreadArgs* r = (SpreadArgs*)p; kas::spread_pass_a<W>(*r->a, r->s, r->c, r->lds); }
 template <int W> void run_spread_b(void* p) { SpreadArgs* r = (SpreadArgs*)p; kas::spread_pass_b<W>(*r->a, r->s, r->c, r->lds); }
 template <int W> void run_spread_p4(void* p) { SpreadArgs* r = (SpreadArgs*)p; kas::spread_p4<W, KAS_SPREAD_P4_WAVES>(*r->a, r->s, r->lds); }
-template <int W> void spread_quota_all(const KasLaunch& a) {
+template <int W> void run_spread_quota(void* p) {
+  const KasLaunch& a = *((SpreadArgs*)p)->a;
   for (int32_t s = 0; s < a.n_scenarios; ++s)
     for (int32_t n = 0; n < a.n_max; ++n) kas::spread_quota<W>(a, s, n);
 }
@@ -265,13 +261,88 @@ template <int W, int NW> void run_fill_block(void* p) {
   kas::fill_block<W, NW>(*r->a, r->block, r->grid, r->lds);
 }
 typedef void (*run_fn)(void*);
-template <int NW> run_fn fill_for_w(int Wc) {
-  switch (Wc) {                            // the same width classes the product launcher uses
-    case 2: return run_fill_block<2, NW>;
-    case 3: return run_fill_block<3, NW>;
-    case 4: return run_fill_block<4, NW>;
-    case 5: return run_fill_block<5, NW>;
-    default: return run_fill_block<8, NW>;
+// relaxation form: the instance for (tiles, Context)
+template <int W, bool VERIFY, bool C16, bool IDL> run_fn relax_instance(const KasKernelId& k) {
+  if constexpr (W == 3)
+    if (k.tiles == 1) return k.ctx ? run_order_relax<3, true, true, VERIFY, C16, IDL> : run_order_relax<3, true, false, VERIFY, C16, IDL>;
+  if (k.tiles != 0) return nullptr;
+  return k.ctx ? run_order_relax<W, false, true, VERIFY, C16, IDL> : run_order_relax<W, false, false, VERIFY, C16, IDL>;
+}
+template <int W, bool C16> run_fn p4_order_instance(const KasKernelId& k) {
+  if constexpr (W == 3)
+    if (k.tiles == 1) return run_p4_order<3, true, C16, !C16>;
+  return k.tiles == 0 ? run_p4_order<W, false, C16, !C16> : nullptr;
+}
+// kernel identity (kas_launch_plan.h) -> the function a fiber runs; the same width classes and instances the product's mapping has
+// (+ 8 fill wavefronts per scenario, which exist here only)
+template <int W> run_fn emu_kernel_w(const KasKernelId& k) {
+  switch (k.family) {
+    case KAS_K_FILL:
+      return k.NW == 1 ? run_fill_block<W, 1> : k.NW == 2 ? run_fill_block<W, 2> : k.NW == 4 ? run_fill_block<W, 4> : k.NW == 8 ? run_fill_block<W, 8> : nullptr;
+    case KAS_K_FILL_SLIM:
+      if constexpr (W == 3) if (k.m32) return run_fill_slim<3, 1>;
+      if constexpr (W <= 3) if (!k.m32) return run_fill_slim<W>;
+      return nullptr;
+    case KAS_K_P4:
+      if constexpr (W == 3) if (k.m32) return run_p4<3, 1>;
+      return k.m32 ? nullptr : run_p4<W>;
+    case KAS_K_ORDER_RELAX:
+      if constexpr (W == 3)
+        if (k.m32) {
+          if (!k.idl || k.ctx || k.verify || k.c16) return nullptr;
+          return k.tiles == 2 ? run_order_relax_m32<true, true> : k.tiles == 1 ? run_order_relax_m32<true> : run_order_relax_m32<false>;
+        }
+      if constexpr (W <= 3) {
+        if (k.m32 || (k.c16 && k.idl)) return nullptr;
+        if (k.c16) return k.verify ? relax_instance<W, true, true, false>(k) : relax_instance<W, false, true, false>(k);
+        if (k.idl) return k.verify ? relax_instance<W, true, false, true>(k) : relax_instance<W, false, false, true>(k);
+        return k.verify ? nullptr : relax_instance<W, false, false, false>(k);
+      }
+      return nullptr;
+    case KAS_K_P4_ORDER:
+      if constexpr (W == 3)
+        if (k.m32) {
+          if (!k.idl || k.c16) return nullptr;
+          return k.tiles == 2 ? run_p4_order<3, true, false, true, true, true> : k.tiles == 1 ? run_p4_order<3, true, false, true, true> : run_p4_order<3, false, false, true, true>;
+        }
+      if constexpr (W <= 3) {
+        if (k.m32 || (k.c16 != 0) == (k.idl != 0)) return nullptr;
+        return k.c16 ? p4_order_instance<W, true>(k) : p4_order_instance<W, false>(k);
+      }
+      return nullptr;
+    case KAS_K_ORDER_RELAX_WIDE:
+      if constexpr (W == 4 || W == 5) return run_order_relax_wide<W>;
+      return nullptr;
+    case KAS_K_ORDER_TICKET:
+      if constexpr (W <= 3) {
+        if (k.G == 1) return k.packed ? run_order_tickets<W, 1, true> : run_order_tickets<W, 1, false>;
+        if (k.G == 2) return k.packed ? run_order_tickets<W, 2, true> : run_order_tickets<W, 2, false>;
+        if (k.G == 4) return k.packed ? run_order_tickets<W, 4, true> : run_order_tickets<W, 4, false>;
+      }
+      return nullptr;
+    case KAS_K_ORDER_WIDE:
+      if constexpr (W == 4 || W == 5) return run_order_wide<W>;
+      return nullptr;
+    case KAS_K_ORDER_ROUND: return run_order_rounds<W>;
+    default:
+      if constexpr (W >= 3 && W <= 5) {
+        if (k.family == KAS_K_SPREAD_A) return run_spread_a<W>;
+        if (k.family == KAS_K_SPREAD_Q) return run_spread_quota<W>;
+        if (k.family == KAS_K_SPREAD_B) return run_spread_b<W>;
+        if (k.family == KAS_K_SPREAD_P4) return run_spread_p4<W>;
+      }
+      return nullptr;
+  }
+}
+run_fn emu_kernel_for(const KasKernelId& k) {
+  if (k.family == KAS_K_PERMUTATION) return run_permutation;
+  switch (k.W) {
+    case 2: return emu_kernel_w<2>(k);
+    case 3: return emu_kernel_w<3>(k);
+    case 4: return emu_kernel_w<4>(k);
+    case 5: return emu_kernel_w<5>(k);
+    case 8: return emu_kernel_w<8>(k);
+    default: return nullptr;
   }
 }
 // workgroups of an emulated kas_fill_kernel launch: KAS_EMU_FILL_GRID (default 3: most batches of the suites then have workgroups
@@ -283,35 +354,6 @@ static int32_t emu_fill_grid(int32_t n_scenarios) {
   return g < n_scenarios ? g : (n_scenarios > 0 ? n_scenarios : 1);
 }
 static int g_last_handback = -1;           // what the last by-rank launch left in KasLaunch::handback (-1: there was none)
-// one emulated launch of kas_fill_kernel; returns the workgroup that failed, or -1
-static int32_t emu_launch_fill(run_fn fill, KasLaunch& a, int NW, std::vector<unsigned char>& lds, int32_t n_scenarios, bool want_handback) {
-  const int32_t G = emu_fill_grid(n_scenarios);
-  int32_t hb = -1;
-  a.handback = want_handback ? &hb : nullptr;
-  for (int32_t blk = 0; blk < G; ++blk) {
-    memset(lds.data(), 0xCD, lds.size());   // LDS is uninitialised on hardware too
-    BlockArgs ra{&a, blk, G, lds.data()};
-    if (kasw::run_block(fill, &ra, NW) != 0) { a.handback = nullptr; return blk; }
-  }
-  a.handback = nullptr;
-  if (want_handback) g_last_handback = hb;
-  return -1;
-}
-template <int G, bool PK> run_fn tickets_for_g(int Wc) {
-  switch (Wc) {
-    case 2: return run_order_tickets<2, G, PK>;
-    default: return run_order_tickets<3, G, PK>;
-  }
-}
-run_fn rounds_for(int Wc) {
-  switch (Wc) {
-    case 2: return run_order_rounds<2>;
-    case 3: return run_order_rounds<3>;
-    case 4: return run_order_rounds<4>;
-    case 5: return run_order_rounds<5>;
-    default: return run_order_rounds<8>;
-  }
-}
 
 }  // namespace
 
@@ -355,342 +397,219 @@ int kas_emu_solve_batch16(const kas_batch_desc* b, const kas_tables* t, unsigned
 static int emu_solve(const kas_batch_desc* b, const kas_tables* t, unsigned flags, char* errbuf, int errlen, bool c16) {
   KasShape sh;
   std::string err;
+  auto refuse = [&](int code, const char* why) {
+    if (errbuf && errlen > 0) { strncpy(errbuf, why, (size_t)errlen - 1); errbuf[errlen - 1] = 0; }
+    return code;
+  };
   int rc = kas_shape_batch(b, &sh, &err, (int)((flags >> 8) & 0xfu), (int)((flags >> 12) & 0xfu));
-  if (rc != KAS_E_OK) {
-    if (errbuf && errlen > 0) { strncpy(errbuf, err.c_str(), (size_t)errlen - 1); errbuf[errlen - 1] = 0; }
-    return rc;
-  }
-  if (c16 && (sh.Wc > 3 || !(sh.relax_ok || sh.round_fits))) {   // (kas_plan_build's refusal for plans with 16-bit cells)
-    if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "16-bit cells: lists up to 3 wide, relaxation or round form");
-    return KAS_E_UNSUPPORTED;
-  }
-  if (c16 && kas_flags_want_tickets(flags) && !sh.round_fits) {   // (kas_plan_set_flags' refusal)
-    if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "16-bit cells: no ticket form");
-    return KAS_E_UNSUPPORTED;
-  }
-  // (the launch decisions of kas_launch_plan in kas_hip.hip)
-  const bool relax = sh.relax_ok && !(flags & KAS_FLAG_ROUND_ORDER) && !(kas_flags_want_tickets(flags) && sh.tickets_ok);
-  const bool tickets = !relax && sh.tickets_ok && !(flags & KAS_FLAG_ROUND_ORDER) && !c16;
-  const bool relaxw = !relax && !c16 && sh.relaxw_ok && kas_relaxw_wanted(flags);   // relaxation form for lists 4 and 5 wide
-  const bool wide = !relaxw && sh.wide_ok && !(flags & KAS_FLAG_ROUND_ORDER) && !c16;
-  g_last_order_form = relax ? 3 : (relaxw ? 4 : (tickets ? 1 : (wide ? 2 : 0)));
+  if (rc != KAS_E_OK) return refuse(rc, err.c_str());
+  // the plan's state as kas_plan_create(16) + kas_plan_set_flags(flags) leave it, on a context whose self-test passed
+  KasLaunchIn in;
+  kas_launch_in_shape(&in, &sh);
+  in.n_scenarios = b->n_scenarios; in.single_topic = kas_batch_single_topic(b) ? 1 : 0; in.cells16 = c16 ? 1 : 0;
+  in.relax_gather = getenv("KAS_EMU_RELAX_GATHER") && getenv("KAS_EMU_RELAX_GATHER")[0] == '1';
+  kas_launch_in_user_flags(&in, flags);
+  if (c16 && !kas_cells16_ok(sh, in.lane_order_ok, in.built)) return refuse(KAS_E_UNSUPPORTED, "16-bit cells: lists up to 3 wide, relaxation or round form");
+  if (const char* why = kas_flags_refusal(sh, c16, flags, in.relax_gather != 0)) return refuse(KAS_E_UNSUPPORTED, why);
+  const KasResolvedLaunch L = kas_resolve_launch(in);
+  const int32_t S = b->n_scenarios, CH = L.spread_chunks;
+  const KasStage* order = L.find(KAS_STAGE_ORDER);
+  g_last_order_form = L.order_form;
+  g_last_fused = (L.flags & KAS_FLAG_FUSED_HIST) ? 1 : 0;
+  g_last_mid32 = (L.flags & KAS_FLAG_MID32) ? 1 : 0;
+  g_last_p4_order = order->k.family == KAS_K_P4_ORDER ? 1 : 0;
+  g_last_split_p4 = L.find(KAS_STAGE_P4) ? 1 : 0;
+  g_last_relax_quad = L.order_form == 3 && order->k.tiles == 2 ? 1 : 0;
+  if (L.order_form == 3) g_last_relax_idl = order->k.idl;
   g_last_relax_tiles = 0; g_last_relax_evals = 0; g_last_relax_slow = 0;
+  g_last_queue_rows = 0; g_last_flagged = 0; g_last_index_rows = 0; g_last_spread = 0; g_last_slim_fill = 0; g_last_handback = -1;
+  // scratch the kernels must write before they read it
   std::vector<uint64_t> accmask((size_t)sh.accmask_words + 1, 0xDEADBEEFDEADBEEFull);
   std::vector<int32_t> orph((size_t)sh.orph_ints + 64, (int32_t)0xDEADBEEF);
-  const bool fused = sh.fused_ok && !(flags & KAS_FLAG_TWO_PASS_HIST) && !(flags & KAS_FLAG_GENERIC_FILL);
-  size_t lds_bytes = (size_t)(fused ? sh.lds_fused.total : sh.lds.total);
-  if (sh.round_fits && (size_t)kas_order_round_lds(sh.n_max, sh.Wc) > lds_bytes) lds_bytes = (size_t)kas_order_round_lds(sh.n_max, sh.Wc);
-  if ((flags & KAS_FLAG_ROUND_ORDER) && !sh.round_fits) {
-    if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "round form does not fit LDS");
-    return KAS_E_UNSUPPORTED;
-  }
-  if ((size_t)kas_order_ticket_lds(sh.n_max, sh.G, 0) > lds_bytes) lds_bytes = (size_t)kas_order_ticket_lds(sh.n_max, sh.G, 0);
-  if ((size_t)kas_order_relax_lds(sh.n_max, 1, 1, 1) > lds_bytes) lds_bytes = (size_t)kas_order_relax_lds(sh.n_max, 1, 1, 1);   // (an upper bound)
-  if (wide && (size_t)kas_order_wide_lds(sh.n_max) > lds_bytes) lds_bytes = (size_t)kas_order_wide_lds(sh.n_max);
-  if (lds_bytes < sizeof(int32_t) * (KAS_PERM_BINS + 8)) lds_bytes = sizeof(int32_t) * (KAS_PERM_BINS + 8);
-  std::vector<unsigned char> lds(lds_bytes + 64, 0xCD);
+  std::vector<int64_t> stats((size_t)KAS_STATS_PER_SCENARIO * (size_t)(S + 1), 0);
+  std::vector<int32_t> perm((size_t)S + 1, -1);
+  std::vector<int32_t> ord_flag((size_t)S + 1, 0);      // scenarios an order kernel leaves to the round form
+  std::vector<int32_t> sp_hist, sp_quota, sp_node, sp_oc, p4s;
+  std::vector<int32_t> sp_flag((size_t)S + 1, CH > 0 ? 0 : (int32_t)0xDEADBEEF);   // (the slim kernel writes every scenario's; the spread fill's are cleared)
   KasLaunch a;
   a.scen = b->scenarios; a.topics = b->topics; a.node_id = b->node_id; a.node_rack = b->node_rack;
   a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.ctx = t->ctx;
   a.topic_results = t->topic_results; a.scenario_results = t->scenario_results;
   a.accmask = accmask.data(); a.accmask_off = sh.accmask_off.data();
-  std::vector<int64_t> stats((size_t)KAS_STATS_PER_SCENARIO * (size_t)(b->n_scenarios + 1), 0);
   a.stats = stats.data();
-  g_last_queue_rows = 0;
-  g_last_fused = fused ? 1 : 0;
   a.orph = orph.data(); a.orph_off = sh.orph_off.data();
-  std::vector<int32_t> perm((size_t)b->n_scenarios + 1, -1);
-  a.perm = nullptr;
-  std::vector<int32_t> ord_flag((size_t)b->n_scenarios + 1, 0);   // scenarios a ticket form leaves to the round form
-  a.ord_flag = ord_flag.data();
-  g_last_flagged = 0;
-  a.n_scenarios = b->n_scenarios; a.n_max = sh.n_max; a.idmap_entries = sh.idmap_entries;
-  a.need_bsearch = sh.need_bsearch;
-  // (bit 64 of the caller's word is KAS_PLAN_NO_INDEX_ROWS, of a launch word KAS_FLAG_ONLY_FLAGGED: as kas_plan_set_flags / kas_plan_index_rows)
-  const bool index_rows = !c16 && kas_index_rows_wanted(flags) && sh.Wc <= 3 && fused && !(flags & KAS_FLAG_NO_RTN_QUOTA) &&
-                          sh.n_max < 0x3fff && sh.idmap_entries > 0;
-  a.flags = (flags & (0xff0000ffu | KAS_FLAG_TICKET_ORDER | KAS_FLAG_RELAX_TILES_64 | KAS_FLAG_RELAX_TILES_128 | KAS_FLAG_FILL_WITH_P4 | KAS_FLAG_SPLIT_P4) & ~(KAS_FLAG_FUSED_HIST | KAS_FLAG_ONLY_FLAGGED | KAS_FLAG_ORDER_FLAGGED)) |
-            (sh.with_x ? 0u : KAS_FLAG_GENERIC_FILL) | (fused ? KAS_FLAG_FUSED_HIST : 0u) |
-            (kas_relax_double_tiles(flags, b->n_scenarios) ? KAS_FLAG_RELAX_DUAL : 0u) |
-            ((flags & KAS_FLAG_NO_RTN_QUOTA) ? 0u : KAS_FLAG_LANE_ORDER) | (c16 ? KAS_FLAG_CELLS16 : 0u) |
-            (index_rows ? KAS_FLAG_INDEX_ROWS : 0u);
-  g_last_index_rows = 0;
-  g_last_mid32 = 0;
-  auto bad = [&](const char* what, int32_t s) {
-    if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "wave divergence / deadlock in the %s kernel, scenario %d", what, s);
-    return -100;
-  };
-  // spread fill (same decision as kas_solve_device): passes A and B over one-wavefront workgroups
+  a.perm = nullptr; a.ord_flag = ord_flag.data();
+  a.n_scenarios = S; a.n_max = sh.n_max; a.idmap_entries = sh.idmap_entries; a.need_bsearch = sh.need_bsearch;
   a.sp_hist = nullptr; a.sp_quota = nullptr; a.sp_node = nullptr; a.sp_flag = nullptr; a.sp_oc = nullptr; a.sp_chunks = 0;
-  a.handback = nullptr;                                  // (set by emu_launch_fill for a by-rank launch)
-  g_last_spread = 0;
-  const int32_t CH = (!c16 && sh.NW == 4 && sh.Wc >= 3 && sh.Wc <= 5 && !(flags & KAS_FLAG_GENERIC_FILL))
-                         ? kas_spread_chunks(sh, b->n_scenarios, kas_batch_single_topic(b), (flags & KAS_FLAG_SPREAD_FILL) != 0) : 0;
-  std::vector<int32_t> sp_hist, sp_quota, sp_node, sp_flag, sp_oc;
+  a.handback = nullptr; a.p4s = nullptr;
   if (CH > 0) {
-    const size_t S = (size_t)b->n_scenarios, NM = (size_t)sh.n_max;
-    sp_hist.assign(S * (size_t)CH * (size_t)sh.Wc * NM + 1, (int32_t)0xDEADBEEF);
-    sp_quota.assign(S * (size_t)CH * NM + 1, (int32_t)0xDEADBEEF);
-    sp_node.assign(S * 2 * NM + 1, (int32_t)0xDEADBEEF);
-    sp_flag.assign(S + 1, 0);
-    sp_oc.assign(S * (size_t)(CH + 2) + 1, 0);
-    a.sp_hist = sp_hist.data(); a.sp_quota = sp_quota.data(); a.sp_node = sp_node.data();
-    a.sp_flag = sp_flag.data(); a.sp_oc = sp_oc.data(); a.sp_chunks = CH;
-    if ((size_t)kas_fill_lds_layout(sh.n_max, sh.Wc, 1, sh.idmap_entries, sh.need_bsearch, 1).total > lds.size()) return bad("spread fill (LDS)", 0);
-    run_fn fa = sh.Wc == 3 ? run_spread_a<3> : sh.Wc == 4 ? run_spread_a<4> : run_spread_a<5>;
-    run_fn fb = sh.Wc == 3 ? run_spread_b<3> : sh.Wc == 4 ? run_spread_b<4> : run_spread_b<5>;
-    run_fn fp = sh.Wc == 3 ? run_spread_p4<3> : sh.Wc == 4 ? run_spread_p4<4> : run_spread_p4<5>;
-    for (int32_t s = 0; s < b->n_scenarios; ++s)
-      for (int32_t c = 0; c < CH; ++c) {
-        memset(lds.data(), 0xCD, lds.size());
-        SpreadArgs ra{&a, s, c, lds.data()};
-        if (kasw::run_block(fa, &ra, 1) != 0) return bad("spread fill A", s);
-      }
-    if (sh.Wc == 3) spread_quota_all<3>(a); else if (sh.Wc == 4) spread_quota_all<4>(a); else spread_quota_all<5>(a);
-    for (int32_t s = 0; s < b->n_scenarios; ++s)
-      for (int32_t c = 0; c < CH; ++c) {
-        memset(lds.data(), 0xCD, lds.size());
-        SpreadArgs ra{&a, s, c, lds.data()};
-        if (kasw::run_block(fb, &ra, 1) != 0) return bad("spread fill B", s);
-      }
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(lds.data(), 0xCD, lds.size());
-      SpreadArgs ra{&a, s, 0, lds.data()};
-      if (kasw::run_block(fp, &ra, KAS_SPREAD_P4_WAVES) != 0) return bad("spread fill P4", s);
-      g_last_spread += sp_flag[(size_t)s] == 0 ? 1 : 0;
-    }
-    a.flags |= KAS_FLAG_ONLY_FLAGGED;
+    const size_t NM = (size_t)sh.n_max;
+    sp_hist.assign((size_t)S * (size_t)CH * (size_t)sh.Wc * NM + 1, (int32_t)0xDEADBEEF);
+    sp_quota.assign((size_t)S * (size_t)CH * NM + 1, (int32_t)0xDEADBEEF);
+    sp_node.assign((size_t)S * 2 * NM + 1, (int32_t)0xDEADBEEF);
+    sp_oc.assign((size_t)S * (size_t)(CH + 2) + 1, 0);
   }
-  // fill kernel: one workgroup of NW wavefronts per scenario
-  run_fn fill = nullptr;
-  switch (sh.NW) {
-    case 1: fill = fill_for_w<1>(sh.Wc); break;
-    case 2: fill = fill_for_w<2>(sh.Wc); break;
-    case 8: fill = fill_for_w<8>(sh.Wc); break;
-    default: fill = fill_for_w<4>(sh.Wc); break;
-  }
-  // first fit in a kernel of its own (same decision as kas_solve_device)
-  std::vector<int32_t> p4s;
-  a.p4s = nullptr;
-  // first fit inside the order kernel's workgroup (kas_p4_order_kernel; same decision as kas_launch_plan in kas_hip.hip)
-  const bool relax_dual = sh.Wc == 3 && (a.flags & KAS_FLAG_RELAX_DUAL) != 0u;
-  const bool relax_idl = !c16 && kas_relax_lds_ids(sh.n_max, sh.any_ctx) && !(getenv("KAS_EMU_RELAX_GATHER") && getenv("KAS_EMU_RELAX_GATHER")[0] == '1');
-  // dword mid rows (same decision as kas_plan_mid32 in kas_hip.hip)
-  const bool m32 = kas_mid32_launch(sh, c16, flags, relax, a.flags, relax_idl ? 1 : 0, index_rows, CH);
-  if (m32) a.flags |= KAS_FLAG_MID32;
-  g_last_mid32 = m32 ? 1 : 0;
-  // quad tiles (same decision as kas_launch_plan in kas_hip.hip): double tiles + dword mid rows + asked for
-  const bool relax_quad = relax_dual && m32 && kas_relax_quad_tiles(flags, b->n_scenarios) && kas_order_relax_lds(sh.n_max, 2, 0, 1) <= KAS_LDS_LIMIT;
-  const int relax_tiles = relax_quad ? 2 : (relax_dual ? 1 : 0);
-  g_last_relax_quad = relax && relax_quad ? 1 : 0;
-  const bool p4_order = relax && kas_p4_with_order(sh, sh.NW, a.flags, CH, b->n_scenarios,
-                                                   !sh.any_ctx && (a.flags >> 24) == 0u && (c16 || relax_idl), relax_tiles, relax_idl);
-  g_last_p4_order = p4_order ? 1 : 0;
-  const bool split_p4 = p4_order || kas_split_p4(sh, sh.NW, a.flags, CH, b->n_scenarios);   // (the fill kernel hands first fit over)
-  if (split_p4) {
+  if (L.flags & KAS_FLAG_SPLIT_P4) {
     p4s.assign((size_t)b->n_topics * (size_t)(KAS_P4S_HEAD + (sh.n_max > 0 ? sh.n_max : 1)) + 64, (int32_t)0xDEADBEEF);
     a.p4s = p4s.data();
-    a.flags |= KAS_FLAG_SPLIT_P4;
-  } else {
-    a.flags &= ~KAS_FLAG_SPLIT_P4;
   }
-  g_last_split_p4 = (split_p4 && !p4_order) ? 1 : 0;
-  // the slim fill kernel in front (same decision as kas_plan_slim_fill in kas_hip.hip): it writes every scenario's hand-back flag
-  const bool slim = KAS_SLIM_FILL_DEFAULT && !(flags & KAS_PLAN_FULL_FILL_BIT) && !c16 && sh.Wc <= 3 && sh.NW == 4 && fused && sh.with_x &&
-                    !(flags & KAS_FLAG_NO_RTN_QUOTA) && !index_rows && split_p4 && CH == 0 && sh.idmap_entries > 0 && !sh.need_bsearch;
-  g_last_slim_fill = 0;
-  if (slim) {
-    sp_flag.assign((size_t)b->n_scenarios + 1, (int32_t)0xDEADBEEF);
-    a.sp_flag = sp_flag.data();
-    run_fn fs = sh.Wc <= 2 ? run_fill_slim<2> : (m32 ? run_fill_slim<3, 1> : run_fill_slim<3>);   // (the product's instance per mid-row layout)
-    // exactly the LDS the product launches kas_fill_slim_kernel with (kas_fill_slim_lds), and a guard behind it
-    const size_t slim_bytes = (size_t)kas_fill_slim_lds(sh.n_max, sh.Wc, sh.idmap_entries).total;
-    std::vector<unsigned char> sl(slim_bytes + 4096);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(sl.data(), 0xCD, slim_bytes);
-      memset(sl.data() + slim_bytes, 0xA5, 4096);
-      RunArgs ra{&a, s, sl.data()};
-      if (kasw::run_block(fs, &ra, 4) != 0) return bad("slim fill", s);
-      for (size_t i = 0; i < 4096; ++i)
-        if (sl[slim_bytes + i] != 0xA5) return bad("slim fill: LDS written beyond kas_fill_slim_lds()", s);
-      if (sp_flag[(size_t)s] != 0 && sp_flag[(size_t)s] != 1) return bad("slim fill (hand-back flag not written)", s);
-      g_last_slim_fill += sp_flag[(size_t)s] == 0 ? 1 : 0;
+  auto bad = [&](const std::string& what, int32_t s) {
+    if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "wave divergence / deadlock in %s, workgroup %d", what.c_str(), s);
+    return -100;
+  };
+  const size_t GUARD = 4096;
+  for (int32_t i = 0; i < L.n_stages; ++i) {
+    const KasStage& sg = L.stages[i];
+    const run_fn f = emu_kernel_for(sg.k);
+    const std::string name = kas_kernel_name(sg.k);
+    if (!f) return refuse(KAS_E_UNSUPPORTED, (name + ": no such instance").c_str());
+    KasLaunch la = a;
+    la.flags = sg.flags;
+    la.perm = sg.perm ? perm.data() : nullptr;
+    la.sp_flag = sg.sp_flag == KAS_SP_FLAG_PLAN ? sp_flag.data() : (sg.sp_flag == KAS_SP_FLAG_ORD ? ord_flag.data() : nullptr);
+    if (sg.spread) { la.sp_hist = sp_hist.data(); la.sp_quota = sp_quota.data(); la.sp_node = sp_node.data(); la.sp_oc = sp_oc.data(); la.sp_chunks = CH; }
+    // the by-rank launch's count (the product asks for it behind the slim kernel; here behind the spread fill too)
+    int32_t hb = -1;
+    const bool by_rank = sg.role == KAS_STAGE_FILL && sg.sp_flag == KAS_SP_FLAG_PLAN;
+    if (by_rank) la.handback = &hb;
+    if (sg.role == KAS_STAGE_ROUND_FLAGGED)
+      for (int32_t s = 0; s < S; ++s) g_last_flagged += ord_flag[(size_t)s] != 0 ? 1 : 0;
+    if (sg.k.family == KAS_K_SPREAD_Q) {                     // (a thread per (scenario, node): no collectives)
+      SpreadArgs ra{&la, 0, 0, nullptr};
+      f(&ra);
+      continue;
     }
-    a.flags |= KAS_FLAG_ONLY_FLAGGED;
-  }
-  g_last_handback = -1;
-  {
-    const bool by_rank = (a.flags & KAS_FLAG_ONLY_FLAGGED) != 0u && a.sp_flag != nullptr;
-    const int32_t failed = emu_launch_fill(fill, a, sh.NW, lds, b->n_scenarios, by_rank);
-    if (failed >= 0) return bad("fill (workgroup)", failed);
-  }
-  for (int32_t s = 0; s < b->n_scenarios; ++s)
-    g_last_index_rows += (long)a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + 6];   // (the fill's own tally, before an order kernel writes there)
-  a.flags &= ~KAS_FLAG_ONLY_FLAGGED;
-  if (split_p4 && !p4_order) {
-    // exactly the LDS the product launches kas_p4_kernel with, and a guard behind it
-    const size_t p4_bytes = (size_t)kas_p4_lds_layout(sh.n_max).total;
-    std::vector<unsigned char> pl(p4_bytes + 4096);
-    run_fn fp4 = sh.Wc <= 2 ? run_p4<2> : sh.Wc == 3 ? (m32 ? run_p4<3, 1> : run_p4<3>) : sh.Wc == 4 ? run_p4<4> : sh.Wc == 5 ? run_p4<5> : run_p4<8>;
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(pl.data(), 0xCD, p4_bytes);
-      memset(pl.data() + p4_bytes, 0xA5, 4096);
-      RunArgs ra{&a, s, pl.data()};
-      if (kasw::run_block(fp4, &ra, 1) != 0) return bad("first fit (kas_p4_kernel)", s);
-      for (size_t i = 0; i < 4096; ++i)
-        if (pl[p4_bytes + i] != 0xA5) return bad("first fit: LDS written beyond kas_p4_lds_layout()", s);
+    // every workgroup on exactly the LDS the product launches the kernel with, uninitialised as on hardware, and a guard behind it:
+    // the hardware drops what a workgroup writes beyond its allocation and reads zeros there — here that must not pass unnoticed
+    std::vector<unsigned char> lds((size_t)sg.lds + GUARD);
+    const bool per_chunk = sg.k.family == KAS_K_SPREAD_A || sg.k.family == KAS_K_SPREAD_B;
+    const bool is_fill = sg.k.family == KAS_K_FILL;
+    const int32_t step = sg.k.family == KAS_K_ORDER_TICKET ? sg.k.G : 1;
+    const int32_t n_blocks = sg.k.family == KAS_K_PERMUTATION ? 1 : is_fill ? emu_fill_grid(S) : per_chunk ? S * CH : (S + step - 1) / step;
+    for (int32_t blk = 0; blk < n_blocks; ++blk) {
+      memset(lds.data(), 0xCD, (size_t)sg.lds);
+      memset(lds.data() + sg.lds, 0xA5, GUARD);
+      int r;
+      if (is_fill) {                                          // (fill_block: its loop over the scenarios it takes, the LDS NOT cleared between them)
+        BlockArgs ra{&la, blk, n_blocks, lds.data()};
+        r = kasw::run_block(f, &ra, (int)sg.block / 64);
+      } else if (sg.role == KAS_STAGE_SPREAD) {
+        SpreadArgs ra{&la, per_chunk ? blk / CH : blk, per_chunk ? blk % CH : 0, lds.data()};
+        r = kasw::run_block(f, &ra, (int)sg.block / 64);
+      } else {
+        RunArgs ra{&la, blk * step, lds.data()};
+        r = kasw::run_block(f, &ra, (int)sg.block / 64);
+      }
+      if (r != 0) return bad(name, blk);
+      for (size_t j = 0; j < GUARD; ++j)
+        if (lds[(size_t)sg.lds + j] != 0xA5) return bad(name + ": LDS written beyond the launch's allocation", blk);
     }
-  }
-  // order kernel: one wavefront per scenario (relaxation form, round form), three per G scenarios (ticket form)
-  if (relax && p4_order) {
-    run_fn f = m32 ? (relax_quad ? run_p4_order<3, true, false, true, true, true> : relax_dual ? run_p4_order<3, true, false, true, true> : run_p4_order<3, false, false, true, true>)
-               : sh.Wc <= 2 ? (c16 ? run_p4_order<2, false, true, false> : run_p4_order<2, false, false, true>)
-               : c16 ? (relax_dual ? run_p4_order<3, true, true, false> : run_p4_order<3, false, true, false>)
-                     : (relax_dual ? run_p4_order<3, true, false, true> : run_p4_order<3, false, false, true>);
-    const size_t fb_bytes = (size_t)kas_p4_order_lds(sh.n_max, relax_tiles, relax_idl);   // exactly the product's LDS, and a guard behind it
-    std::vector<unsigned char> rl(fb_bytes + 4096);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(rl.data(), 0xCD, fb_bytes);
-      memset(rl.data() + fb_bytes, 0xA5, 4096);
-      RunArgs ra{&a, s, rl.data()};
-      if (kasw::run_block(f, &ra, 2) != 0) return bad("first fit + order (kas_p4_order_kernel)", s);
-      for (size_t i = 0; i < 4096; ++i)
-        if (rl[fb_bytes + i] != 0xA5) return bad("kas_p4_order_kernel: LDS written beyond kas_p4_order_lds()", s);
-      const int64_t* st = a.stats + (int64_t)s * KAS_STATS_PER_SCENARIO;
-      g_last_relax_evals += (long)st[9]; g_last_relax_tiles += (long)st[12]; g_last_relax_slow += (long)st[13];
-    }
-  } else if (relax) {
-    const bool rdual = sh.Wc == 3 && (a.flags & KAS_FLAG_RELAX_DUAL) != 0u;
-    // the instance kas_order_relax_any (kas_hip.hip) picks: 16-bit cells; int32 cells with the broker ids in the LDS
-    // (kas_relax_lds_ids; KAS_EMU_RELAX_GATHER=1 in the environment: the instances that gather them from the node table, which
-    // exist without the sampled verification only — as in the product, which refuses the flag there)
-    const bool verify = (a.flags >> 24) != 0u;
-    const bool idl = !c16 && kas_relax_lds_ids(sh.n_max, sh.any_ctx) && !(getenv("KAS_EMU_RELAX_GATHER") && getenv("KAS_EMU_RELAX_GATHER")[0] == '1');
-    if (verify && !c16 && !idl) {
-      if (errbuf && errlen > 0) snprintf(errbuf, (size_t)errlen, "KAS_PLAN_VERIFY_SAMPLE: not instantiated for the gather instances");
-      return KAS_E_UNSUPPORTED;
-    }
-    run_fn f = m32 ? (relax_quad ? run_order_relax_m32<true, true> : rdual ? run_order_relax_m32<true> : run_order_relax_m32<false>)
-               : c16 ? (verify ? relax_pick<true, true, false>(sh.Wc, rdual, sh.any_ctx) : relax_pick<false, true, false>(sh.Wc, rdual, sh.any_ctx))
-               : idl ? (verify ? relax_pick<true, false, true>(sh.Wc, rdual, sh.any_ctx) : relax_pick<false, false, true>(sh.Wc, rdual, sh.any_ctx))
-                     : relax_pick<false, false, false>(sh.Wc, rdual, sh.any_ctx);
-    g_last_relax_idl = idl ? 1 : 0;
-    // exactly the LDS the product launches the kernel with, and a guard behind it: the hardware drops what a
-    // workgroup writes beyond its allocation and reads zeros there — here that must not pass unnoticed
-    const size_t relax_bytes = (size_t)kas_order_relax_lds(sh.n_max, relax_quad ? 2 : (rdual ? 1 : 0), sh.any_ctx, idl);
-    std::vector<unsigned char> rl(relax_bytes + 4096);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(rl.data(), 0xCD, relax_bytes);
-      memset(rl.data() + relax_bytes, 0xA5, 4096);
-      RunArgs ra{&a, s, rl.data()};
-      if (kasw::run_block(f, &ra, 1) != 0) return bad("order (relaxation)", s);
-      for (size_t i = 0; i < 4096; ++i)
-        if (rl[relax_bytes + i] != 0xA5) return bad("order (relaxation): LDS written beyond kas_order_relax_lds()", s);
-      const int64_t* st = a.stats + (int64_t)s * KAS_STATS_PER_SCENARIO;
-      g_last_relax_evals += (long)st[9]; g_last_relax_tiles += (long)st[12]; g_last_relax_slow += (long)st[13];
-    }
-  } else if (relaxw) {
-    run_fn f = sh.Wc == 4 ? run_order_relax_wide<4> : run_order_relax_wide<5>;
-    const size_t rw_bytes = (size_t)kas_order_relaxw_lds(sh.n_max, sh.Wc);      // exactly the product's LDS, and a guard behind it
-    std::vector<unsigned char> rl(rw_bytes + 4096);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(rl.data(), 0xCD, rw_bytes);
-      memset(rl.data() + rw_bytes, 0xA5, 4096);
-      RunArgs ra{&a, s, rl.data()};
-      if (kasw::run_block(f, &ra, 1) != 0) return bad("order (relaxation, wide lists)", s);
-      for (size_t i = 0; i < 4096; ++i)
-        if (rl[rw_bytes + i] != 0xA5) return bad("order (relaxation, wide lists): LDS written beyond kas_order_relaxw_lds()", s);
-      const int64_t* st = a.stats + (int64_t)s * KAS_STATS_PER_SCENARIO;
-      g_last_relax_evals += (long)st[9]; g_last_relax_tiles += (long)st[12];
-    }
-  } else if (tickets) {
-    if (sh.G > 1 && b->n_scenarios > sh.G) {
-      a.perm = perm.data();                              // the permutation kernel: one workgroup
-      memset(lds.data(), 0xCD, lds.size());
-      RunArgs ra{&a, 0, lds.data()};
-      if (kasw::run_block(run_permutation, &ra, KAS_PERM_WAVES) != 0) return bad("permutation", 0);
-      std::vector<char> seen((size_t)b->n_scenarios, 0);  // it must be a permutation, whatever the order
-      for (int32_t j = 0; j < b->n_scenarios; ++j) {
+    if (by_rank) g_last_handback = hb;
+    // what the tests observe, per family
+    if (sg.k.family == KAS_K_SPREAD_P4)
+      for (int32_t s = 0; s < S; ++s) g_last_spread += sp_flag[(size_t)s] == 0 ? 1 : 0;
+    if (sg.role == KAS_STAGE_SLIM)
+      for (int32_t s = 0; s < S; ++s) {
+        if (sp_flag[(size_t)s] != 0 && sp_flag[(size_t)s] != 1) return bad("slim fill (hand-back flag not written)", s);
+        g_last_slim_fill += sp_flag[(size_t)s] == 0 ? 1 : 0;
+      }
+    if (sg.role == KAS_STAGE_FILL)
+      for (int32_t s = 0; s < S; ++s)
+        g_last_index_rows += (long)a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + 6];   // (the fill's own tally, before an order kernel writes there)
+    if (sg.role == KAS_STAGE_PERMUTATION) {
+      std::vector<char> seen((size_t)S, 0);                  // it must be a permutation, whatever the order
+      for (int32_t j = 0; j < S; ++j) {
         const int32_t v = perm[(size_t)j];
-        if (v < 0 || v >= b->n_scenarios || seen[(size_t)v]) return bad("permutation (not a permutation)", j);
+        if (v < 0 || v >= S || seen[(size_t)v]) return bad("permutation (not a permutation)", j);
         seen[(size_t)v] = 1;
       }
-      int32_t kmax = 0, shift = 0;                       // ... and largest key classes first
-      for (int32_t j = 0; j < b->n_scenarios; ++j) kmax = a.scenario_results[j].moved_replicas > kmax ? a.scenario_results[j].moved_replicas : kmax;
+      int32_t kmax = 0, shift = 0;                           // ... and largest key classes first
+      for (int32_t j = 0; j < S; ++j) kmax = a.scenario_results[j].moved_replicas > kmax ? a.scenario_results[j].moved_replicas : kmax;
       while ((kmax >> shift) >= KAS_PERM_BINS) ++shift;
-      for (int32_t j = 0; j + 1 < b->n_scenarios; ++j)
+      for (int32_t j = 0; j + 1 < S; ++j)
         if ((a.scenario_results[perm[(size_t)j]].moved_replicas >> shift) < (a.scenario_results[perm[(size_t)j + 1]].moved_replicas >> shift))
           return bad("permutation (not descending by key class)", j);
     }
-    const bool pk = sh.packed_ok && !(flags & KAS_FLAG_WIDE_COUNTERS);
-    run_fn f = sh.G == 1 ? (pk ? tickets_for_g<1, true>(sh.Wc) : tickets_for_g<1, false>(sh.Wc))
-             : sh.G == 2 ? (pk ? tickets_for_g<2, true>(sh.Wc) : tickets_for_g<2, false>(sh.Wc))
-                         : (pk ? tickets_for_g<4, true>(sh.Wc) : tickets_for_g<4, false>(sh.Wc));
-    for (int32_t s = 0; s < b->n_scenarios; s += sh.G) {
-      memset(lds.data(), 0xCD, lds.size());
-      RunArgs ra{&a, s, lds.data()};
-      if (kasw::run_block(f, &ra, 3) != 0) return bad("order (tickets)", s);
-    }
-    for (int32_t s = 0; s < b->n_scenarios; ++s) g_last_queue_rows += (long)a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + 14];
-    if (getenv("KAS_EMU_STATS")) {
-      for (int32_t s = 0; s < b->n_scenarios; ++s) {
-        const int64_t* st = a.stats + (int64_t)s * KAS_STATS_PER_SCENARIO;
-        fprintf(stderr, "emu stats s=%d solver_iter=%lld queue_passes=%lld run_rounds=%lld run_rows=%lld blocked=%lld stager_iter=%lld\n", s,
-                (long long)st[9], (long long)st[6], (long long)st[10], (long long)st[14], (long long)st[11], (long long)st[12]);
+    if (sg.role != KAS_STAGE_ORDER) continue;
+    const bool ticket_form = sg.k.family == KAS_K_ORDER_TICKET || sg.k.family == KAS_K_ORDER_WIDE;
+    for (int32_t s = 0; s < S; ++s) {
+      const int64_t* st = a.stats + (int64_t)s * KAS_STATS_PER_SCENARIO;
+      if (ticket_form) g_last_queue_rows += (long)st[14];
+      else if (sg.k.family != KAS_K_ORDER_ROUND) {
+        g_last_relax_evals += (long)st[9]; g_last_relax_tiles += (long)st[12];
+        if (sg.k.family != KAS_K_ORDER_RELAX_WIDE) g_last_relax_slow += (long)st[13];
       }
-    }
-  } else if (wide) {
-    if (sh.wide_checked) a.flags |= KAS_FLAG_WIDE_CHECK;   // as kas_solve_device
-    run_fn f = sh.Wc == 4 ? run_order_wide<4> : run_order_wide<5>;
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(lds.data(), 0xCD, lds.size());
-      RunArgs ra{&a, s, lds.data()};
-      if (kasw::run_block(f, &ra, KAS_ORDER_WIDE_BLOCK / 64) != 0) return bad("order (wide tickets)", s);
-    }
-    for (int32_t s = 0; s < b->n_scenarios; ++s) g_last_queue_rows += (long)a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + 14];
-    if (getenv("KAS_EMU_STATS")) {
-      for (int32_t s = 0; s < b->n_scenarios; ++s) {
-        const int64_t* st = a.stats + (int64_t)s * KAS_STATS_PER_SCENARIO;
-        fprintf(stderr, "emu stats (wide) s=%d solver_iter=%lld bulk_solver_iter=%lld queue_passes=%lld run_rounds=%lld run_rows=%lld blocked=%lld stager_iter=%lld stager_idle=%lld sched_rounds(last block)=%ld\n", s,
-                (long long)st[9], (long long)st[15], (long long)st[6], (long long)st[10], (long long)st[14], (long long)st[11], (long long)st[12],
-                (long long)st[13], kasw::g_last_block_rounds);
+      if (!ticket_form || !getenv("KAS_EMU_STATS")) continue;
+      fprintf(stderr, "emu stats (%s) s=%d solver_iter=%lld bulk_solver_iter=%lld queue_passes=%lld run_rounds=%lld run_rows=%lld blocked=%lld stager_iter=%lld stager_idle=%lld sched_rounds(last block)=%ld\n",
+              name.c_str(), s, (long long)st[9], (long long)st[15], (long long)st[6], (long long)st[10], (long long)st[14], (long long)st[11], (long long)st[12],
+              (long long)st[13], kasw::g_last_block_rounds);
+      if (sg.k.family == KAS_K_ORDER_WIDE)
         fprintf(stderr, "emu diag (wide, -DKAS_WIDE_DIAG) joint_steps=%lld in_hand=%lld hold_hot=%lld wait_hot_only=%lld eligible=%lld | not eligible: many_ahead_elsewhere=%lld one_ahead_not_in_hand=%lld behind_gap=%lld\n",
                 (long long)st[13], (long long)st[3], (long long)st[4], (long long)st[5], (long long)st[7], (long long)st[0], (long long)st[1], (long long)st[2]);
-      }
-    }
-  } else {
-    run_fn f = rounds_for(sh.Wc);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      memset(lds.data(), 0xCD, lds.size());
-      RunArgs ra{&a, s, lds.data()};
-      if (kasw::run_block(f, &ra, 1) != 0) return bad("order (rounds)", s);
-    }
-  }
-  const bool wide_recheck = wide && sh.wide_checked;
-  if (wide_recheck) {
-    // as kas_solve_device: a scenario whose counts outgrew the wide form's fields is filled again ...
-    KasLaunch af = a;
-    af.flags = (af.flags | KAS_FLAG_ONLY_FLAGGED) & ~(KAS_FLAG_WIDE_CHECK | KAS_FLAG_SPLIT_P4);
-    af.sp_flag = ord_flag.data();
-    {
-      const int32_t failed = emu_launch_fill(fill, af, sh.NW, lds, b->n_scenarios, false);
-      if (failed >= 0) return bad("fill (flagged by the wide form; workgroup)", failed);
-    }
-    a.flags &= ~KAS_FLAG_WIDE_CHECK;
-  }
-  if ((sh.any_ctx && (tickets || wide || relax)) || wide_recheck) {
-    // as kas_solve_device: the round form behind a ticket form, taking only what that one flagged
-    a.flags |= KAS_FLAG_ORDER_FLAGGED;
-    a.perm = nullptr;
-    run_fn f = rounds_for(sh.Wc);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      g_last_flagged += ord_flag[(size_t)s] != 0 ? 1 : 0;
-      memset(lds.data(), 0xCD, lds.size());
-      RunArgs ra{&a, s, lds.data()};
-      if (kasw::run_block(f, &ra, 1) != 0) return bad("order (rounds, flagged)", s);
     }
   }
   return KAS_E_OK;
+}
+
+// kas_plan_describe for a batch + flag word + cell width, without running anything: the text rendered from the launch the emulator
+// would walk (a context whose self-test passed, a plan that has not solved yet).  Returns kas_shape_batch's / the plan's refusal.
+extern "C" __attribute__((visibility("default")))
+int kas_emu_describe(const kas_batch_desc* b, unsigned flags, int cells16, char* buf, int n) {
+  KasShape sh;
+  std::string err;
+  int rc = kas_shape_batch(b, &sh, &err, (int)((flags >> 8) & 0xfu), (int)((flags >> 12) & 0xfu));
+  if (rc == KAS_E_OK && cells16 && !kas_cells16_ok(sh, 1, KAS_BUILT_ALL)) { rc = KAS_E_UNSUPPORTED; err = "16-bit cells: lists up to 3 wide, relaxation or round form"; }
+  if (rc == KAS_E_OK)
+    if (const char* why = kas_flags_refusal(sh, cells16 != 0, flags, false)) { rc = KAS_E_UNSUPPORTED; err = why; }
+  KasLaunchIn in;
+  if (rc == KAS_E_OK) {
+    kas_launch_in_shape(&in, &sh);
+    in.n_scenarios = b->n_scenarios; in.single_topic = kas_batch_single_topic(b) ? 1 : 0; in.cells16 = cells16 ? 1 : 0;
+    kas_launch_in_user_flags(&in, flags);
+    err = kas_describe_launch(kas_resolve_launch(in));
+  }
+  if (buf && n > 0) { strncpy(buf, err.c_str(), (size_t)n - 1); buf[n - 1] = 0; }
+  return rc;
+}
+
+// Is the launch the resolver returns for a batch + flag word + cell width launchable?  Every stage's LDS within 160 KiB, exactly one
+// order stage, every kernel identity an instance of the emulator's mapping, and every (identity, LDS) among those the enumeration
+// behind kas_plan_set_kernels covers for the plan as kas_plan_create leaves it.  0 and the describe text; 1 and what is wrong; a
+// negative KAS_E_* and the refusal when no plan takes the batch / the flags.
+extern "C" __attribute__((visibility("default")))
+int kas_emu_launch_check(const kas_batch_desc* b, unsigned flags, int cells16, char* buf, int n) {
+  const int rc = kas_emu_describe(b, flags, cells16, buf, n);
+  if (rc != KAS_E_OK) return rc;
+  KasShape sh;                                               // the plan as created (its shape's own waves and groups) ...
+  std::string err;
+  if (kas_shape_batch(b, &sh, &err, 0, 0) != KAS_E_OK) return 1;
+  KasLaunchIn created, in;
+  kas_launch_in_shape(&created, &sh);
+  created.n_scenarios = b->n_scenarios; created.single_topic = kas_batch_single_topic(b) ? 1 : 0; created.cells16 = cells16 ? 1 : 0;
+  in = created;
+  KasShape asked = sh;                                       // ... and as kas_plan_set_flags(flags) leaves it
+  if (kas_shape_batch(b, &asked, &err, (int)((flags >> 8) & 0xfu), (int)((flags >> 12) & 0xfu)) != KAS_E_OK) return 1;
+  kas_launch_in_shape(&in, &asked);
+  kas_launch_in_user_flags(&in, flags);
+  created.NW = in.NW; created.G = in.G; created.fused = in.fused;   // (kas_plan_set_flags moves these before it opts the kernels in)
+  created.lds_total = in.lds_total; created.lds_fused_total = in.lds_fused_total;
+  const KasResolvedLaunch L = kas_resolve_launch(in);
+  std::string bad;
+  int orders = 0;
+  for (int32_t i = 0; i < L.n_stages && bad.empty(); ++i) {
+    const KasStage& sg = L.stages[i];
+    orders += sg.role == KAS_STAGE_ORDER ? 1 : 0;
+    bool opted = sg.lds == 0u;
+    created.shape = in.shape;
+    kas_enumerate_launches(created, [&](const KasStage& e) { opted = opted || (e.k == sg.k && e.lds >= sg.lds); });
+    if (sg.lds > (uint32_t)KAS_LDS_LIMIT) bad = kas_kernel_name(sg.k) + ": LDS beyond 160 KiB";
+    else if (!emu_kernel_for(sg.k)) bad = kas_kernel_name(sg.k) + ": not an instance of the emulator";
+    else if (!opted) bad = kas_kernel_name(sg.k) + ": not among the launches kas_plan_set_kernels enumerates";
+  }
+  if (bad.empty() && orders != 1) bad = "not exactly one order stage";
+  if (bad.empty()) return 0;
+  if (buf && n > 0) { strncpy(buf, bad.c_str(), (size_t)n - 1); buf[n - 1] = 0; }
+  return 1;
 }
 
 // The product's planning decision for a batch shape, without running anything (plan-math tests):

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import glob
 import os
 import shlex
 import subprocess
@@ -31,10 +32,9 @@ TEST_VARIANTS = {
 
 
 def _deps():
-    return [os.path.join(EMU_DIR, "emu_driver.cpp"), os.path.join(EMU_DIR, "kas_wave.h"),
-            os.path.join(CSRC, "kas_solver_body.h"), os.path.join(CSRC, "kas_order_wide.h"),
-            os.path.join(CSRC, "kas_order_relax.h"),
-            os.path.join(CSRC, "kas_plan_math.h"), os.path.join(ROOT, "include", "kas_abi.h")]
+    """The driver first (the file that is compiled), then everything it may include: every header of the kernel sources."""
+    return [os.path.join(EMU_DIR, "emu_driver.cpp"), os.path.join(EMU_DIR, "kas_wave.h"), os.path.join(ROOT, "include", "kas_abi.h"),
+            *sorted(glob.glob(os.path.join(CSRC, "*.h")))]
 
 
 def _stale(so: str) -> bool:
@@ -316,6 +316,30 @@ def plan_shape(fb: FlatBatch):
     rc = L.kas_emu_shape(C.byref(bd), out, err, 512)
     names = ("tickets_ok", "wide_ok", "round_fits", "G", "NW", "with_x", "packed_ok", "fused_ok", "wide_checked", "relax_ok")
     return rc, dict(zip(names, list(out))), err.value.decode()
+
+
+def describe(fb: FlatBatch, flags: int = 0, cells16: bool = False):
+    """kas_plan_describe's text for a batch shape + plan flags + cell width (the product's launch resolver and renderer, nothing is
+    run; a context whose LDS lane-order self-test passed): (return code, text — the refusal when the code is not 0)."""
+    L = lib()
+    L.kas_emu_describe.restype = C.c_int
+    L.kas_emu_describe.argtypes = [C.POINTER(abi.BatchDesc), C.c_uint, C.c_int, C.c_char_p, C.c_int]
+    bd = batch_desc(fb)
+    buf = C.create_string_buffer(1024)
+    rc = L.kas_emu_describe(C.byref(bd), flags, 1 if cells16 else 0, buf, 1024)
+    return rc, buf.value.decode()
+
+
+def launch_check(fb: FlatBatch, flags: int = 0, cells16: bool = False):
+    """Is the resolved launch of a batch shape + plan flags + cell width launchable (LDS, one order stage, every kernel an instance,
+    every kernel among those kas_plan_set_kernels enumerates)?  (0, describe text), (1, what is wrong) or (KAS_E_*, the refusal)."""
+    L = lib()
+    L.kas_emu_launch_check.restype = C.c_int
+    L.kas_emu_launch_check.argtypes = [C.POINTER(abi.BatchDesc), C.c_uint, C.c_int, C.c_char_p, C.c_int]
+    bd = batch_desc(fb)
+    buf = C.create_string_buffer(1024)
+    rc = L.kas_emu_launch_check(C.byref(bd), flags, 1 if cells16 else 0, buf, 1024)
+    return rc, buf.value.decode()
 
 
 def last_flagged() -> int:

@@ -706,7 +706,7 @@ def test_slim_fill_kernel_and_the_scenarios_it_hands_back():
 @pytest.mark.gpu
 def test_launch_behind_the_slim_kernel_grows_with_what_was_handed_back():
     """The kas_fill_kernel launch behind the slim kernel deals the flagged scenarios to its workgroups by RANK among them and leaves
-    their number in a word of pinned host memory; the plan's next solve sizes that launch by it (kas_plan_back_grid: one workgroup
+    their number in a word of pinned host memory; the plan's next solve sizes that launch by it (kas_back_grid: one workgroup
     per handed-back scenario and a quarter more, in steps of 64, at most the fill's own grid).  600 scenarios of which two in three
     start from rows that are not rack-diverse (400 handed back): the first solve launches 256 workgroups behind the slim kernel, the
     second and third 512 — lists and records equal to the oracle's every time; a plan rebuilt for another batch starts small again."""
