@@ -27,6 +27,7 @@
 #include "kas_plan_math.h"
 #include "kas_solver_body.h"
 #include "kas_launch_plan.h"   // which kernels a solve launches: the resolver the emulator shares
+#include "kas_host_call.h"     // what a host call does: ranges, cell width, buffer sizes, the plan cache's choice
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
 
 // ---------------------------------------------------------------------------------------------
@@ -383,27 +384,19 @@ struct KasCachedPlan {
   uint64_t last_use = 0;
   uint64_t call = 0;                    // host call that last used the entry (its ranges must not evict each other)
 };
-#define KAS_HOST_PLAN_CACHE 16
-#ifndef KAS_HOST_STREAMS
-#define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
-#endif
 struct kas_ctx {
   int device;
   hipStream_t stream;
   hipStream_t hstream[KAS_HOST_STREAMS];   // the host path's chains (upload -> solve -> download of a scenario range)
-  hipEvent_t hevent;                       // "shared pools are up" of the current host call
   // a call cut into scenario ranges: every upload on one stream, every download on another (copies of one direction
   // queue behind each other anyway, and the two directions only run at the same time when no stream carries both),
   // the solves on hstream[]; events hand a range from upload to solve to download
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf h_cur, h_out, h_aux, h_ctx, h_tr, h_sr;
-  KasBuf h_cur16, h_out16;              // the 16-bit cells of kas_solve_host16 as they travel (widened / narrowed on the device)
+  KasBuf hbuf[KAS_HB_COUNT];            // device pools, record staging, impact records (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
-  KasBuf h_tr_pin, h_sr_pin;            // pinned HOST staging of the result records (see kas_solve_host_locked)
-  KasBuf h_imp_nodes, h_imp_scen;       // the impact records of kas_solve_host_impact / 16 on the device
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
   uint64_t use_clock = 0;
   uint64_t host_calls = 0, host_plan_hits = 0, host_allocs = 0;
@@ -587,7 +580,7 @@ int kas_ctx_create(int device, kas_ctx** out_ctx) {
                                     ", the kernels are built for gfx950 only");
   kas_ctx* c = new kas_ctx();
   c->device = device;
-  c->stream = nullptr; c->hevent = nullptr; c->hup = nullptr; c->hdown = nullptr;
+  c->stream = nullptr; c->hup = nullptr; c->hdown = nullptr;
   for (hipStream_t& h : c->hstream) h = nullptr;
   for (hipEvent_t& ev : c->hev_up) ev = nullptr;
   for (hipEvent_t& ev : c->hev_done) ev = nullptr;
@@ -596,7 +589,6 @@ int kas_ctx_create(int device, kas_ctx** out_ctx) {
   // all eight with itself, each took one of the process's GPU_MAX_HW_QUEUES hardware queues, and the streams of a caller
   // that never makes a host call — bench.py's eight slots — were left to share what remained: the kernel trace showed
   // two pairs of slots on one queue each, their solves serialised.  hup / hdown: kas_host_copy_streams.)
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->hevent, hipEventDisableTiming);
   for (hipEvent_t& ev : c->hev_up) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   for (hipEvent_t& ev : c->hev_done) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   if (e != hipSuccess) {
@@ -617,10 +609,12 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (KasBuf* b : {&ctx->h_cur, &ctx->h_out, &ctx->h_aux, &ctx->h_ctx, &ctx->h_tr, &ctx->h_sr, &ctx->h_cur16, &ctx->h_out16}) kas_buf_free(b);
-  for (KasBuf* b : {&ctx->h_tr_pin, &ctx->h_sr_pin}) { if (b->p) (void)hipHostFree(b->p); b->p = nullptr; b->cap = 0; }
-  for (KasBuf* b : {&ctx->h_imp_nodes, &ctx->h_imp_scen}) kas_buf_free(b);
-  if (ctx->hevent) (void)hipEventDestroy(ctx->hevent);
+  for (int i = 0; i < KAS_HB_COUNT; ++i) {
+    KasBuf* b = &ctx->hbuf[i];
+    if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
+    if (b->p) (void)hipHostFree(b->p);
+    b->p = nullptr; b->cap = 0;
+  }
   for (hipEvent_t ev : ctx->hev_up) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : ctx->hev_done) if (ev) (void)hipEventDestroy(ev);
   if (ctx->hup) (void)hipStreamDestroy(ctx->hup);
@@ -835,44 +829,13 @@ int kas_plan_create(kas_ctx* ctx, const kas_batch_desc* batch, kas_plan** out_pl
   return kas_plan_new(ctx, batch, nullptr, out_plan);
 }
 
-// 16-bit cells are node indices: the node table the kernels see gives node i the id i (`ids` holds it, `out` = *b with it).
-// `ids` may be a table an earlier call filled (the context's): it is rewritten only where the scenarios' node ranges
-// differ from the ones it was filled for (`stamp`: a hash of them) — a what-if caller's 1000 x 1000 table stays.
-static int kas_ident_batch(const kas_batch_desc* b, std::vector<int32_t>* ids, kas_batch_desc* out, uint64_t* stamp = nullptr) {
-  if (b->n_scenarios < 0 || b->node_pool_len < 0 || (b->n_scenarios > 0 && !b->scenarios))
-    return set_error(KAS_E_INVALID_ARG, "negative size / scenarios == NULL");
-  uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)b->node_pool_len;
-  for (int32_t s = 0; s < b->n_scenarios; ++s) {
-    const kas_scenario_desc& sd = b->scenarios[s];
-    if (sd.n_nodes < 0 || sd.node_off < 0 || sd.node_off + sd.n_nodes > b->node_pool_len)
-      return set_error(KAS_E_INVALID_ARG, "scenario " + std::to_string(s) + ": node table outside the node pool");
-    // (a cell's bit 15 says "no holder" inside the kernels, mid_to_index: an index is below 32,768 — KAS_N_LIMIT, the
-    // limit of every plan; 0xFFFF is the only cell value above it that means anything)
-    if (sd.n_nodes > KAS_N_LIMIT)
-      return set_error(KAS_E_UNSUPPORTED, "scenario " + std::to_string(s) + ": more than 32,767 brokers do not fit 16-bit cells");
-    h = (h ^ (((uint64_t)(uint32_t)sd.node_off << 32) | (uint32_t)sd.n_nodes)) * 0x100000001b3ull;
-    h ^= h >> 29;
-  }
-  h |= 1ull;
-  if (!(stamp && *stamp == h && ids->size() == (size_t)b->node_pool_len)) {
-    ids->assign((size_t)b->node_pool_len, 0);
-    for (int32_t s = 0; s < b->n_scenarios; ++s) {
-      const kas_scenario_desc& sd = b->scenarios[s];
-      for (int32_t i = 0; i < sd.n_nodes; ++i) (*ids)[(size_t)(sd.node_off + i)] = i;
-    }
-    if (stamp) *stamp = h;
-  }
-  *out = *b;
-  out->node_id = ids->data();
-  return KAS_E_OK;
-}
-
 int kas_plan_create16(kas_ctx* ctx, const kas_batch_desc* batch, kas_plan** out_plan) {
   if (!ctx || !batch || !out_plan) return set_error(KAS_E_INVALID_ARG, "NULL argument");
   std::vector<int32_t> ids;
   kas_batch_desc ib;
-  const int rc = kas_ident_batch(batch, &ids, &ib);
-  if (rc != KAS_E_OK) return rc;
+  std::string err;
+  const int rc = kas_ident_batch(batch, &ids, &ib, nullptr, &err);
+  if (rc != KAS_E_OK) return set_error(rc, err);
   return kas_plan_new(ctx, &ib, nullptr, out_plan, 1);
 }
 
@@ -1181,138 +1144,38 @@ int kas_host_alloc(int64_t bytes, void** out_ptr) {
 
 void kas_host_free(void* ptr) { if (ptr) (void)hipHostFree(ptr); }
 
-void kas_shard_range(int64_t total, int32_t rank, int32_t world, int64_t* lo, int64_t* hi) {
-  if (world < 1) world = 1;
-  if (rank < 0) rank = 0;
-  if (rank >= world) rank = world - 1;
-  if (total < 0) total = 0;
-  const int64_t base = total / world, rem = total % world;
-  const int64_t l = (int64_t)rank * base + (rank < rem ? rank : rem);
-  if (lo) *lo = l;
-  if (hi) *hi = l + base + (rank < rem ? 1 : 0);
-}
+void kas_shard_range(int64_t total, int32_t rank, int32_t world, int64_t* lo, int64_t* hi) { kas_range_of(total, rank, world, lo, hi); }
 
 int kas_batch_slice(const kas_batch_desc* b, int64_t lo, int64_t hi, kas_scenario_desc* scratch, kas_batch_desc* out,
                     const kas_tables* tables, kas_tables* tables_out) {
-  if (!b || !out || lo < 0 || hi < lo || hi > b->n_scenarios || (hi > lo && (!scratch || !b->scenarios)))
-    return set_error(KAS_E_INVALID_ARG, "kas_batch_slice: bad range / NULL argument");
-  int64_t tlo = INT64_MAX, thi = 0, nlo = INT64_MAX, nhi = 0;
-  for (int64_t i = lo; i < hi; ++i) {
-    const kas_scenario_desc& sd = b->scenarios[i];
-    if (sd.topic_begin < 0 || sd.topic_count < 0 || (int64_t)sd.topic_begin + sd.topic_count > b->n_topics || sd.n_nodes < 0 ||
-        sd.node_off < 0 || sd.node_off + sd.n_nodes > b->node_pool_len)
-      return set_error(KAS_E_INVALID_ARG, "kas_batch_slice: scenario " + std::to_string(i) + " refers outside the batch");
-    if (sd.topic_count > 0) {
-      if (sd.topic_begin < tlo) tlo = sd.topic_begin;
-      if ((int64_t)sd.topic_begin + sd.topic_count > thi) thi = (int64_t)sd.topic_begin + sd.topic_count;
-    }
-    if (sd.n_nodes > 0) {
-      if (sd.node_off < nlo) nlo = sd.node_off;
-      if (sd.node_off + sd.n_nodes > nhi) nhi = sd.node_off + sd.n_nodes;
-    }
-  }
-  if (tlo > thi) tlo = thi = 0;
-  if (nlo > nhi) nlo = nhi = 0;
-  for (int64_t i = lo; i < hi; ++i) {
-    kas_scenario_desc sd = b->scenarios[i];
-    sd.topic_begin = sd.topic_count > 0 ? (int32_t)(sd.topic_begin - tlo) : 0;
-    sd.node_off = sd.n_nodes > 0 ? sd.node_off - nlo : 0;
-    scratch[i - lo] = sd;
-  }
-  out->n_scenarios = (int32_t)(hi - lo);
-  out->n_topics = (int32_t)(thi - tlo);
-  out->scenarios = scratch;
-  out->topics = b->topics ? b->topics + tlo : nullptr;
-  out->node_id = b->node_id ? b->node_id + nlo : nullptr;
-  out->node_rack = b->node_rack ? b->node_rack + nlo : nullptr;
-  out->node_pool_len = nhi - nlo;
-  if (tables && tables_out) {
-    *tables_out = *tables;
-    tables_out->topic_results = tables->topic_results ? tables->topic_results + tlo : nullptr;
-    tables_out->scenario_results = tables->scenario_results ? tables->scenario_results + lo : nullptr;
-  }
-  return KAS_E_OK;
+  std::string err;
+  const int rc = kas_slice_batch(b, lo, hi, scratch, out, tables, tables_out, &err);
+  return rc == KAS_E_OK ? rc : set_error(rc, err);
 }
 
-// word-at-a-time hash of the descriptor bytes (a what-if call hashes megabytes of node tables)
-// (four independent lanes over 32-byte blocks: one dependent multiply chain ran at ~4 GB/s and made the 8 MB of
-// descriptors and node tables of a 1000-variant what-if call cost 2 of its 5 ms)
-static uint64_t kas_hash64(uint64_t h, const void* data, size_t n) {
-  const unsigned char* p = (const unsigned char*)data;
-  const uint64_t M = 0x9E3779B97F4A7C15ull;
-  uint64_t a = h, b = h ^ 0x243F6A8885A308D3ull, c = h ^ 0x13198A2E03707344ull, d = h ^ 0xA4093822299F31D0ull;
-  size_t i = 0;
-  for (; i + 32 <= n; i += 32) {
-    uint64_t w[4];
-    memcpy(w, p + i, 32);
-    a = (a ^ w[0]) * M; a ^= a >> 29;
-    b = (b ^ w[1]) * M; b ^= b >> 29;
-    c = (c ^ w[2]) * M; c ^= c >> 29;
-    d = (d ^ w[3]) * M; d ^= d >> 29;
-  }
-  h = a;
-  h = (h ^ b) * M; h ^= h >> 29;
-  h = (h ^ c) * M; h ^= h >> 29;
-  h = (h ^ d) * M; h ^= h >> 29;
-  for (; i + 8 <= n; i += 8) {
-    uint64_t w;
-    memcpy(&w, p + i, 8);
-    h = (h ^ w) * M;
-    h ^= h >> 29;
-  }
-  for (; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
-  return h;
-}
-
-// The plan of this batch from the context's cache: the one whose descriptors and node tables are the
-// same byte for byte, else the least recently used entry rebuilt in place (or a new one into a free entry).
+// The plan of this batch from the context's cache (kas_cache_choose): the one whose descriptors and node tables are the
+// same byte for byte, else the victim rebuilt in place (or a new one into a free entry).
 static int kas_host_plan(kas_ctx* ctx, const kas_batch_desc* b, kas_plan** out_plan, int cells16 = 0) {
   *out_plan = nullptr;
-  if (b->n_scenarios < 0 || b->n_topics < 0 || b->node_pool_len < 0 ||
-      (b->n_scenarios > 0 && !b->scenarios) || (b->n_topics > 0 && !b->topics) ||
-      (b->node_pool_len > 0 && (!b->node_id || !b->node_rack)))
-    return set_error(KAS_E_INVALID_ARG, "null/negative batch");
-  const size_t sb = sizeof(kas_scenario_desc) * (size_t)b->n_scenarios, tb = sizeof(kas_topic_desc) * (size_t)b->n_topics,
-               nb = sizeof(int32_t) * (size_t)b->node_pool_len;
-  // what identifies the batch: (S, T, node pool length), scenario and topic descriptors, node tables — hashed and
-  // compared where they lie; a copy is made only when a plan is built for them
-  int64_t hdr[2] = {((int64_t)b->n_scenarios << 32) | (uint32_t)b->n_topics, b->node_pool_len | ((int64_t)(cells16 ? 1 : 0) << 62)};   // (a plan for 16-bit cells is another plan)
-  const void* seg[5] = {hdr, b->scenarios, b->topics, b->node_id, b->node_rack};
-  const size_t seg_bytes[5] = {16, sb, tb, nb, nb};
-  const size_t desc_bytes = 16 + sb + tb + 2 * nb;
-  uint64_t key = 0xcbf29ce484222325ull;
-  for (int i = 0; i < 5; ++i) if (seg_bytes[i]) key = kas_hash64(key, seg[i], seg_bytes[i]);
-  // (S, T) + topic descriptors + the cell width: a plan for the other cell width is never the one rebuilt in place
-  const uint64_t sig = kas_hash64(0x84222325cbf29ce4ull, hdr, 8) ^ kas_hash64(0, b->topics, tb) ^ (cells16 ? 0x5bd1e995c16c16c1ull : 0ull);
-  auto same_bytes = [&](const std::vector<unsigned char>& have) {
-    if (have.size() != desc_bytes) return false;
-    size_t off = 0;
-    for (int i = 0; i < 5; ++i) {
-      if (seg_bytes[i] && memcmp(have.data() + off, seg[i], seg_bytes[i]) != 0) return false;
-      off += seg_bytes[i];
-    }
-    return true;
-  };
-  ctx->use_clock += 1;
-  // hit: the same bytes.  Miss: rebuild the least recently used plan of the same signature in place (a
-  // what-if caller: same snapshot, other broker sets — every buffer is already large enough), else fill a
-  // free entry, else rebuild the least recently used plan of any shape.  Entries this call already uses
-  // (the other scenario ranges of a split call) are never victims.
-  KasCachedPlan *same = nullptr, *empty = nullptr, *lru = nullptr;
-  for (KasCachedPlan& c : ctx->plans) {
-    if (c.plan && c.key == key && same_bytes(c.desc)) {
-      c.last_use = ctx->use_clock; c.call = ctx->host_calls;
-      ctx->host_plan_hits += 1;
-      *out_plan = c.plan;
-      return KAS_E_OK;                                         // (its flags are the ones set below when it was built)
-    }
-    if (!c.plan) { if (!empty) empty = &c; continue; }
-    if (c.call == ctx->host_calls) continue;
-    if (c.sig == sig && (!same || c.last_use < same->last_use)) same = &c;
-    if (!lru || c.last_use < lru->last_use) lru = &c;
+  if (!kas_batch_ident_ok(b)) return set_error(KAS_E_INVALID_ARG, "null/negative batch");
+  const KasBatchIdent id(b, cells16);
+  KasCacheEntry entries[KAS_HOST_PLAN_CACHE];
+  for (int i = 0; i < KAS_HOST_PLAN_CACHE; ++i) {
+    const KasCachedPlan& c = ctx->plans[i];
+    entries[i] = KasCacheEntry{c.plan != nullptr, c.key, c.sig, c.last_use, c.call};
   }
-  KasCachedPlan* victim = same ? same : (empty ? empty : lru);
-  if (!victim) return set_error(KAS_E_NOMEM, "host-path plan cache exhausted by one call");
+  ctx->use_clock += 1;
+  const KasCacheChoice choice = kas_cache_choose(entries, KAS_HOST_PLAN_CACHE, id.key, id.sig, ctx->host_calls);
+  for (int i = 0; i < KAS_HOST_PLAN_CACHE; ++i) {
+    KasCachedPlan& c = ctx->plans[i];
+    if (!((choice.hits >> i) & 1u) || !id.same_bytes(c.desc)) continue;
+    c.last_use = ctx->use_clock; c.call = ctx->host_calls;
+    ctx->host_plan_hits += 1;
+    *out_plan = c.plan;
+    return KAS_E_OK;                                           // (its flags are the ones set below when it was built)
+  }
+  if (choice.victim < 0) return set_error(KAS_E_NOMEM, "host-path plan cache exhausted by one call");
+  KasCachedPlan* victim = &ctx->plans[choice.victim];
   int rc;
   if (victim->plan) {
     victim->plan->cells16 = cells16;
@@ -1324,12 +1187,8 @@ static int kas_host_plan(kas_ctx* ctx, const kas_batch_desc* b, kas_plan** out_p
     if (rc != KAS_E_OK) return rc;
     victim->plan = plan;
   }
-  victim->desc.resize(desc_bytes);
-  {
-    size_t off = 0;
-    for (int i = 0; i < 5; ++i) { if (seg_bytes[i]) memcpy(victim->desc.data() + off, seg[i], seg_bytes[i]); off += seg_bytes[i]; }
-  }
-  victim->key = key; victim->sig = sig; victim->last_use = ctx->use_clock; victim->call = ctx->host_calls;
+  id.copy_to(&victim->desc);
+  victim->key = id.key; victim->sig = id.sig; victim->last_use = ctx->use_clock; victim->call = ctx->host_calls;
   // a host call blocks until its results are back: its solve has the GPU to itself (or shares it with the few other
   // scenario ranges of the same call), so the relaxation form takes double tiles whatever the batch size — the order
   // kernel of a 1000-variant what-if call 2.0 -> 1.7 ms
@@ -1341,34 +1200,27 @@ static int kas_host_plan(kas_ctx* ctx, const kas_batch_desc* b, kas_plan** out_p
   return KAS_E_OK;
 }
 
-// grow-only device buffer of the host path
-static int kas_host_buf(kas_ctx* ctx, KasBuf* b, size_t bytes) {
+// grow-only buffer of the host path (KasHostBuf): device memory, or pinned host memory for the record staging
+static int kas_host_reserve(kas_ctx* ctx, int id, size_t bytes) {
+  KasBuf* b = &ctx->hbuf[id];
   if (bytes <= b->cap) return KAS_E_OK;
+  const size_t want = bytes + bytes / 4 + 256;
   // (every host call drains its streams before it returns: nothing is in flight on the old buffer)
-  return kas_buf_reserve(b, bytes + bytes / 4 + 256, &ctx->host_allocs, "host-path buffer");
-}
-
-// grow-only pinned host buffer of the host path
-static int kas_host_pinned(kas_ctx* ctx, KasBuf* b, size_t bytes) {
-  if (bytes <= b->cap) return KAS_E_OK;
+  if (!kas_host_buf_pinned(id)) return kas_buf_reserve(b, want, &ctx->host_allocs, "host-path buffer");
   if (b->p) (void)hipHostFree(b->p);
   b->p = nullptr; b->cap = 0;
-  const size_t want = bytes + bytes / 4 + 256;
   if (hipHostMalloc(&b->p, want, hipHostMallocDefault) != hipSuccess) { b->p = nullptr; return set_error(KAS_E_NOMEM, "hipHostMalloc failed (host-path record staging)"); }
   b->cap = want;
   ctx->host_allocs += 1;
   return KAS_E_OK;
 }
 
-// one scenario range of a host call: its slice of the batch, its plan, what it moves
-struct KasChain {
-  int64_t lo = 0, hi = 0;                       // scenarios
-  int64_t tlo = 0, thi = 0;                     // topics (absolute indices)
-  std::vector<kas_scenario_desc> scen;          // rebased descriptors of the slice
-  kas_batch_desc bd;
-  kas_plan* plan = nullptr;
-  int64_t cur_lo = 0, cur_hi = 0, out_lo = 0, out_hi = 0;
-};
+// the host path's solve streams: the first n of hstream[] exist after this
+static int kas_host_solve_streams(kas_ctx* c, int n) {
+  for (int i = 0; i < n && i < KAS_HOST_STREAMS; ++i)
+    if (!c->hstream[i]) KAS_HIP_TRY(hipStreamCreateWithFlags(&c->hstream[i], hipStreamNonBlocking));
+  return KAS_E_OK;
+}
 
 // The two copy streams of a host call that is cut into scenario ranges, made on first use.  They get hardware queues
 // of their own: the runtime maps ordinary streams onto a pool of GPU_MAX_HW_QUEUES (default 4) queues, and an upload
@@ -1377,13 +1229,6 @@ struct KasChain {
 // and the mask here is every CU.  Only these two: a process that holds dozens of queues is time-sliced by the
 // hardware scheduler (every stream of the host path on a queue of its own, two contexts alive: configs[4]'s 35 ms
 // chain kernel ran 13 % slower, configs[3]'s share fell from 590k to 341k scenarios/s).
-// the host path's solve streams: the first n of hstream[] exist after this
-static int kas_host_solve_streams(kas_ctx* c, int n) {
-  for (int i = 0; i < n && i < KAS_HOST_STREAMS; ++i)
-    if (!c->hstream[i]) KAS_HIP_TRY(hipStreamCreateWithFlags(&c->hstream[i], hipStreamNonBlocking));
-  return KAS_E_OK;
-}
-
 static int kas_host_copy_streams(kas_ctx* c) {
   if (c->hup && c->hdown) return KAS_E_OK;
   hipDeviceProp_t prop;
@@ -1452,160 +1297,76 @@ static unsigned kas_cells_grid(int64_t n) {
 }
 
 
-#define KAS_HOST_SPLIT_MIN_BYTES (48ll << 20)   // tables smaller than this are moved and solved as one range
-// Scenario ranges of one call.  A range's solve is a chain of ~2.5-3 ms however few scenarios it holds (one workgroup per
-// scenario walks its 100,000 rows), so a call lasts upload + that chain + the last range's download, and more ranges only
-// shorten the last download — while the runtime maps the ranges' solve streams onto GPU_MAX_HW_QUEUES (default 4) hardware
-// queues shared with everything else, where ranges on one queue run one after the other (a kernel + copy trace of eight
-// ranges: the last one solved alone, 3.4 ms after the others).  240 scenarios x 100,000 x 3 cells, 16-bit cells, pinned:
-// 2 ranges 6.4 ms, 3: 6.0, 4: 7.1 (5.9 with eight hardware queues), 8: 7.8; int32 cells 9.3-10.0 ms whatever the count
-// (scripts/e2e_host_path.py; KAS_HOST_RANGES overrides for such measurements).
-#define KAS_HOST_SPLIT_MAX 3
+// a cur / out pool of a host call as it travels: device and host base (both take the descriptors' absolute cell offsets), bytes a cell
+struct KasCellPool {
+  char *dev, *host;
+  size_t cell;
+  char* d(int64_t at) const { return dev + (int64_t)cell * at; }
+  char* h(int64_t at) const { return host + (int64_t)cell * at; }
+};
 
+// One host call: plan it (kas_host_call.h: validation, cell width, offsets, scenario ranges, buffer sizes), reserve, fetch the
+// ranges' plans, enqueue, drain, copy the records.
 static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select,
                                  int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
-  const bool all_rows = n_select < 0;
-  if (!all_rows && n_select > 0 && !select) return set_error(KAS_E_INVALID_ARG, "select == NULL");
-  // 16-bit cells are node indices: the node table the kernels see gives node i the id i (h->cur / h->out are unused)
-  kas_batch_desc ident_batch;
-  if (c16) {
-    const int irc = kas_ident_batch(batch, &ctx->ident_ids, &ident_batch, &ctx->ident_stamp);
-    if (irc != KAS_E_OK) return irc;
-    batch = &ident_batch;
-  }
-  const size_t cell = c16 ? sizeof(uint16_t) : sizeof(int32_t);     // bytes of a cur / out cell as it travels
-  const bool have_cur = c16 ? c16->cur != nullptr : h->cur != nullptr;
-  const bool have_out = c16 ? c16->out != nullptr : h->out != nullptr;
-  // the whole batch: validation and the extents of every pool
-  KasShape full;
+  KasHostCallIn in;
+  in.batch = batch;
+  in.cur_len = h->cur_len; in.out_len = h->out_len; in.aux_len = h->aux_len; in.ctx_len = h->ctx_len;
+  in.have_cur = c16 ? c16->cur != nullptr : h->cur != nullptr;
+  in.have_out = c16 ? c16->out != nullptr : h->out != nullptr;
+  in.have_aux = h->aux != nullptr; in.have_ctx = h->ctx != nullptr;
+  in.have_topic_results = h->topic_results != nullptr; in.have_scenario_results = h->scenario_results != nullptr;
+  in.select = select; in.n_select = n_select;
+  in.cells16 = c16 != nullptr; in.ident_ids = &ctx->ident_ids; in.ident_stamp = &ctx->ident_stamp;
+  in.impact = himp != nullptr; in.have_imp_nodes = himp && himp->nodes; in.have_imp_scenarios = himp && himp->scenarios;
+  in.lane_order_ok = ctx->lds_lane_order_ok;
+  for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
+  if (const char* e = getenv("KAS_HOST_RANGES")) in.ranges_override = atoi(e);
+  KasHostCall hc;
+  int rc;
   {
     std::string err;
-    const int rc = kas_shape_batch(batch, &full, &err, 0, 0);
-    if (rc != KAS_E_OK) return set_error(rc, err);
+    if ((rc = kas_plan_host_call(in, &hc, &err)) != KAS_E_OK) return set_error(rc, err);
   }
-  const int64_t S = batch->n_scenarios, T = batch->n_topics;
-  // A 16-bit call is solved on its 16-bit cells where the kernels with that I/O take the batch (what kas_plan_create16
-  // accepts, asked HERE on the shape: a batch the 16-bit kernels refuse never reaches the plan cache with the 16-bit bit
-  // set); any other batch is widened before and narrowed behind an int32 solve.
-  bool native16 = c16 != nullptr && kas_cells16_ok(full, ctx->lds_lane_order_ok, kas_built_mask(full.Wc, 1));
-  const bool need32 = c16 == nullptr || !native16;             // int32 cell pools on the device
-  if (h->cur_len < full.cur_need || (all_rows && h->out_len < full.out_need) || h->aux_len < full.aux_need ||
-      h->ctx_len < full.ctx_need)
-    return set_error(KAS_E_INVALID_ARG, "a descriptor offset reaches beyond the pool length given in kas_tables");
-  if ((full.cur_need > full.cur_lo && !have_cur) || (all_rows && full.out_need > full.out_lo && !have_out) ||
-      (full.aux_need > full.aux_lo && !h->aux) || (full.ctx_need > full.ctx_lo && !h->ctx) || (T && !h->topic_results) ||
-      (S && !h->scenario_results))
-    return set_error(KAS_E_INVALID_ARG, "a table the descriptors refer to is NULL");
-  // rows of the selected scenarios, packed: where each one goes
-  std::vector<int64_t> sel_off;
-  if (!all_rows) {
-    int64_t at = 0;
-    sel_off.resize((size_t)n_select + 1);
-    for (int32_t k = 0; k < n_select; ++k) {
-      if (select[k] < 0 || select[k] >= S) return set_error(KAS_E_INVALID_ARG, "select: scenario index out of range");
-      sel_off[(size_t)k] = at;
-      const kas_scenario_desc& sd = batch->scenarios[select[k]];
-      for (int32_t t = 0; t < sd.topic_count; ++t) {
-        const kas_topic_desc& td = batch->topics[sd.topic_begin + t];
-        at += (int64_t)td.n_partitions * td.out_width;
-      }
-    }
-    sel_off[(size_t)n_select] = at;
-    if (h->out_len < at || (at > 0 && !have_out))
-      return set_error(KAS_E_INVALID_ARG, "select: out / out_len too small for the selected scenarios' rows");
-  }
-  // device pools: only [lo, need) of each is ever touched, the pointers are rebased so that the
-  // descriptors' absolute offsets apply (+ 8 ints: the fill kernel's full-row loads re-read the last
-  // row for lanes past the end)
-  int rc;
-  // (a 16-bit call solved on its own cells never touches the int32 pools: not reserved for it)
-  if (need32 && (rc = kas_host_buf(ctx, &ctx->h_cur, sizeof(int32_t) * (size_t)(full.cur_need - full.cur_lo + 8))) != KAS_E_OK) return rc;
-  if (need32 && (rc = kas_host_buf(ctx, &ctx->h_out, sizeof(int32_t) * (size_t)(full.out_need - full.out_lo + 8))) != KAS_E_OK) return rc;
-  if ((rc = kas_host_buf(ctx, &ctx->h_aux, sizeof(int32_t) * (size_t)(full.aux_need - full.aux_lo + 8))) != KAS_E_OK) return rc;
-  if ((rc = kas_host_buf(ctx, &ctx->h_ctx, sizeof(int32_t) * (size_t)(full.ctx_need - full.ctx_lo + 8))) != KAS_E_OK) return rc;
-  if (c16 && ((rc = kas_host_buf(ctx, &ctx->h_cur16, sizeof(uint16_t) * (size_t)(full.cur_need - full.cur_lo + 8))) != KAS_E_OK ||
-              (rc = kas_host_buf(ctx, &ctx->h_out16, sizeof(uint16_t) * (size_t)(full.out_need - full.out_lo + 8))) != KAS_E_OK))
-    return rc;
-  if ((rc = kas_host_buf(ctx, &ctx->h_tr, sizeof(kas_topic_result) * (size_t)(T + 1))) != KAS_E_OK) return rc;
-  if ((rc = kas_host_buf(ctx, &ctx->h_sr, sizeof(kas_scenario_result) * (size_t)(S + 1))) != KAS_E_OK) return rc;
+  batch = &hc.batch;                                           // (a 16-bit call: node i of every scenario has the id i)
+  const KasShape& full = hc.full;
+  const int K = hc.K;
+  const int64_t S = batch->n_scenarios;
+  const bool all_rows = hc.all_rows, native16 = hc.native16, widened = c16 && !native16;
   // The result records come back through pinned staging of the context's own: the caller's record arrays are ordinary
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  if ((rc = kas_host_pinned(ctx, &ctx->h_tr_pin, sizeof(kas_topic_result) * (size_t)(T + 1))) != KAS_E_OK) return rc;
-  if ((rc = kas_host_pinned(ctx, &ctx->h_sr_pin, sizeof(kas_scenario_result) * (size_t)(S + 1))) != KAS_E_OK) return rc;
-  // impact records (kas_solve_host_impact): scenario s's node block starts at the sum of the n_nodes before it
-  std::vector<int64_t> imp_base;
-  if (himp) {
-    imp_base.assign((size_t)S + 1, 0);
-    for (int64_t s = 0; s < S; ++s) imp_base[(size_t)s + 1] = imp_base[(size_t)s] + (batch->scenarios[s].n_nodes > 0 ? batch->scenarios[s].n_nodes : 0);
-    if ((S > 0 && !himp->scenarios) || (imp_base[(size_t)S] > 0 && !himp->nodes))
-      return set_error(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
-    if ((rc = kas_host_buf(ctx, &ctx->h_imp_nodes, sizeof(kas_node_impact) * (size_t)(imp_base[(size_t)S] + 1))) != KAS_E_OK ||
-        (rc = kas_host_buf(ctx, &ctx->h_imp_scen, sizeof(kas_scenario_impact) * (size_t)(S + 1))) != KAS_E_OK)
-      return rc;
-  }
-  kas_topic_result* p_tr = (kas_topic_result*)ctx->h_tr_pin.p;
-  kas_scenario_result* p_sr = (kas_scenario_result*)ctx->h_sr_pin.p;
-  int32_t* d_cur = need32 ? (int32_t*)ctx->h_cur.p - full.cur_lo : nullptr;
-  int32_t* d_out = need32 ? (int32_t*)ctx->h_out.p - full.out_lo : nullptr;
-  uint16_t* d_cur16 = c16 ? (uint16_t*)ctx->h_cur16.p - full.cur_lo : nullptr;
-  uint16_t* d_out16 = c16 ? (uint16_t*)ctx->h_out16.p - full.out_lo : nullptr;
-  int32_t* d_aux = (int32_t*)ctx->h_aux.p - full.aux_lo;
-  int32_t* d_ctx = (int32_t*)ctx->h_ctx.p - full.ctx_lo;
-  kas_topic_result* d_tr = (kas_topic_result*)ctx->h_tr.p;
-  kas_scenario_result* d_sr = (kas_scenario_result*)ctx->h_sr.p;
+  for (int i = 0; i < KAS_HB_COUNT; ++i)
+    if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
+  // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
+  auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
+  int32_t* d_cur = (int32_t*)rebased(KAS_HB_CUR, 4, full.cur_lo);
+  int32_t* d_out = (int32_t*)rebased(KAS_HB_OUT, 4, full.out_lo);
+  uint16_t* d_cur16 = (uint16_t*)rebased(KAS_HB_CUR16, 2, full.cur_lo);
+  uint16_t* d_out16 = (uint16_t*)rebased(KAS_HB_OUT16, 2, full.out_lo);
+  int32_t* d_aux = (int32_t*)rebased(KAS_HB_AUX, 4, full.aux_lo);
+  int32_t* d_ctx = (int32_t*)rebased(KAS_HB_CTX, 4, full.ctx_lo);
+  kas_topic_result* d_tr = (kas_topic_result*)ctx->hbuf[KAS_HB_TR].p;
+  kas_scenario_result* d_sr = (kas_scenario_result*)ctx->hbuf[KAS_HB_SR].p;
+  kas_topic_result* p_tr = (kas_topic_result*)ctx->hbuf[KAS_HB_TR_PIN].p;
+  kas_scenario_result* p_sr = (kas_scenario_result*)ctx->hbuf[KAS_HB_SR_PIN].p;
+  // 16-bit cells travel through the 16-bit pools whatever they are solved on
+  const KasCellPool cur = c16 ? KasCellPool{(char*)d_cur16, (char*)c16->cur, 2} : KasCellPool{(char*)d_cur, (char*)h->cur, 4};
+  const KasCellPool out = c16 ? KasCellPool{(char*)d_out16, (char*)c16->out, 2} : KasCellPool{(char*)d_out, (char*)h->out, 4};
 
-  // ---- scenario ranges (chains).  Large tables laid out scenario by scenario are cut so that the upload
-  // of one range, the solve of the previous one and the download of the one before overlap.
-  const int64_t bytes_in = (int64_t)cell * (full.cur_need - full.cur_lo);
-  const int64_t bytes_out = all_rows ? (int64_t)cell * (full.out_need - full.out_lo) : 0;
-  int K = 1;
-  if (bytes_in + bytes_out >= KAS_HOST_SPLIT_MIN_BYTES && S >= 2) {
-    K = (int)((bytes_in + bytes_out) / (KAS_HOST_SPLIT_MIN_BYTES / 2));
-    if (K > KAS_HOST_SPLIT_MAX) K = KAS_HOST_SPLIT_MAX;
-    if (const char* e = getenv("KAS_HOST_RANGES")) { const int k = atoi(e); if (k >= 1 && k <= KAS_HOST_STREAMS) K = k; }
-    if (K > S) K = (int)S;
-  }
-  std::vector<KasChain> chains;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    chains.assign((size_t)K, KasChain());
-    bool ok = true;
-    for (int i = 0; i < K && ok; ++i) {
-      KasChain& c = chains[(size_t)i];
-      kas_shard_range(S, i, K, &c.lo, &c.hi);
-      c.scen.resize((size_t)(c.hi - c.lo) + 1);
-      if ((rc = kas_batch_slice(batch, c.lo, c.hi, c.scen.data(), &c.bd, nullptr, nullptr)) != KAS_E_OK) return rc;
-      c.tlo = c.bd.topics ? (int64_t)(c.bd.topics - batch->topics) : 0;
-      c.thi = c.tlo + c.bd.n_topics;
-      if (K > 1) {
-        // extents of the range; ranges must own disjoint, ascending stretches of topics, cur and out
-        KasShape sh;
-        std::string err;
-        if ((rc = kas_shape_batch(&c.bd, &sh, &err, 0, 0)) != KAS_E_OK) return set_error(rc, err);
-        c.cur_lo = sh.cur_lo; c.cur_hi = sh.cur_need; c.out_lo = sh.out_lo; c.out_hi = sh.out_need;
-        if (i > 0) {
-          const KasChain& q = chains[(size_t)i - 1];
-          ok = c.tlo >= q.thi && c.cur_lo >= q.cur_hi && c.out_lo >= q.out_hi;
-        }
-      } else {
-        c.cur_lo = full.cur_lo; c.cur_hi = full.cur_need; c.out_lo = full.out_lo; c.out_hi = full.out_need;
-      }
-    }
-    if (ok) break;
-    K = 1;                                                     // shared or interleaved tables: one range
-  }
-  for (KasChain& c : chains) {
-    rc = kas_host_plan(ctx, &c.bd, &c.plan, native16 ? 1 : 0);
+  kas_plan* plans[KAS_HOST_STREAMS];
+  for (int i = 0; i < K; ++i) {
+    rc = kas_host_plan(ctx, &hc.ranges[(size_t)i].bd, &plans[i], native16 ? 1 : 0);
     if (rc == KAS_E_UNSUPPORTED && native16)                   // (cannot happen: a range's shape is a part of the batch's)
       return set_error(KAS_E_UNSUPPORTED, "internal: a scenario range of a batch the 16-bit kernels take was refused by them: " + g_last_error);
     if (rc != KAS_E_OK) return rc;
   }
 
   // ---- enqueue.  From here on every exit drains the streams first.
-  if ((rc = kas_host_solve_streams(ctx, K > 1 ? K : 1)) != KAS_E_OK) return rc;
+  if ((rc = kas_host_solve_streams(ctx, K)) != KAS_E_OK) return rc;
   hipStream_t s0 = ctx->hstream[0];
   hipError_t he = hipSuccess;
   int fail_rc = KAS_E_OK;
@@ -1621,25 +1382,33 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (ctx->hup) hip_ok(hipStreamSynchronize(ctx->hup), "hipStreamSynchronize");
     if (ctx->hdown) hip_ok(hipStreamSynchronize(ctx->hdown), "hipStreamSynchronize");
   };
-  static_assert(KAS_HOST_SPLIT_MAX <= KAS_HOST_STREAMS, "one event pair per scenario range");
   // one range: everything on s0.  Several: uploads on hup, solves on hstream[i], downloads on hdown.
   hipStream_t s_up = K > 1 ? ctx->hup : s0, s_down = K > 1 ? ctx->hdown : s0;
+  // a widened call: int32 cells from / to the 16-bit ones, on the stream that solves (the copy streams only copy)
+  auto widen = [&](hipStream_t st, int64_t at, int64_t n) {
+    hipLaunchKernelGGL(kas_cells_widen_kernel, dim3(kas_cells_grid(n)), dim3(256), 0, st, d_cur16 + at, d_cur + at, n);
+    return hip_ok(hipGetLastError(), "kas_cells_widen_kernel");
+  };
+  // (into the staging buffer, not into the caller's pinned pool: the kernel's stores over the link ran at 20 GB/s —
+  // a call of 240 scenarios 10.5 ms against 8.4 ms with the copy engine, experiments/README.md)
+  auto narrow = [&](hipStream_t st, int64_t at, int64_t n) {
+    hipLaunchKernelGGL(kas_cells_narrow_kernel, dim3(kas_cells_grid(n)), dim3(256), 0, st, d_out + at, d_out16 + at, n);
+    return hip_ok(hipGetLastError(), "kas_cells_narrow_kernel");
+  };
+  auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st, const char* what) {
+    return hip_ok(hipMemcpyAsync(dst, src, bytes, kind, st), what);
+  };
+  const KasExtent aux_x{full.aux_lo, full.aux_need}, ctx_x{full.ctx_lo, full.ctx_need};
   // pools every range reads (aux, Context) go up first (the ranges' own uploads queue behind them on the same stream)
-  if (full.aux_need > full.aux_lo)
-    hip_ok(hipMemcpyAsync(d_aux + full.aux_lo, h->aux + full.aux_lo, 4 * (size_t)(full.aux_need - full.aux_lo), hipMemcpyHostToDevice, s_up), "upload aux");
-  if (full.ctx_need > full.ctx_lo)
-    hip_ok(hipMemcpyAsync(d_ctx + full.ctx_lo, h->ctx + full.ctx_lo, 4 * (size_t)(full.ctx_need - full.ctx_lo), hipMemcpyHostToDevice, s_up), "upload ctx");
+  if (aux_x.hi > aux_x.lo) copy(d_aux + aux_x.lo, h->aux + aux_x.lo, 4 * (size_t)(aux_x.hi - aux_x.lo), hipMemcpyHostToDevice, s_up, "upload aux");
+  if (ctx_x.hi > ctx_x.lo) copy(d_ctx + ctx_x.lo, h->ctx + ctx_x.lo, 4 * (size_t)(ctx_x.hi - ctx_x.lo), hipMemcpyHostToDevice, s_up, "upload ctx");
   auto download = [&](int i) {
-    const KasChain& c = chains[(size_t)i];
+    const KasHostRange& r = hc.ranges[(size_t)i];
+    const KasExtent &o = r.own[KAS_POOL_OUT], &t = r.own[KAS_POOL_TOPICS];
     if (K > 1) hip_ok(hipStreamWaitEvent(s_down, ctx->hev_done[i], 0), "wait");
-    if (all_rows && c.out_hi > c.out_lo) {
-      if (c16) hip_ok(hipMemcpyAsync(c16->out + c.out_lo, d_out16 + c.out_lo, 2 * (size_t)(c.out_hi - c.out_lo), hipMemcpyDeviceToHost, s_down), "download out");
-      else hip_ok(hipMemcpyAsync(h->out + c.out_lo, d_out + c.out_lo, 4 * (size_t)(c.out_hi - c.out_lo), hipMemcpyDeviceToHost, s_down), "download out");
-    }
-    if (c.thi > c.tlo)
-      hip_ok(hipMemcpyAsync(p_tr + c.tlo, d_tr + c.tlo, sizeof(kas_topic_result) * (size_t)(c.thi - c.tlo), hipMemcpyDeviceToHost, s_down), "download topic results");
-    if (c.hi > c.lo)
-      hip_ok(hipMemcpyAsync(p_sr + c.lo, d_sr + c.lo, sizeof(kas_scenario_result) * (size_t)(c.hi - c.lo), hipMemcpyDeviceToHost, s_down), "download scenario results");
+    if (all_rows && o.hi > o.lo) copy(out.h(o.lo), out.d(o.lo), out.cell * (size_t)(o.hi - o.lo), hipMemcpyDeviceToHost, s_down, "download out");
+    if (t.hi > t.lo) copy(p_tr + t.lo, d_tr + t.lo, sizeof(kas_topic_result) * (size_t)(t.hi - t.lo), hipMemcpyDeviceToHost, s_down, "download topic results");
+    if (r.hi > r.lo) copy(p_sr + r.lo, d_sr + r.lo, sizeof(kas_scenario_result) * (size_t)(r.hi - r.lo), hipMemcpyDeviceToHost, s_down, "download scenario results");
   };
   // software-pipelined issue order (upload i, solve i, download i - 2): with pageable host memory the copies block
   // the issuing thread, and this order still lets the device overlap them with the solves.  (A range's solve takes
@@ -1647,80 +1416,62 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // a lag of one made the thread wait ~1 ms per range: 15.6 ms per call of eight ranges.)
   const int lag = K >= 3 ? 2 : 1;
   for (int i = 0; i < K && he == hipSuccess && fail_rc == KAS_E_OK; ++i) {
-    KasChain& c = chains[(size_t)i];
+    const KasHostRange& r = hc.ranges[(size_t)i];
+    const KasExtent &c = r.own[KAS_POOL_CUR], &o = r.own[KAS_POOL_OUT];
     hipStream_t st = K > 1 ? ctx->hstream[i % KAS_HOST_STREAMS] : s0;
-    if (c.cur_hi > c.cur_lo) {
-      if (c16) hip_ok(hipMemcpyAsync(d_cur16 + c.cur_lo, c16->cur + c.cur_lo, 2 * (size_t)(c.cur_hi - c.cur_lo), hipMemcpyHostToDevice, s_up), "upload cur");
-      else hip_ok(hipMemcpyAsync(d_cur + c.cur_lo, h->cur + c.cur_lo, 4 * (size_t)(c.cur_hi - c.cur_lo), hipMemcpyHostToDevice, s_up), "upload cur");
-    }
+    if (c.hi > c.lo) copy(cur.d(c.lo), cur.h(c.lo), cur.cell * (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s_up, "upload cur");
     if (K > 1) {
       hip_ok(hipEventRecord(ctx->hev_up[i], s_up), "record");
       hip_ok(hipStreamWaitEvent(st, ctx->hev_up[i], 0), "wait");
     }
     if (he != hipSuccess) break;
-    if (c16 && !native16 && c.cur_hi > c.cur_lo) {             // (on the range's solve stream: the copy streams only copy)
-      const int64_t n = c.cur_hi - c.cur_lo;
-      hipLaunchKernelGGL(kas_cells_widen_kernel, dim3(kas_cells_grid(n)), dim3(256), 0, st, d_cur16 + c.cur_lo, d_cur + c.cur_lo, n);
-      if (!hip_ok(hipGetLastError(), "kas_cells_widen_kernel")) break;
-    }
+    if (widened && c.hi > c.lo && !widen(st, c.lo, c.hi - c.lo)) break;
     kas_tables d;
     memset(&d, 0, sizeof(d));
-    d.cur = d_cur; d.out = d_out; d.aux = d_aux; d.ctx = d_ctx;
-    d.topic_results = d_tr + c.tlo; d.scenario_results = d_sr + c.lo;
-    if (native16) { d.cur = reinterpret_cast<const int32_t*>(d_cur16); d.out = reinterpret_cast<int32_t*>(d_out16); }
-    const int src = kas_solve_device_impl(c.plan, &d, st);
+    d.cur = native16 ? reinterpret_cast<const int32_t*>(d_cur16) : d_cur;
+    d.out = native16 ? reinterpret_cast<int32_t*>(d_out16) : d_out;
+    d.aux = d_aux; d.ctx = d_ctx;
+    d.topic_results = d_tr + r.own[KAS_POOL_TOPICS].lo; d.scenario_results = d_sr + r.lo;
+    const int src = kas_solve_device_impl(plans[i], &d, st);
     if (src != KAS_E_OK) { fail_rc = src; break; }
     if (himp) {                                                // the impact pass on the range's solve stream, behind its solve
       kas_impact_tables di;
-      di.nodes = (kas_node_impact*)ctx->h_imp_nodes.p + imp_base[(size_t)c.lo];
-      di.scenarios = (kas_scenario_impact*)ctx->h_imp_scen.p + c.lo;
-      const int irc = kas_impact_impl(c.plan, &d, &di, st, &c.bd);
+      di.nodes = (kas_node_impact*)ctx->hbuf[KAS_HB_IMP_NODES].p + hc.imp_base[(size_t)r.lo];
+      di.scenarios = (kas_scenario_impact*)ctx->hbuf[KAS_HB_IMP_SCEN].p + r.lo;
+      const int irc = kas_impact_impl(plans[i], &d, &di, st, &r.bd);
       if (irc != KAS_E_OK) { fail_rc = irc; break; }
     }
-    if (c16 && !native16 && all_rows && c.out_hi > c.out_lo) {
-      const int64_t n = c.out_hi - c.out_lo;
-      // (into the staging buffer, not into the caller's pinned pool: the kernel's stores over the link ran at 20 GB/s —
-      // a call of 240 scenarios 10.5 ms against 8.4 ms with the copy engine, experiments/README.md)
-      hipLaunchKernelGGL(kas_cells_narrow_kernel, dim3(kas_cells_grid(n)), dim3(256), 0, st, d_out + c.out_lo, d_out16 + c.out_lo, n);
-      if (!hip_ok(hipGetLastError(), "kas_cells_narrow_kernel")) break;
-    }
+    if (widened && all_rows && o.hi > o.lo && !narrow(st, o.lo, o.hi - o.lo)) break;
     if (K > 1) hip_ok(hipEventRecord(ctx->hev_done[i], st), "record");
     if (i >= lag) download(i - lag);
   }
   for (int i = K - lag < 0 ? 0 : K - lag; i < K && he == hipSuccess && fail_rc == KAS_E_OK; ++i) download(i);
   drain();
   if (he != hipSuccess || fail_rc != KAS_E_OK) return fail_rc != KAS_E_OK ? fail_rc : KAS_E_HIP;
-  for (const KasChain& c : chains) {                           // (only what the ranges own: as the direct copies did)
-    if (c.thi > c.tlo) memcpy(h->topic_results + c.tlo, p_tr + c.tlo, sizeof(kas_topic_result) * (size_t)(c.thi - c.tlo));
-    if (c.hi > c.lo) memcpy(h->scenario_results + c.lo, p_sr + c.lo, sizeof(kas_scenario_result) * (size_t)(c.hi - c.lo));
+  for (const KasHostRange& r : hc.ranges) {                    // (only what the ranges own: as the direct copies did)
+    const KasExtent& t = r.own[KAS_POOL_TOPICS];
+    if (t.hi > t.lo) memcpy(h->topic_results + t.lo, p_tr + t.lo, sizeof(kas_topic_result) * (size_t)(t.hi - t.lo));
+    if (r.hi > r.lo) memcpy(h->scenario_results + r.lo, p_sr + r.lo, sizeof(kas_scenario_result) * (size_t)(r.hi - r.lo));
   }
   // Context counters back; the selected scenarios' rows, packed
-  if (full.ctx_need > full.ctx_lo)
-    hip_ok(hipMemcpyAsync(h->ctx + full.ctx_lo, d_ctx + full.ctx_lo, 4 * (size_t)(full.ctx_need - full.ctx_lo), hipMemcpyDeviceToHost, s0), "download ctx");
-  if (!all_rows) {
-    for (int32_t k = 0; k < n_select && he == hipSuccess; ++k) {
-      const kas_scenario_desc& sd = batch->scenarios[select[k]];
-      int64_t at = sel_off[(size_t)k];
-      for (int32_t t = 0; t < sd.topic_count && he == hipSuccess; ++t) {
-        const kas_topic_desc& td = batch->topics[sd.topic_begin + t];
-        const int64_t cells = (int64_t)td.n_partitions * td.out_width;
-        if (cells > 0 && c16) {
-          if (!native16) {
-            hipLaunchKernelGGL(kas_cells_narrow_kernel, dim3(kas_cells_grid(cells)), dim3(256), 0, s0, d_out + td.out_off, d_out16 + td.out_off, cells);
-            hip_ok(hipGetLastError(), "kas_cells_narrow_kernel");
-          }
-          hip_ok(hipMemcpyAsync(c16->out + at, d_out16 + td.out_off, 2 * (size_t)cells, hipMemcpyDeviceToHost, s0), "download selected rows");
-        } else if (cells > 0)
-          hip_ok(hipMemcpyAsync(h->out + at, d_out + td.out_off, 4 * (size_t)cells, hipMemcpyDeviceToHost, s0), "download selected rows");
-        at += cells;
+  if (ctx_x.hi > ctx_x.lo) copy(h->ctx + ctx_x.lo, d_ctx + ctx_x.lo, 4 * (size_t)(ctx_x.hi - ctx_x.lo), hipMemcpyDeviceToHost, s0, "download ctx");
+  for (int32_t k = 0; !all_rows && k < n_select && he == hipSuccess; ++k) {
+    const kas_scenario_desc& sd = batch->scenarios[select[k]];
+    int64_t at = hc.sel_off[(size_t)k];
+    for (int32_t t = 0; t < sd.topic_count && he == hipSuccess; ++t) {
+      const kas_topic_desc& td = batch->topics[sd.topic_begin + t];
+      const int64_t cells = (int64_t)td.n_partitions * td.out_width;
+      if (cells > 0) {
+        if (widened) narrow(s0, td.out_off, cells);
+        copy(out.h(at), out.d(td.out_off), out.cell * (size_t)cells, hipMemcpyDeviceToHost, s0, "download selected rows");
       }
+      at += cells;
     }
   }
   if (himp) {
-    if (imp_base[(size_t)S] > 0)
-      hip_ok(hipMemcpyAsync(himp->nodes, ctx->h_imp_nodes.p, sizeof(kas_node_impact) * (size_t)imp_base[(size_t)S], hipMemcpyDeviceToHost, s0), "download node impact");
-    if (S > 0)
-      hip_ok(hipMemcpyAsync(himp->scenarios, ctx->h_imp_scen.p, sizeof(kas_scenario_impact) * (size_t)S, hipMemcpyDeviceToHost, s0), "download scenario impact");
+    const int64_t nodes = hc.imp_base[(size_t)S];
+    if (nodes > 0) copy(himp->nodes, ctx->hbuf[KAS_HB_IMP_NODES].p, sizeof(kas_node_impact) * (size_t)nodes, hipMemcpyDeviceToHost, s0, "download node impact");
+    if (S > 0) copy(himp->scenarios, ctx->hbuf[KAS_HB_IMP_SCEN].p, sizeof(kas_scenario_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario impact");
   }
   hip_ok(hipStreamSynchronize(s0), "hipStreamSynchronize");
   return he == hipSuccess ? KAS_E_OK : fail_rc;
@@ -1767,39 +1518,23 @@ int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_
   // Every shard downloads the whole extent of `out` (and round-trips the whole extent of `ctx`) its scenarios refer
   // to: with pools that are not laid out in scenario order one shard's download would overwrite rows or Context
   // counters another has already delivered.  Such a batch is solved on one context (same results, no overlap).
+  std::vector<KasHostRange> shards;
   {
-    int64_t out_end = -1, ctx_end = -1;
-    bool disjoint = true;
-    for (int32_t r = 0; r < n_ctx && disjoint; ++r) {
-      int64_t lo = 0, hi = 0;
-      kas_shard_range(batch->n_scenarios, r, n_ctx, &lo, &hi);
-      if (hi <= lo) continue;
-      std::vector<kas_scenario_desc> scratch((size_t)(hi - lo));
-      kas_batch_desc bd;
-      kas_tables ht;
-      KasShape sh;
-      std::string err;
-      int rc = kas_batch_slice(batch, lo, hi, scratch.data(), &bd, h, &ht);
-      if (rc == KAS_E_OK) rc = kas_shape_batch(&bd, &sh, &err, 0, 0);
-      if (rc != KAS_E_OK) return rc == KAS_E_OK ? rc : set_error(rc, "shard " + std::to_string(r) + ": " + (err.empty() ? g_last_error : err));
-      if (sh.out_need > sh.out_lo) { disjoint = disjoint && sh.out_lo >= out_end; out_end = sh.out_need; }
-      if (sh.ctx_need > sh.ctx_lo) { disjoint = disjoint && sh.ctx_lo >= ctx_end; ctx_end = sh.ctx_need; }
-    }
-    if (!disjoint) return kas_solve_host(ctxs[0], batch, h);
+    std::string err;
+    int32_t bad = 0;
+    const int rc = kas_cut_ranges(batch, n_ctx, nullptr, &shards, &err, &bad);
+    if (rc != KAS_E_OK) return set_error(rc, "shard " + std::to_string(bad) + ": " + err);
   }
+  if (!kas_ranges_disjoint(shards, (1u << KAS_POOL_OUT) | (1u << KAS_POOL_CTX), false)) return kas_solve_host(ctxs[0], batch, h);
   std::vector<int> rcs((size_t)n_ctx, KAS_E_OK);
   std::vector<std::string> errs((size_t)n_ctx);
   std::vector<std::thread> threads;
   for (int32_t r = 0; r < n_ctx; ++r) {
     threads.emplace_back([&, r]() {
-      int64_t lo = 0, hi = 0;
-      kas_shard_range(batch->n_scenarios, r, n_ctx, &lo, &hi);
-      if (hi <= lo) return;
-      std::vector<kas_scenario_desc> scratch((size_t)(hi - lo));
-      kas_batch_desc bd;
-      kas_tables ht;
-      int rc = kas_batch_slice(batch, lo, hi, scratch.data(), &bd, h, &ht);
-      if (rc == KAS_E_OK) rc = kas_solve_host(ctxs[r], &bd, &ht);
+      const KasHostRange& sh = shards[(size_t)r];
+      if (sh.hi <= sh.lo) return;
+      const kas_tables ht = kas_tables_at(*h, sh.own[KAS_POOL_TOPICS].lo, sh.lo);
+      const int rc = kas_solve_host(ctxs[r], &sh.bd, &ht);
       rcs[(size_t)r] = rc;
       if (rc != KAS_E_OK) errs[(size_t)r] = g_last_error;      // (thread-local: carried to the caller below)
     });

@@ -1,0 +1,403 @@
+// kas_host_call.h — what a host call (kas_solve_host*, kas_solve_host_sharded) will do, decided ONCE and on the CPU.
+//
+// Pure host C++ (no HIP calls, no environment).  kas_plan_host_call() turns a call's arguments into a KasHostCall: the batch the
+// kernels see, its shape, the cell width it is solved on, where selected rows and impact records go, the scenario ranges and the
+// byte size of every buffer the call needs.  The library (kas_hip.hip) reserves, enqueues and drains from that value and holds no
+// decision of its own; the CPU emulator (tests/emu/emu_driver.cpp) exports the same functions to tests/test_host_call.py.
+// Also here: the slicing arithmetic behind kas_shard_range / kas_batch_slice and the pure half of the host path's plan cache.
+// Include behind kas_solver_body.h, as kas_launch_plan.h asks.
+#pragma once
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "kas_plan_math.h"
+#include "kas_launch_plan.h"   // kas_cells16_ok, KAS_BUILT_*
+
+#ifndef KAS_HOST_STREAMS
+#define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
+#endif
+#define KAS_HOST_PLAN_CACHE 16
+#define KAS_HOST_SPLIT_MIN_BYTES (48ll << 20)   // tables smaller than this are moved and solved as one range
+// Scenario ranges of one call.  A range's solve is a chain of ~2.5-3 ms however few scenarios it holds (one workgroup per
+// scenario walks its 100,000 rows), so a call lasts upload + that chain + the last range's download, and more ranges only
+// shorten the last download — while the runtime maps the ranges' solve streams onto GPU_MAX_HW_QUEUES (default 4) hardware
+// queues shared with everything else, where ranges on one queue run one after the other (a kernel + copy trace of eight
+// ranges: the last one solved alone, 3.4 ms after the others).  240 scenarios x 100,000 x 3 cells, 16-bit cells, pinned:
+// 2 ranges 6.4 ms, 3: 6.0, 4: 7.1 (5.9 with eight hardware queues), 8: 7.8; int32 cells 9.3-10.0 ms whatever the count
+// (scripts/e2e_host_path.py; KAS_HOST_RANGES overrides for such measurements).
+#define KAS_HOST_SPLIT_MAX 3
+static_assert(KAS_HOST_SPLIT_MAX <= KAS_HOST_STREAMS, "one event pair per scenario range");
+
+// ---- slicing ------------------------------------------------------------------------------------------------------------
+// kas_shard_range (include/kas_abi.h)
+static inline void kas_range_of(int64_t total, int32_t rank, int32_t world, int64_t* lo, int64_t* hi) {
+  if (world < 1) world = 1;
+  if (rank < 0) rank = 0;
+  if (rank >= world) rank = world - 1;
+  if (total < 0) total = 0;
+  const int64_t base = total / world, rem = total % world;
+  const int64_t l = (int64_t)rank * base + (rank < rem ? rank : rem);
+  if (lo) *lo = l;
+  if (hi) *hi = l + base + (rank < rem ? 1 : 0);
+}
+
+// the tables of a slice that begins at this topic and scenario: the pools as they are, the slice's result records
+static inline kas_tables kas_tables_at(kas_tables t, int64_t topic, int64_t scenario) {
+  if (t.topic_results) t.topic_results += topic;
+  if (t.scenario_results) t.scenario_results += scenario;
+  return t;
+}
+
+// kas_batch_slice (include/kas_abi.h)
+static inline int kas_slice_batch(const kas_batch_desc* b, int64_t lo, int64_t hi, kas_scenario_desc* scratch, kas_batch_desc* out,
+                                  const kas_tables* tables, kas_tables* tables_out, std::string* err) {
+  auto fail = [&](const std::string& m) { if (err) *err = m; return KAS_E_INVALID_ARG; };
+  if (!b || !out || lo < 0 || hi < lo || hi > b->n_scenarios || (hi > lo && (!scratch || !b->scenarios)))
+    return fail("kas_batch_slice: bad range / NULL argument");
+  int64_t tlo = INT64_MAX, thi = 0, nlo = INT64_MAX, nhi = 0;
+  for (int64_t i = lo; i < hi; ++i) {
+    const kas_scenario_desc& sd = b->scenarios[i];
+    if (sd.topic_begin < 0 || sd.topic_count < 0 || (int64_t)sd.topic_begin + sd.topic_count > b->n_topics || sd.n_nodes < 0 ||
+        sd.node_off < 0 || sd.node_off + sd.n_nodes > b->node_pool_len)
+      return fail("kas_batch_slice: scenario " + std::to_string(i) + " refers outside the batch");
+    if (sd.topic_count > 0) {
+      if (sd.topic_begin < tlo) tlo = sd.topic_begin;
+      if ((int64_t)sd.topic_begin + sd.topic_count > thi) thi = (int64_t)sd.topic_begin + sd.topic_count;
+    }
+    if (sd.n_nodes > 0) {
+      if (sd.node_off < nlo) nlo = sd.node_off;
+      if (sd.node_off + sd.n_nodes > nhi) nhi = sd.node_off + sd.n_nodes;
+    }
+  }
+  if (tlo > thi) tlo = thi = 0;
+  if (nlo > nhi) nlo = nhi = 0;
+  for (int64_t i = lo; i < hi; ++i) {
+    kas_scenario_desc sd = b->scenarios[i];
+    sd.topic_begin = sd.topic_count > 0 ? (int32_t)(sd.topic_begin - tlo) : 0;
+    sd.node_off = sd.n_nodes > 0 ? sd.node_off - nlo : 0;
+    scratch[i - lo] = sd;
+  }
+  out->n_scenarios = (int32_t)(hi - lo);
+  out->n_topics = (int32_t)(thi - tlo);
+  out->scenarios = scratch;
+  out->topics = b->topics ? b->topics + tlo : nullptr;
+  out->node_id = b->node_id ? b->node_id + nlo : nullptr;
+  out->node_rack = b->node_rack ? b->node_rack + nlo : nullptr;
+  out->node_pool_len = nhi - nlo;
+  if (tables && tables_out) *tables_out = kas_tables_at(*tables, tlo, lo);
+  return KAS_E_OK;
+}
+
+// One scenario range of a batch — a range of a host call, a shard of kas_solve_host_sharded: its slice, and the stretches of the
+// pools it touches
+struct KasExtent { int64_t lo = 0, hi = 0; };
+enum KasPool { KAS_POOL_TOPICS, KAS_POOL_CUR, KAS_POOL_OUT, KAS_POOL_CTX, KAS_POOLS };
+struct KasHostRange {
+  int64_t lo = 0, hi = 0;                       // scenarios
+  std::vector<kas_scenario_desc> scen;          // rebased descriptors of the slice
+  kas_batch_desc bd{};
+  KasExtent own[KAS_POOLS];                     // topics (absolute indices), cur, out, ctx
+};
+
+// [0, n_scenarios) cut into K ranges (kas_range_of), each sliced and — unless it is the whole batch, whose shape the caller has —
+// shaped for its extents (an empty one of several is left as it is: all zero).  A KAS_E_* and its text; *bad: the range that was refused.
+static inline int kas_cut_ranges(const kas_batch_desc* b, int32_t K, const KasShape* whole, std::vector<KasHostRange>* out, std::string* err,
+                                 int32_t* bad = nullptr) {
+  out->assign((size_t)K, KasHostRange());
+  for (int32_t i = 0; i < K; ++i) {
+    KasHostRange& r = (*out)[(size_t)i];
+    if (bad) *bad = i;
+    kas_range_of(b->n_scenarios, i, K, &r.lo, &r.hi);
+    if (r.hi <= r.lo && K > 1) continue;
+    r.scen.resize((size_t)(r.hi - r.lo) + 1);
+    int rc = kas_slice_batch(b, r.lo, r.hi, r.scen.data(), &r.bd, nullptr, nullptr, err);
+    if (rc != KAS_E_OK) return rc;
+    const int64_t tlo = r.bd.topics ? (int64_t)(r.bd.topics - b->topics) : 0;
+    r.own[KAS_POOL_TOPICS] = {tlo, tlo + r.bd.n_topics};
+    KasShape own;
+    if (!(K == 1 && whole) && (rc = kas_shape_batch(&r.bd, &own, err, 0, 0)) != KAS_E_OK) return rc;
+    const KasShape& sh = K == 1 && whole ? *whole : own;
+    r.own[KAS_POOL_CUR] = {sh.cur_lo, sh.cur_need};
+    r.own[KAS_POOL_OUT] = {sh.out_lo, sh.out_need};
+    r.own[KAS_POOL_CTX] = {sh.ctx_lo, sh.ctx_need};
+  }
+  return KAS_E_OK;
+}
+
+// Do the ranges own ascending, disjoint stretches of every pool in `pools` (bits 1 << KasPool)?  Ranges that do may be moved and
+// solved independently: no copy of one overwrites what another delivered.  `empty_counts`: an empty stretch must lie in line as
+// well (the ranges of a host call); else it is passed over (the shards of kas_solve_host_sharded).
+static inline bool kas_ranges_disjoint(const std::vector<KasHostRange>& ranges, uint32_t pools, bool empty_counts) {
+  for (int32_t p = 0; p < KAS_POOLS; ++p) {
+    if (!((pools >> p) & 1u)) continue;
+    int64_t end = INT64_MIN;
+    for (const KasHostRange& r : ranges) {
+      const KasExtent& e = r.own[p];
+      if (e.hi <= e.lo && !empty_counts) continue;
+      if (e.lo < end) return false;
+      end = e.hi;
+    }
+  }
+  return true;
+}
+
+// 16-bit cells are node indices: the node table the kernels see gives node i the id i (`ids` holds it, `out` = *b with it).
+// `ids` may be a table an earlier call filled (the context's): it is rewritten only where the scenarios' node ranges
+// differ from the ones it was filled for (`stamp`: a hash of them) — a what-if caller's 1000 x 1000 table stays.
+static inline int kas_ident_batch(const kas_batch_desc* b, std::vector<int32_t>* ids, kas_batch_desc* out, uint64_t* stamp, std::string* err) {
+  auto fail = [&](int code, const std::string& m) { if (err) *err = m; return code; };
+  if (b->n_scenarios < 0 || b->node_pool_len < 0 || (b->n_scenarios > 0 && !b->scenarios))
+    return fail(KAS_E_INVALID_ARG, "negative size / scenarios == NULL");
+  uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)b->node_pool_len;
+  for (int32_t s = 0; s < b->n_scenarios; ++s) {
+    const kas_scenario_desc& sd = b->scenarios[s];
+    if (sd.n_nodes < 0 || sd.node_off < 0 || sd.node_off + sd.n_nodes > b->node_pool_len)
+      return fail(KAS_E_INVALID_ARG, "scenario " + std::to_string(s) + ": node table outside the node pool");
+    // (a cell's bit 15 says "no holder" inside the kernels, mid_to_index: an index is below 32,768 — KAS_N_LIMIT, the
+    // limit of every plan; 0xFFFF is the only cell value above it that means anything)
+    if (sd.n_nodes > KAS_N_LIMIT)
+      return fail(KAS_E_UNSUPPORTED, "scenario " + std::to_string(s) + ": more than 32,767 brokers do not fit 16-bit cells");
+    h = (h ^ (((uint64_t)(uint32_t)sd.node_off << 32) | (uint32_t)sd.n_nodes)) * 0x100000001b3ull;
+    h ^= h >> 29;
+  }
+  h |= 1ull;
+  if (!(stamp && *stamp == h && ids->size() == (size_t)b->node_pool_len)) {
+    ids->assign((size_t)b->node_pool_len, 0);
+    for (int32_t s = 0; s < b->n_scenarios; ++s) {
+      const kas_scenario_desc& sd = b->scenarios[s];
+      for (int32_t i = 0; i < sd.n_nodes; ++i) (*ids)[(size_t)(sd.node_off + i)] = i;
+    }
+    if (stamp) *stamp = h;
+  }
+  *out = *b;
+  out->node_id = ids->data();
+  return KAS_E_OK;
+}
+
+// ---- a host call ----------------------------------------------------------------------------------------------------------
+// the buffers of a context's host path, in the order they are reserved
+enum KasHostBuf {
+  KAS_HB_CUR, KAS_HB_OUT, KAS_HB_AUX, KAS_HB_CTX,   // int32 pools on the device
+  KAS_HB_CUR16, KAS_HB_OUT16,                       // the 16-bit cells of kas_solve_host16 as they travel (widened / narrowed on the device)
+  KAS_HB_TR, KAS_HB_SR,                             // result records on the device
+  KAS_HB_TR_PIN, KAS_HB_SR_PIN,                     // ... and their pinned HOST staging
+  KAS_HB_IMP_NODES, KAS_HB_IMP_SCEN,                // the impact records of kas_solve_host_impact / 16 on the device
+  KAS_HB_COUNT
+};
+static inline bool kas_host_buf_pinned(int32_t id) { return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN; }
+
+// everything the decisions read
+struct KasHostCallIn {
+  const kas_batch_desc* batch = nullptr;
+  int64_t cur_len = 0, out_len = 0, aux_len = 0, ctx_len = 0;   // kas_tables: the pool lengths, and which tables are there
+  bool have_cur = false, have_out = false, have_aux = false, have_ctx = false, have_topic_results = false, have_scenario_results = false;
+  const int32_t* select = nullptr;
+  int32_t n_select = -1;                        // < 0: every scenario's rows come back where the descriptors say
+  bool cells16 = false;                         // cur / out travel as 16-bit node indices
+  std::vector<int32_t>* ident_ids = nullptr;    // ... the identity id table of such a call and its stamp (kas_ident_batch): the context's
+  uint64_t* ident_stamp = nullptr;
+  bool impact = false, have_imp_nodes = false, have_imp_scenarios = false;   // kas_impact_tables
+  int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
+  uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
+  int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
+  KasHostCallIn() { for (uint32_t& m : built16) m = KAS_BUILT_ALL; }
+};
+
+struct KasHostCall {
+  kas_batch_desc batch{};                       // the batch the kernels see (a 16-bit call: with the identity id table)
+  KasShape full;                                // ... validated, with the extents of every pool
+  bool all_rows = true;
+  bool native16 = false;                        // a 16-bit call solved on its own cells (what kas_plan_create16 accepts)
+  bool need32 = true;                           // int32 cell pools on the device: every other call
+  std::vector<int64_t> sel_off;                 // [n_select + 1] where each selected scenario's rows go, packed (cells)
+  std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
+  int32_t K = 1;
+  std::vector<KasHostRange> ranges;             // [K]
+  size_t bytes[KAS_HB_COUNT] = {};              // what to reserve of each buffer; 0: this call must not touch it
+};
+
+// Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
+// that the upload of one range, the solve of the previous one and the download of the one before overlap.
+static inline int32_t kas_host_range_count(int64_t bytes, int64_t S, int32_t ranges_override) {
+  if (bytes < KAS_HOST_SPLIT_MIN_BYTES || S < 2) return 1;
+  int64_t K = bytes / (KAS_HOST_SPLIT_MIN_BYTES / 2);
+  if (K > KAS_HOST_SPLIT_MAX) K = KAS_HOST_SPLIT_MAX;
+  if (ranges_override >= 1 && ranges_override <= KAS_HOST_STREAMS) K = ranges_override;
+  return (int32_t)(K > S ? S : K);
+}
+
+// Validate a host call and decide everything about it.  Returns KAS_E_* and fills err; the checks run in the order callers know.
+static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, std::string* err) {
+  auto fail = [&](int code, const char* m) { if (err) *err = m; return code; };
+  int rc;
+  hc->all_rows = in.n_select < 0;
+  if (!hc->all_rows && in.n_select > 0 && !in.select) return fail(KAS_E_INVALID_ARG, "select == NULL");
+  hc->batch = *in.batch;
+  if (in.cells16 && (rc = kas_ident_batch(in.batch, in.ident_ids, &hc->batch, in.ident_stamp, err)) != KAS_E_OK) return rc;
+  const kas_batch_desc* b = &hc->batch;
+  KasShape& full = hc->full;
+  if ((rc = kas_shape_batch(b, &full, err, 0, 0)) != KAS_E_OK) return rc;
+  const int64_t S = b->n_scenarios, T = b->n_topics;
+  // A 16-bit call is solved on its 16-bit cells where the kernels with that I/O take the batch (what kas_plan_create16
+  // accepts, asked HERE on the shape: a batch the 16-bit kernels refuse never reaches the plan cache with the 16-bit bit
+  // set); any other batch is widened before and narrowed behind an int32 solve.
+  hc->native16 = in.cells16 && kas_cells16_ok(full, in.lane_order_ok, in.built16[full.Wc]);
+  hc->need32 = !hc->native16;
+  if (in.cur_len < full.cur_need || (hc->all_rows && in.out_len < full.out_need) || in.aux_len < full.aux_need || in.ctx_len < full.ctx_need)
+    return fail(KAS_E_INVALID_ARG, "a descriptor offset reaches beyond the pool length given in kas_tables");
+  if ((full.cur_need > full.cur_lo && !in.have_cur) || (hc->all_rows && full.out_need > full.out_lo && !in.have_out) ||
+      (full.aux_need > full.aux_lo && !in.have_aux) || (full.ctx_need > full.ctx_lo && !in.have_ctx) || (T && !in.have_topic_results) ||
+      (S && !in.have_scenario_results))
+    return fail(KAS_E_INVALID_ARG, "a table the descriptors refer to is NULL");
+  hc->sel_off.clear();
+  if (!hc->all_rows) {
+    int64_t at = 0;
+    hc->sel_off.resize((size_t)in.n_select + 1);
+    for (int32_t k = 0; k < in.n_select; ++k) {
+      if (in.select[k] < 0 || in.select[k] >= S) return fail(KAS_E_INVALID_ARG, "select: scenario index out of range");
+      hc->sel_off[(size_t)k] = at;
+      const kas_scenario_desc& sd = b->scenarios[in.select[k]];
+      for (int32_t t = 0; t < sd.topic_count; ++t) {
+        const kas_topic_desc& td = b->topics[sd.topic_begin + t];
+        at += (int64_t)td.n_partitions * td.out_width;
+      }
+    }
+    hc->sel_off[(size_t)in.n_select] = at;
+    if (in.out_len < at || (at > 0 && !in.have_out))
+      return fail(KAS_E_INVALID_ARG, "select: out / out_len too small for the selected scenarios' rows");
+  }
+  hc->imp_base.clear();
+  if (in.impact) {
+    hc->imp_base.assign((size_t)S + 1, 0);
+    for (int64_t s = 0; s < S; ++s) hc->imp_base[(size_t)s + 1] = hc->imp_base[(size_t)s] + (b->scenarios[s].n_nodes > 0 ? b->scenarios[s].n_nodes : 0);
+    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes))
+      return fail(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
+  }
+  // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
+  const int64_t cell = in.cells16 ? 2 : 4;                     // bytes of a cur / out cell as it travels
+  const int64_t cur_cells = full.cur_need - full.cur_lo, out_cells = full.out_need - full.out_lo;
+  hc->K = kas_host_range_count(cell * (cur_cells + (hc->all_rows ? out_cells : 0)), S, in.ranges_override);
+  const uint32_t own = (1u << KAS_POOL_TOPICS) | (1u << KAS_POOL_CUR) | (1u << KAS_POOL_OUT);
+  if ((rc = kas_cut_ranges(b, hc->K, &full, &hc->ranges, err)) != KAS_E_OK) return rc;
+  if (hc->K > 1 && !kas_ranges_disjoint(hc->ranges, own, true)) {
+    hc->K = 1;
+    if ((rc = kas_cut_ranges(b, 1, &full, &hc->ranges, err)) != KAS_E_OK) return rc;
+  }
+  // device pools: only [lo, need) of each is ever touched (+ 8 cells: the fill kernel's full-row loads re-read the last row for
+  // lanes past the end); a 16-bit call solved on its own cells never touches the int32 pools
+  size_t* by = hc->bytes;
+  by[KAS_HB_CUR] = hc->need32 ? 4 * (size_t)(cur_cells + 8) : 0;
+  by[KAS_HB_OUT] = hc->need32 ? 4 * (size_t)(out_cells + 8) : 0;
+  by[KAS_HB_AUX] = 4 * (size_t)(full.aux_need - full.aux_lo + 8);
+  by[KAS_HB_CTX] = 4 * (size_t)(full.ctx_need - full.ctx_lo + 8);
+  by[KAS_HB_CUR16] = in.cells16 ? 2 * (size_t)(cur_cells + 8) : 0;
+  by[KAS_HB_OUT16] = in.cells16 ? 2 * (size_t)(out_cells + 8) : 0;
+  by[KAS_HB_TR] = by[KAS_HB_TR_PIN] = sizeof(kas_topic_result) * (size_t)(T + 1);
+  by[KAS_HB_SR] = by[KAS_HB_SR_PIN] = sizeof(kas_scenario_result) * (size_t)(S + 1);
+  by[KAS_HB_IMP_NODES] = in.impact ? sizeof(kas_node_impact) * (size_t)(hc->imp_base[(size_t)S] + 1) : 0;
+  by[KAS_HB_IMP_SCEN] = in.impact ? sizeof(kas_scenario_impact) * (size_t)(S + 1) : 0;
+  return KAS_E_OK;
+}
+
+// ---- the plan cache's pure half -------------------------------------------------------------------------------------------
+// word-at-a-time hash of the descriptor bytes (a what-if call hashes megabytes of node tables)
+// (four independent lanes over 32-byte blocks: one dependent multiply chain ran at ~4 GB/s and made the 8 MB of
+// descriptors and node tables of a 1000-variant what-if call cost 2 of its 5 ms)
+static inline uint64_t kas_hash64(uint64_t h, const void* data, size_t n) {
+  const unsigned char* p = (const unsigned char*)data;
+  const uint64_t M = 0x9E3779B97F4A7C15ull;
+  uint64_t a = h, b = h ^ 0x243F6A8885A308D3ull, c = h ^ 0x13198A2E03707344ull, d = h ^ 0xA4093822299F31D0ull;
+  size_t i = 0;
+  for (; i + 32 <= n; i += 32) {
+    uint64_t w[4];
+    memcpy(w, p + i, 32);
+    a = (a ^ w[0]) * M; a ^= a >> 29;
+    b = (b ^ w[1]) * M; b ^= b >> 29;
+    c = (c ^ w[2]) * M; c ^= c >> 29;
+    d = (d ^ w[3]) * M; d ^= d >> 29;
+  }
+  h = a;
+  h = (h ^ b) * M; h ^= h >> 29;
+  h = (h ^ c) * M; h ^= h >> 29;
+  h = (h ^ d) * M; h ^= h >> 29;
+  for (; i + 8 <= n; i += 8) {
+    uint64_t w;
+    memcpy(&w, p + i, 8);
+    h = (h ^ w) * M;
+    h ^= h >> 29;
+  }
+  for (; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
+  return h;
+}
+
+// What identifies a batch to the cache: (S, T, node pool length, cell width), scenario and topic descriptors, node tables — hashed
+// and compared where they lie; a copy is made only when a plan is built for them.
+struct KasBatchIdent {
+  int64_t hdr[2];
+  const void* seg[5];
+  size_t seg_bytes[5], total = 0;
+  uint64_t key = 0;             // every byte
+  uint64_t sig = 0;             // (S, T) + topic descriptors + the cell width: what-if variants of one snapshot share it, and a plan
+                                // for the other cell width is never the one rebuilt in place
+  KasBatchIdent(const kas_batch_desc* b, int cells16) {
+    const size_t nb = sizeof(int32_t) * (size_t)b->node_pool_len;
+    hdr[0] = ((int64_t)b->n_scenarios << 32) | (uint32_t)b->n_topics;
+    hdr[1] = b->node_pool_len | ((int64_t)(cells16 ? 1 : 0) << 62);   // (a plan for 16-bit cells is another plan)
+    const void* s[5] = {hdr, b->scenarios, b->topics, b->node_id, b->node_rack};
+    const size_t n[5] = {16, sizeof(kas_scenario_desc) * (size_t)b->n_scenarios, sizeof(kas_topic_desc) * (size_t)b->n_topics, nb, nb};
+    key = 0xcbf29ce484222325ull;
+    for (int i = 0; i < 5; ++i) {
+      seg[i] = s[i]; seg_bytes[i] = n[i]; total += n[i];
+      if (n[i]) key = kas_hash64(key, s[i], n[i]);
+    }
+    sig = kas_hash64(0x84222325cbf29ce4ull, hdr, 8) ^ kas_hash64(0, b->topics, n[2]) ^ (cells16 ? 0x5bd1e995c16c16c1ull : 0ull);
+  }
+  KasBatchIdent(const KasBatchIdent&) = delete;                 // (seg[0] points into the object)
+  bool same_bytes(const std::vector<unsigned char>& have) const {
+    if (have.size() != total) return false;
+    size_t off = 0;
+    for (int i = 0; i < 5; ++i) {
+      if (seg_bytes[i] && memcmp(have.data() + off, seg[i], seg_bytes[i]) != 0) return false;
+      off += seg_bytes[i];
+    }
+    return true;
+  }
+  void copy_to(std::vector<unsigned char>* to) const {
+    to->resize(total);
+    size_t off = 0;
+    for (int i = 0; i < 5; ++i) { if (seg_bytes[i]) memcpy(to->data() + off, seg[i], seg_bytes[i]); off += seg_bytes[i]; }
+  }
+};
+static inline bool kas_batch_ident_ok(const kas_batch_desc* b) {
+  return !(b->n_scenarios < 0 || b->n_topics < 0 || b->node_pool_len < 0 || (b->n_scenarios > 0 && !b->scenarios) ||
+           (b->n_topics > 0 && !b->topics) || (b->node_pool_len > 0 && (!b->node_id || !b->node_rack)));
+}
+
+// what the choice reads of a cache entry
+struct KasCacheEntry {
+  int32_t occupied = 0;
+  uint64_t key = 0, sig = 0;
+  uint64_t last_use = 0;
+  uint64_t call = 0;            // host call that last used the entry (its ranges must not evict each other)
+};
+// Which entry serves a batch with this key and signature.  hits: the occupied entries whose key is the batch's (bit i: entry i) —
+// the caller confirms one with the byte compare, lowest first, and a confirmed hit beats everything.  victim: where the plan is
+// built on a miss — the least recently used entry of the same signature rebuilt in place (a what-if caller: same snapshot, other
+// broker sets — every buffer is already large enough), else a free entry, else the least recently used entry of any shape; never an
+// entry this call already uses (the other scenario ranges of a split call).  -1: every entry is this call's.
+struct KasCacheChoice { uint32_t hits = 0; int32_t victim = -1; };
+static inline KasCacheChoice kas_cache_choose(const KasCacheEntry* e, int32_t n, uint64_t key, uint64_t sig, uint64_t this_call) {
+  KasCacheChoice c;
+  int32_t same = -1, empty = -1, lru = -1;
+  for (int32_t i = 0; i < n; ++i) {
+    if (!e[i].occupied) { if (empty < 0) empty = i; continue; }
+    if (e[i].key == key) c.hits |= 1u << i;
+    if (e[i].call == this_call) continue;
+    if (e[i].sig == sig && (same < 0 || e[i].last_use < e[same].last_use)) same = i;
+    if (lru < 0 || e[i].last_use < e[lru].last_use) lru = i;
+  }
+  c.victim = same >= 0 ? same : (empty >= 0 ? empty : lru);
+  return c;
+}

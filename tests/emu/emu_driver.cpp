@@ -10,6 +10,7 @@
 #include "emu/kas_wave.h"     // defines KAS_WAVE_H_ first, so the body's own #include "kas_wave.h" is a no-op
 #include "kas_solver_body.h"
 #include "kas_launch_plan.h"   // the launch resolver the product shares: which kernels, grids, LDS and launch words
+#include "kas_host_call.h"     // what a host call does, decided on the CPU: the planner the product's host path executes
 
 namespace kasw {
 
@@ -642,6 +643,79 @@ int kas_emu_spread_plan(const kas_batch_desc* b, int32_t* out) {
   out[3] = kas_fill_lds_layout(sh.n_max, sh.Wc, 1, sh.idmap_entries, sh.need_bsearch, 1).total;
   out[4] = (int32_t)(((int64_t)sh.max_partitions + 63) / 64);
   return rc;
+}
+
+// kas_plan_host_call for a batch + the kas_tables lengths + a selection, without running anything (tests/test_host_call.py).
+//   lens[4]     cur_len, out_len, aux_len, ctx_len
+//   missing     tables that are NULL: bit 0 cur, 1 out, 2 aux, 3 ctx, 4 topic_results, 5 scenario_results, 6 impact nodes, 7 impact scenarios
+//   head[12]    K, native16, need32, entries of sel_off, entries of imp_base, then the batch's cur / out / aux extents [lo, need) and ctx_lo
+//   ranges      [K][10] scenarios, topics, cur, out, ctx: lo and hi of each
+//   scen        the ranges' rebased scenario descriptors, one range after the other ([n_scenarios])
+//   bytes       [KAS_HB_COUNT] in KasHostBuf's order;  sel_off [n_select + 1];  imp_base [n_scenarios + 1] when `impact`
+// Returns the planner's code; its text in errbuf.
+extern "C" __attribute__((visibility("default")))
+int kas_emu_host_call(const kas_batch_desc* b, const int64_t* lens, unsigned missing, const int32_t* select, int32_t n_select, int cells16,
+                      int impact, int lane_order_ok, unsigned built, int ranges_override, int64_t* head, int64_t* ranges,
+                      kas_scenario_desc* scen, int64_t* bytes, int64_t* sel_off, int64_t* imp_base, char* errbuf, int errlen) {
+  std::vector<int32_t> ident_ids;
+  uint64_t ident_stamp = 0;
+  KasHostCallIn in;
+  in.batch = b;
+  in.cur_len = lens[0]; in.out_len = lens[1]; in.aux_len = lens[2]; in.ctx_len = lens[3];
+  in.have_cur = !(missing & 1u); in.have_out = !(missing & 2u); in.have_aux = !(missing & 4u); in.have_ctx = !(missing & 8u);
+  in.have_topic_results = !(missing & 16u); in.have_scenario_results = !(missing & 32u);
+  in.select = select; in.n_select = n_select;
+  in.cells16 = cells16 != 0; in.ident_ids = &ident_ids; in.ident_stamp = &ident_stamp;
+  in.impact = impact != 0; in.have_imp_nodes = !(missing & 64u); in.have_imp_scenarios = !(missing & 128u);
+  in.lane_order_ok = lane_order_ok;
+  for (uint32_t& m : in.built16) m = built;
+  in.ranges_override = ranges_override;
+  KasHostCall hc;
+  std::string err;
+  const int rc = kas_plan_host_call(in, &hc, &err);
+  if (errbuf && errlen > 0) { strncpy(errbuf, err.c_str(), (size_t)errlen - 1); errbuf[errlen - 1] = 0; }
+  if (rc != KAS_E_OK) return rc;
+  const KasShape& f = hc.full;
+  const int64_t h[12] = {hc.K, hc.native16, hc.need32, (int64_t)hc.sel_off.size(), (int64_t)hc.imp_base.size(),
+                         f.cur_lo, f.cur_need, f.out_lo, f.out_need, f.aux_lo, f.aux_need, f.ctx_lo};
+  memcpy(head, h, sizeof(h));
+  for (const KasHostRange& r : hc.ranges) {
+    *ranges++ = r.lo; *ranges++ = r.hi;
+    for (const KasExtent& e : r.own) { *ranges++ = e.lo; *ranges++ = e.hi; }
+    for (int64_t i = 0; i < r.hi - r.lo; ++i) *scen++ = r.scen[(size_t)i];
+  }
+  for (int i = 0; i < KAS_HB_COUNT; ++i) bytes[i] = (int64_t)hc.bytes[i];
+  for (size_t i = 0; i < hc.sel_off.size(); ++i) sel_off[i] = hc.sel_off[i];
+  for (size_t i = 0; i < hc.imp_base.size(); ++i) imp_base[i] = hc.imp_base[i];
+  return rc;
+}
+
+// kas_cache_choose over a table of n entries of {occupied, key, sig, last_use, call}: the lowest candidate hit (confirmed by the
+// byte compare in the library) in *hit, or -1; the victim of a miss in *victim, or -1 (the library's KAS_E_NOMEM)
+extern "C" __attribute__((visibility("default")))
+void kas_emu_cache_choose(const uint64_t* entries, int32_t n, uint64_t key, uint64_t sig, uint64_t this_call, int32_t* hit, int32_t* victim) {
+  std::vector<KasCacheEntry> e((size_t)n);
+  for (int32_t i = 0; i < n; ++i) e[(size_t)i] = KasCacheEntry{(int32_t)entries[5 * i], entries[5 * i + 1], entries[5 * i + 2], entries[5 * i + 3], entries[5 * i + 4]};
+  const KasCacheChoice c = kas_cache_choose(e.data(), n, key, sig, this_call);
+  *hit = c.hits ? __builtin_ctz(c.hits) : -1;
+  *victim = c.victim;
+}
+
+// the slicing arithmetic behind the library's kas_shard_range / kas_batch_slice and the cache's key and signature of a batch
+extern "C" __attribute__((visibility("default")))
+void kas_emu_shard_range(int64_t total, int32_t rank, int32_t world, int64_t* lo, int64_t* hi) { kas_range_of(total, rank, world, lo, hi); }
+extern "C" __attribute__((visibility("default")))
+int kas_emu_batch_slice(const kas_batch_desc* b, int64_t lo, int64_t hi, kas_scenario_desc* scratch, kas_batch_desc* out, const kas_tables* tables,
+                        kas_tables* tables_out, char* errbuf, int errlen) {
+  std::string err;
+  const int rc = kas_slice_batch(b, lo, hi, scratch, out, tables, tables_out, &err);
+  if (errbuf && errlen > 0) { strncpy(errbuf, err.c_str(), (size_t)errlen - 1); errbuf[errlen - 1] = 0; }
+  return rc;
+}
+extern "C" __attribute__((visibility("default")))
+void kas_emu_batch_ident(const kas_batch_desc* b, int cells16, uint64_t* key_sig) {
+  const KasBatchIdent id(b, cells16);
+  key_sig[0] = id.key; key_sig[1] = id.sig;
 }
 
 extern "C" __attribute__((visibility("default")))

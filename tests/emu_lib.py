@@ -397,3 +397,109 @@ def spread_plan(fb: FlatBatch):
     out = (C.c_int32 * 5)()
     rc = L.kas_emu_spread_plan(C.byref(bd), out)
     return rc, dict(zip(("chunks", "lds_a", "lds_b", "lds_full", "tiles"), list(out)))
+
+
+# ---- the host call planner (csrc/kas_host_call.h), nothing is run ----------------------------------------------------
+HOST_BUFS = ("cur", "out", "aux", "ctx", "cur16", "out16", "tr", "sr", "tr_pin", "sr_pin", "imp_nodes", "imp_scen")   # KasHostBuf
+HOST_STREAMS = 8           # KAS_HOST_STREAMS
+MISSING = {"cur": 1, "out": 2, "aux": 4, "ctx": 8, "topic_results": 16, "scenario_results": 32, "imp_nodes": 64, "imp_scenarios": 128}
+BUILT_ALL, BUILT_RELAX = 63, 1
+
+
+def host_call(fb: FlatBatch, lens=None, missing=(), select=None, cells16=False, impact=False, lane_order_ok=True,
+              built=BUILT_ALL, ranges_override=0):
+    """kas_plan_host_call for a batch as kas_solve_host* would be handed it: `lens` the kas_tables lengths (cur, out, aux, ctx; default:
+    the FlatBatch's own), `missing` the tables that are NULL (keys of MISSING), `select` the scenario indices of a *_select call.
+    (return code, plan, error text); plan: K, native16, need32, full (the batch's cur / out / aux extents), ranges (one dict of
+    (lo, hi) pairs per range + its rebased scenario descriptors), bytes by buffer name, sel_off, imp_base."""
+    import numpy as np
+    L = lib()
+    L.kas_emu_host_call.restype = C.c_int
+    L.kas_emu_host_call.argtypes = [C.POINTER(abi.BatchDesc), C.POINTER(C.c_int64), C.c_uint, C.POINTER(C.c_int32), C.c_int32, C.c_int, C.c_int,
+                                    C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
+    bd = batch_desc(fb)
+    S = fb.n_scenarios
+    lens = (int(fb.cur.shape[0]), int(fb.out_len), int(fb.aux.shape[0]), int(fb.ctx.shape[0])) if lens is None else lens
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    head = (C.c_int64 * 12)()
+    ranges = (C.c_int64 * (10 * HOST_STREAMS))()
+    scen = np.zeros(S + 1, dtype=abi.SCENARIO_DESC_DTYPE)
+    nbytes = (C.c_int64 * len(HOST_BUFS))()
+    sel_off = (C.c_int64 * ((0 if sel is None else len(sel)) + 1))()
+    imp_base = (C.c_int64 * (S + 1))()
+    err = C.create_string_buffer(512)
+    rc = L.kas_emu_host_call(C.byref(bd), (C.c_int64 * 4)(*lens), sum(MISSING[m] for m in missing),
+                             None if sel is None or not len(sel) else sel.ctypes.data_as(C.POINTER(C.c_int32)), -1 if sel is None else len(sel),
+                             int(cells16), int(impact), int(lane_order_ok), built, ranges_override, head, ranges, scen.ctypes.data,
+                             nbytes, sel_off, imp_base, err, 512)
+    if rc != 0:
+        return rc, None, err.value.decode()
+    K = int(head[0])
+    names = ("scenarios", "topics", "cur", "out", "ctx")
+    rs = [dict(zip(names, [(int(ranges[10 * i + 2 * j]), int(ranges[10 * i + 2 * j + 1])) for j in range(5)])) for i in range(K)]
+    for r in rs:
+        r["scen"] = scen[r["scenarios"][0]:r["scenarios"][1]].copy()
+    plan = dict(K=K, native16=bool(head[1]), need32=bool(head[2]), ranges=rs, bytes=dict(zip(HOST_BUFS, [int(v) for v in nbytes])),
+                full=dict(cur=(int(head[5]), int(head[6])), out=(int(head[7]), int(head[8])), aux=(int(head[9]), int(head[10]))),
+                sel_off=[int(v) for v in sel_off[:int(head[3])]], imp_base=[int(v) for v in imp_base[:int(head[4])]])
+    return rc, plan, ""
+
+
+def cache_choose(entries, key: int, sig: int, this_call: int):
+    """kas_cache_choose over entries of (occupied, key, sig, last_use, call): (lowest candidate hit or -1, victim of a miss or -1)"""
+    L = lib()
+    L.kas_emu_cache_choose.restype = None
+    L.kas_emu_cache_choose.argtypes = [C.POINTER(C.c_uint64), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    flat = (C.c_uint64 * (5 * len(entries)))(*[int(v) for e in entries for v in e])
+    hit, victim = C.c_int32(), C.c_int32()
+    L.kas_emu_cache_choose(flat, len(entries), key, sig, this_call, C.byref(hit), C.byref(victim))
+    return hit.value, victim.value
+
+
+def batch_ident(fb: FlatBatch, cells16: bool = False):
+    """(key, signature) of a batch in the host path's plan cache"""
+    L = lib()
+    L.kas_emu_batch_ident.restype = None
+    L.kas_emu_batch_ident.argtypes = [C.POINTER(abi.BatchDesc), C.c_int, C.POINTER(C.c_uint64)]
+    bd = batch_desc(fb)
+    out = (C.c_uint64 * 2)()
+    L.kas_emu_batch_ident(C.byref(bd), int(cells16), out)
+    return int(out[0]), int(out[1])
+
+
+def shard_range(total: int, rank: int, world: int, fn=None):
+    """the header's kas_shard_range (fn: the same call on another library's export)"""
+    fn = fn or lib().kas_emu_shard_range
+    fn.restype = None
+    lo, hi = C.c_int64(), C.c_int64()
+    fn(C.c_int64(total), C.c_int32(rank), C.c_int32(world), C.byref(lo), C.byref(hi))
+    return lo.value, hi.value
+
+
+def batch_slice(fb: FlatBatch, lo: int, hi: int, fn=None):
+    """the header's kas_batch_slice on a batch and its host tables (fn: the library's exported kas_batch_slice instead).  (return code,
+    what the slice is: sizes, where its topics / node tables / result records begin, the rebased scenario descriptors)"""
+    import numpy as np
+    bd = batch_desc(fb)
+    t, ho = host_tables(fb)
+    out, tout = abi.BatchDesc(), abi.Tables()
+    scratch = np.zeros(max(hi - lo, 1), dtype=abi.SCENARIO_DESC_DTYPE)
+    args = [C.byref(bd), C.c_int64(lo), C.c_int64(hi), C.cast(scratch.ctypes.data, C.POINTER(abi.ScenarioDesc)), C.byref(out), C.byref(t), C.byref(tout)]
+    if fn is None:
+        fn = lib().kas_emu_batch_slice
+        args += [C.create_string_buffer(256), C.c_int(256)]
+    fn.restype = C.c_int
+    rc = fn(*args)
+    if rc != 0:
+        return rc, None
+
+    def at(p, base, size):
+        return None if not p else (C.cast(p, C.c_void_p).value - base) // size
+    return rc, dict(n_scenarios=out.n_scenarios, n_topics=out.n_topics, node_pool_len=out.node_pool_len,
+                    topic=at(out.topics, fb.topics.ctypes.data, abi.TOPIC_DESC_DTYPE.itemsize), node_id=at(out.node_id, fb.node_id.ctypes.data, 4),
+                    node_rack=at(out.node_rack, fb.node_rack.ctypes.data, 4),
+                    topic_results=at(tout.topic_results, ho.topic_results.ctypes.data, abi.TOPIC_RESULT_DTYPE.itemsize),
+                    scenario_results=at(tout.scenario_results, ho.scenario_results.ctypes.data, abi.SCENARIO_RESULT_DTYPE.itemsize),
+                    pools=(tout.cur == t.cur, tout.out == t.out, tout.cur_len, tout.out_len),
+                    scen=scratch[:hi - lo].tobytes())
