@@ -44,10 +44,11 @@
 //
 // Tiles whose 64 rows all hold three brokers in rows of the batch's width take the straight-line evaluation above;
 // any other tile (the last tile of a topic, rows with fewer holders after a reduced replication factor, topics
-// narrower than the batch) takes the same loop with per-lane list lengths.  The DUAL instance solves two usual tiles
-// in a row as one tile of 128 rows (two rows per lane, six pair instructions): fewer LDS round trips per scenario,
-// more LDS operations per row, 91 instead of 59 vector registers — for launches that do not fill the GPU
-// (kas_relax_double_tiles).  HBM: mid rows in (8 B per row, read two tiles ahead), final rows out (12 B), broker ids
+// narrower than the batch) takes the same loop with per-lane list lengths.  The straight-line evaluation is ONE step body
+// (usual_step in order_relax) over NR rows per lane: NR consecutive usual tiles are one tile of 64 NR rows, 3 NR pair
+// instructions.  NR = 1 everywhere; the DUAL instance first tries NR = 2 (128 rows: fewer LDS round trips per scenario,
+// more LDS operations per row, 91 instead of 59 vector registers — for launches that do not fill the GPU,
+// kas_relax_double_tiles), the QUAD instance NR = 4, and either falls back to ONE tile where that many do not fit.  HBM: mid rows in (8 B per row, read two tiles ahead), final rows out (12 B), broker ids
 // from the L2-resident node table.
 //
 // Applicable (KasShape::relax_ok) to lists <= 3 wide with no topic hash of Integer.MIN_VALUE and fewer than 65535
@@ -126,31 +127,46 @@ KAS_DEV int32_t relax_eval_generic(const uint32_t (&x)[3], const bool (&valid)[3
   return w0 | (w1 << 2);
 }
 
-// One relaxation step of a tile, as the pair lanes see it: the rows' words are in rbuf; take the previous additions
-// back, add the pairs in row-major order (NP instructions, lanes ascending), put what each add returned into the
-// pair's staging word.  Afterwards every row lane finds in stage[3 i + c] the counter word of its cell c as its row
-// would see it with the current outcomes of all earlier rows of the tile committed.
+// The exchange of one relaxation step, as the pair lanes run it in both relaxation forms (Word: the counter word, uint32_t
+// here, uint64_t in kas_order_relax_wide.h): take the previous addends back, add the new ones in pair order — NP instructions,
+// each a lockstep of its own: one instruction at a time and its lanes in ascending order is the order the hardware serves,
+// and the only one the form's prefix over rows may rest on (kas_wave.h, lds_add_rtn_u32) —, and put what each add returned
+// into the pair's staging word slot[64 t].
+template <int NP, class Word>
+KAS_DEV void relax_exchange(Word* slot, Word* const (&padr)[NP], Word (&padd)[NP], const Word (&nadd)[NP], bool undo) {
+  constexpr bool WORD64 = sizeof(Word) == 8;
+  if (undo) {                                                // (wave-uniform)
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      if constexpr (WORD64) kasw::lds_sub_u64(padr[t], padd[t]);
+      else kasw::lds_sub_u32(padr[t], padd[t]);
+    }
+  }
+  kasw::lockstep();
+  Word got[NP];
+#pragma unroll
+  for (int t = 0; t < NP; ++t) {
+    if constexpr (WORD64) got[t] = kasw::lds_add_rtn_u64(padr[t], nadd[t]);
+    else got[t] = kasw::lds_add_rtn_u32(padr[t], nadd[t]);
+    kasw::lockstep();
+    padd[t] = nadd[t];
+  }
+#pragma unroll
+  for (int t = 0; t < NP; ++t) slot[64 * t] = got[t];
+  kasw::lockstep();
+}
+
+// One relaxation step of a tile, as the pair lanes see it: the rows' words are in rbuf; every pair's addend is its cell's
+// bits of its row's word, and the exchange puts what each add returned into the pair's staging word.  Afterwards every row
+// lane finds in stage[3 i + c] the counter word of its cell c as its row would see it with the current outcomes of all
+// earlier rows of the tile committed.
 template <int NP>
-KAS_DEV void relax_pairs(const RelaxPairs& pp, uint32_t* const (&padr)[KAS_RELAX_MAXP], uint32_t (&padd)[KAS_RELAX_MAXP], bool undo) {
+KAS_DEV void relax_pairs(const RelaxPairs& pp, uint32_t* const (&padr)[NP], uint32_t (&padd)[NP], bool undo) {
   kasw::lockstep();                                          // the row words are written
   uint32_t nadd[NP];
 #pragma unroll
   for (int t = 0; t < NP; ++t) nadd[t] = (*pp.row[t] >> pp.cell[t]) & KAS_RELAX_PICK_BITS;
-  if (undo) {                                                // (wave-uniform)
-#pragma unroll
-    for (int t = 0; t < NP; ++t) kasw::lds_sub_u32(padr[t], padd[t]);
-  }
-  kasw::lockstep();
-  uint32_t got[NP];
-#pragma unroll
-  for (int t = 0; t < NP; ++t) {
-    got[t] = kasw::lds_add_rtn_u32(padr[t], nadd[t]);
-    kasw::lockstep();                                        // (one instruction at a time, lanes in order: the hardware's order)
-    padd[t] = nadd[t];
-  }
-#pragma unroll
-  for (int t = 0; t < NP; ++t) pp.slot[64 * t] = got[t];
-  kasw::lockstep();
+  relax_exchange<NP, uint32_t>(pp.slot, padr, padd, nadd, undo);
 }
 
 // The six tags of a row whose three cells all hold a broker, from the order of its cells (tagtab, per topic).
@@ -369,7 +385,7 @@ KAS_DEV uint64_t relax_verify_rows(uint32_t* cnt, uint32_t w0_cells, uint32_t w1
 // ONE aligned dword — its holders in ascending order — instead of a dword and a halfword at 2-byte alignment, and because the
 // cells are sorted a row's six tags are the topic's constants: no comparison of the cells, no tag table read.
 // QUAD (round 6, with DUAL and M32): FOUR usual tiles in a row as one tile of 256 rows (four rows per lane, twelve pair
-// instructions) — the same fixed point once more: fewer, longer steps for a launch whose latency is one scenario's chain.
+// instructions) — the same step body at NR = 4: fewer, longer steps for a launch whose latency is one scenario's chain.
 template <int W, bool DUAL, bool CTX, bool VERIFY = false, bool C16 = false, bool IDL = false, bool FS = false, bool M32 = false, bool QUAD = false>
 KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, uint64_t* fs = nullptr) {
   static_assert(W == 2 || W == 3, "counter words hold the counts of lists up to 3 wide");
@@ -554,10 +570,11 @@ KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, 
 #pragma unroll
           for (int q = 0; q < 3; ++q) c[q] = q < W ? (ra.w[q] & 0xffffu) : KAS_MID_NONE;
         }
-        // the usual tile: 64 rows, three holders each, rows of the batch's width
+        // The usual tile: every row holds three brokers, in rows of the batch's width.  NR tiles of 64 rows in a row are
+        // settled as ONE tile of 64 NR rows — lane i evaluates rows i, 64 + i, .. (3 NR pair instructions, row-major): the
+        // same fixed point, more work per LDS round trip.  NR is what the instance may take (1, 2 — DUAL — or 4 — QUAD) or 1.
+        // false: a row of the tiles behind the first is short — nothing has been touched, the step goes on with one tile.
         bool fast = false;
-        uint32_t* padr[KAS_RELAX_MAXP];
-        uint32_t padd[KAS_RELAX_MAXP] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // what my pairs added last
         int32_t step = 1;                                      // tiles this step takes (wave-uniform)
         int32_t req_n = 0;                                     // rows per lane whose final rows this step asks the ids for
         uint32_t req_l[NB][3];                                 // ... their lists as node indices
@@ -565,208 +582,160 @@ KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, 
         for (int b = 0; b < NB; ++b)
 #pragma unroll
           for (int q = 0; q < 3; ++q) req_l[b][q] = 0u;
+        auto usual_step = [&](auto nr_tag) -> bool {
+          constexpr int NR = decltype(nr_tag)::value, NP = 3 * NR;
+          MidRaw<W> rv[NR];
+          uint32_t cc[NR][3];
+          rv[0] = ra;
+#pragma unroll
+          for (int q = 0; q < 3; ++q) cc[0][q] = c[q];
+          bool short_row = false;
+#pragma unroll
+          for (int b = 1; b < NR; ++b) {
+            rv[b] = mid_view<W, FULLW, M32>(raw[b], ow);
+            cc[b][0] = rv[b].w[0] & 0xffffu; cc[b][1] = rv[b].w[0] >> 16; cc[b][2] = rv[b].w[1] & 0xffffu;
+            short_row = short_row || (M32 ? cc[b][2] >= NONE_FROM : ((cc[b][0] | cc[b][1] | cc[b][2]) & 0x8000u) != 0u);
+          }
+          if constexpr (NR > 1) {
+            if (kasw::ballot(short_row) != 0ull) return false;
+          }
+          n_tiles += NR;
+          // ---- hand the cells to the pair lanes
+          kasw::lockstep();                                    // (the previous tile's words have been read)
+#pragma unroll
+          for (int b = 0; b < NR; ++b)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) mine[192 * b + q] = cc[b][q];
+          kasw::lockstep();
+          uint32_t* padr[NP];
+          uint32_t padd[NP];                                   // what my pairs added last
+#pragma unroll
+          for (int t = 0; t < NP; ++t) { padr[t] = cnt + pp.slot[64 * t]; padd[t] = 0u; }
+          // my rows' six tags from the order of their cells; counter words of my cells as the previous tile left them
+          RelaxTags g[NR];
+          uint32_t x[NR][3];
+#pragma unroll
+          for (int b = 0; b < NR; ++b) g[b] = KAS_M32_SORTED_TAGS(M32) ? gsorted : relax_tags(cc[b], tagtab);
+#pragma unroll
+          for (int b = 0; b < NR; ++b)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) x[b][q] = cnt[cc[b][q]];
+          kasw::lockstep();
+          int32_t prev[NR];
+#pragma unroll
+          for (int b = 0; b < NR; ++b) prev[b] = -1;
+#pragma nounroll                                             // (two evaluations in flight keep two sets of addends alive: 71 registers for 67)
+          for (int32_t it = 0;; ++it) {
+            n_evals += NR;
+            // (row i of the tile is right after evaluation i + 1, so 64 NR + 1 evaluations always suffice: more means the LDS
+            // did not hand the additions out in lane order — give up with a status instead of looping)
+            if (it > 64 * NR + 2) { stuck = true; break; }
+            int32_t oc[NR];
+            bool moved = false;
+#pragma unroll
+            for (int b = 0; b < NR; ++b) { oc[b] = relax_eval3(x[b], g[b]); moved = moved || oc[b] != prev[b]; }
+            if (kasw::ballot(moved) == 0ull) break;            // nobody's outcome moved: the words hold the tile's commits
+#pragma unroll
+            for (int b = 0; b < NR; ++b) rbuf[64 * b + lane] = relax_row_word((uint32_t)oc[b] & 3u, (uint32_t)oc[b] >> 2);
+            relax_pairs<NP>(pp, padr, padd, it > 0);
+#pragma unroll
+            for (int b = 0; b < NR; ++b) {
+#pragma unroll
+              for (int q = 0; q < 3; ++q) x[b][q] = mine[192 * b + q];
+              prev[b] = oc[b];
+            }
+          }
+          rows1 += 64u * NR; rows2 += 64u * NR;
+          if constexpr (VERIFY) {
+            bool sampled = false;                              // (wave-uniform)
+#pragma unroll
+            for (int b = 0; b < NR; ++b) sampled = sampled || (vstride > 0 && ((tile + b) % vstride) == voff);
+            if (sampled) {
+              n_verified += NR;
+#pragma unroll
+              for (int t = 0; t < NP; ++t) kasw::lds_sub_u32(padr[t], padd[t]);
+              kasw::lockstep();
+#pragma unroll
+              for (int b = 0; b < NR; ++b)
+                if (relax_verify_rows(cnt, rv[b].w[0], rv[b].w[1], tagtab, prev[b]) != 0ull) unsound = true;
+            }
+          }
+          // ---- the final rows: their lists as node indices now, broker ids and the stores one step later
+#pragma unroll
+          for (int b = 0; b < NR; ++b) relax_list3(rv[b], prev[b] < 0 ? 4 : prev[b], req_l[b], cnt2);
+          req_n = NR;
+          step = NR;
+          return true;
+        };
+        bool settled = false;
         if constexpr (W == 3) {
           if (FULLW && ((tile + 1) << 6) <= P)
             fast = M32 ? kasw::ballot(c[2] >= NONE_FROM) == 0ull      // (sorted: a row holds three brokers iff its last cell does)
                        : kasw::ballot(((c[0] | c[1] | c[2]) & 0x8000u) != 0u) == 0ull;
-          // ---- four usual tiles in a row: one quad tile of 256 rows, lane i evaluates rows i, 64 + i, 128 + i, 192 + i (twelve
-          // pair instructions, row-major); anything else falls through to a single tile
-          if constexpr (QUAD) if (fast && ((tile + 4) << 6) <= P) {
-            MidRaw<W> rv[4];
-            uint32_t cc[4][3];
-            rv[0] = ra;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) cc[0][q] = c[q];
-            bool short_row = false;
-#pragma unroll
-            for (int b = 1; b < 4; ++b) {
-              rv[b] = mid_view<W, FULLW, M32>(raw[b], ow);
-              cc[b][0] = rv[b].w[0] & 0xffffu; cc[b][1] = rv[b].w[0] >> 16; cc[b][2] = rv[b].w[1] & 0xffffu;
-              short_row = short_row || cc[b][2] >= NONE_FROM;
-            }
-            if (kasw::ballot(short_row) == 0ull) {
-              n_tiles += 4;
-              kasw::lockstep();                                // (the previous tile's words have been read)
-#pragma unroll
-              for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) mine[192 * b + q] = cc[b][q];
-              kasw::lockstep();
-#pragma unroll
-              for (int t = 0; t < 12; ++t) padr[t] = cnt + pp.slot[64 * t];
-              uint32_t xq[4][3];
-#pragma unroll
-              for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) xq[b][q] = cnt[cc[b][q]];
-              kasw::lockstep();
-              int32_t pq[4] = {-1, -1, -1, -1};
-              for (int32_t it = 0;; ++it) {
-                n_evals += 4;
-                if (it > 258) { stuck = true; break; }         // (row i is right after evaluation i + 1: 257 suffice)
-                int32_t oq[4];
-                bool moved = false;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) { oq[b] = relax_eval3(xq[b], gsorted); moved = moved || oq[b] != pq[b]; }
-                if (kasw::ballot(moved) == 0ull) break;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) rbuf[64 * b + lane] = relax_row_word((uint32_t)oq[b] & 3u, (uint32_t)oq[b] >> 2);
-                relax_pairs<12>(pp, padr, padd, it > 0);
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-#pragma unroll
-                  for (int q = 0; q < 3; ++q) xq[b][q] = mine[192 * b + q];
-                  pq[b] = oq[b];
-                }
-              }
-              rows1 += 256u; rows2 += 256u;
-#pragma unroll
-              for (int b = 0; b < 4; ++b) relax_list3(rv[b], pq[b] < 0 ? 4 : pq[b], req_l[b], cnt2);
-              req_n = 4;
-              step = 4;
-            }
+          if constexpr (NBT > 1) {
+            if (fast && ((tile + NBT) << 6) <= P) settled = usual_step(std::integral_constant<int, NBT>{});
           }
-          // ---- two usual tiles in a row: one double tile of 128 rows, lane i evaluates rows i and 64 + i.  The same
-          // fixed point (row-major pairs over six instructions), twice the work per LDS round trip.
-          if constexpr (DUAL && !QUAD) if (fast && ((tile + 2) << 6) <= P) {
-            const MidRaw<W> rb = mid_view<W, FULLW, M32>(raw[NB - 1], ow);
-            const uint32_t cb[3] = {rb.w[0] & 0xffffu, rb.w[0] >> 16, rb.w[1] & 0xffffu};
-            if ((M32 ? kasw::ballot(cb[2] >= NONE_FROM) : kasw::ballot(((cb[0] | cb[1] | cb[2]) & 0x8000u) != 0u)) == 0ull) {
-              n_tiles += 2;
-              kasw::lockstep();                                // (the previous tile's words have been read)
-#pragma unroll
-              for (int q = 0; q < 3; ++q) { mine[q] = c[q]; mine[192 + q] = cb[q]; }
-              kasw::lockstep();
-#pragma unroll
-              for (int t = 0; t < 6; ++t) padr[t] = cnt + pp.slot[64 * t];
-              uint32_t xa[3] = {cnt[c[0]], cnt[c[1]], cnt[c[2]]};
-              uint32_t xb[3] = {cnt[cb[0]], cnt[cb[1]], cnt[cb[2]]};
-              const RelaxTags ga = KAS_M32_SORTED_TAGS(M32) ? gsorted : relax_tags(c, tagtab), gb = KAS_M32_SORTED_TAGS(M32) ? gsorted : relax_tags(cb, tagtab);
-              kasw::lockstep();
-              int32_t pa = -1, pb = -1;
-              for (int32_t it = 0;; ++it) {
-                n_evals += 2;
-                if (it > 130) { stuck = true; break; }         // (row i is right after evaluation i + 1: 129 suffice)
-                const int32_t oa = relax_eval3(xa, ga), ob = relax_eval3(xb, gb);
-                if (kasw::ballot(oa != pa || ob != pb) == 0ull) break;
-                rbuf[lane] = relax_row_word((uint32_t)oa & 3u, (uint32_t)oa >> 2);
-                rbuf[64 + lane] = relax_row_word((uint32_t)ob & 3u, (uint32_t)ob >> 2);
-                relax_pairs<6>(pp, padr, padd, it > 0);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) { xa[q] = mine[q]; xb[q] = mine[192 + q]; }
-                pa = oa; pb = ob;
-              }
-              rows1 += 128u; rows2 += 128u;
-              if (VERIFY && vstride > 0 && ((tile % vstride) == voff || ((tile + 1) % vstride) == voff)) {   // (wave-uniform)
-                n_verified += 2;
-#pragma unroll
-                for (int t = 0; t < 6; ++t) kasw::lds_sub_u32(padr[t], padd[t]);
-                kasw::lockstep();
-                if (relax_verify_rows(cnt, ra.w[0], ra.w[1], tagtab, pa) != 0ull) unsound = true;
-                if (relax_verify_rows(cnt, rb.w[0], rb.w[1], tagtab, pb) != 0ull) unsound = true;
-              }
-              relax_list3(ra, pa < 0 ? 4 : pa, req_l[0], cnt2);
-              relax_list3(rb, pb < 0 ? 4 : pb, req_l[NB - 1], cnt2);
-              req_n = 2;
-              step = 2;
-            }
-          }
+          if (!settled && fast) settled = usual_step(std::integral_constant<int, 1>{});
         }
-        if (step == 1) {
+        if (!settled) {
+          // ---- any other tile: per-lane list lengths
           n_tiles += 1;
-          // ---- hand the cells to the pair lanes
+          n_slow += 1;
           kasw::lockstep();                                    // (the previous tile's words have been read)
 #pragma unroll
           for (int q = 0; q < 3; ++q) mine[q] = c[q];
           kasw::lockstep();
-          bool usual = false;
-          if constexpr (W == 3) usual = fast;
-          if (usual) {
-            if constexpr (W == 3) {
+          if constexpr (M32) {                                // ("no holder" as the code below knows it)
 #pragma unroll
-              for (int t = 0; t < 3; ++t) padr[t] = cnt + pp.slot[64 * t];
-              // counter words of my cells as the previous tile left them
-              uint32_t x[3] = {cnt[c[0]], cnt[c[1]], cnt[c[2]]};
-              const RelaxTags g = KAS_M32_SORTED_TAGS(M32) ? gsorted : relax_tags(c, tagtab);   // my row's six tags from the order of its cells
-              kasw::lockstep();
-              int32_t oc_prev = -1;
-              for (int32_t it = 0;; ++it) {
-                n_evals += 1;
-                // (lane i is right after evaluation i + 1, so 65 evaluations always suffice: more means the LDS did not
-                // hand the additions out in lane order — give up with a status instead of looping)
-                if (it > 66) { stuck = true; break; }
-                const int32_t oc = relax_eval3(x, g);
-                if (kasw::ballot(oc != oc_prev) == 0ull) break;  // nobody's outcome moved: the words hold the tile's commits
-                rbuf[lane] = relax_row_word((uint32_t)oc & 3u, (uint32_t)oc >> 2);
-                relax_pairs<3>(pp, padr, padd, it > 0);
-                x[0] = mine[0]; x[1] = mine[1]; x[2] = mine[2];
-                oc_prev = oc;
-              }
-              rows1 += 64u; rows2 += 64u;
-              if (VERIFY && vstride > 0 && (tile % vstride) == voff) {     // (wave-uniform)
-                n_verified += 1;
+            for (int q = 0; q < 3; ++q) c[q] = c[q] >= NONE_FROM ? KAS_MID_NONE : c[q];
+          }
+          uint32_t* padr[3];
+          uint32_t padd[3] = {0u, 0u, 0u};                     // what my pairs added last
 #pragma unroll
-                for (int t = 0; t < 3; ++t) kasw::lds_sub_u32(padr[t], padd[t]);
-                kasw::lockstep();
-                if (relax_verify_rows(cnt, ra.w[0], ra.w[1], tagtab, oc_prev) != 0ull) unsound = true;
-              }
-              // ---- the final row: its list as node indices now, broker ids and the store one step later
-              relax_list3(ra, oc_prev < 0 ? 4 : oc_prev, req_l[0], cnt2);
-              req_n = 1;
-            }
-          } else {
-            // ---- any other tile: per-lane list lengths
-            n_slow += 1;
-            if constexpr (M32) {                              // ("no holder" as the code below knows it)
+          for (int t = 0; t < 3; ++t) {
+            const uint32_t n = pp.slot[64 * t];
+            padr[t] = cnt + (n < (uint32_t)nmax ? n : (uint32_t)nmax);   // no holder: the padding node, and + 0
+          }
+          uint32_t x[3];
 #pragma unroll
-              for (int q = 0; q < 3; ++q) c[q] = c[q] >= NONE_FROM ? KAS_MID_NONE : c[q];
-            }
+          for (int q = 0; q < 3; ++q) x[q] = cnt[c[q] < (uint32_t)nmax ? c[q] : (uint32_t)nmax];
+          kasw::lockstep();
+          bool valid[3];
+          int32_t rank[3], Lp = 0;
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-              const uint32_t n = pp.slot[64 * t];
-              padr[t] = cnt + (n < (uint32_t)nmax ? n : (uint32_t)nmax);   // no holder: the padding node, and + 0
-            }
-            uint32_t x[3];
+          for (int q = 0; q < 3; ++q) { valid[q] = active && (c[q] & 0x8000u) == 0u; Lp += valid[q] ? 1 : 0; }
 #pragma unroll
-            for (int q = 0; q < 3; ++q) x[q] = cnt[c[q] < (uint32_t)nmax ? c[q] : (uint32_t)nmax];
-            kasw::lockstep();
-            bool valid[3];
-            int32_t rank[3], Lp = 0;
+          for (int q = 0; q < 3; ++q) {
+            rank[q] = 0;
 #pragma unroll
-            for (int q = 0; q < 3; ++q) { valid[q] = active && (c[q] & 0x8000u) == 0u; Lp += valid[q] ? 1 : 0; }
+            for (int j = 0; j < 3; ++j) rank[q] += (j != q && valid[j] && c[j] < c[q]) ? 1 : 0;
+          }
+          rows1 += (uint32_t)kasw::popc(kasw::ballot(Lp >= 1)); rows2 += (uint32_t)kasw::popc(kasw::ballot(Lp >= 2));
+          int32_t oc_prev = -1;
+          for (int32_t it = 0;; ++it) {
+            n_evals += 1;
+            if (it > 66) { stuck = true; break; }
+            const int32_t oc = relax_eval_generic(x, valid, rank, Lp, rt);
+            if (kasw::ballot(oc != oc_prev) == 0ull) break;
+            const uint32_t w0 = (uint32_t)oc & 3u, w1 = ((uint32_t)oc >> 2) & 3u;
+            rbuf[lane] = (Lp >= 1 ? KAS_RELAX_F0_ONE << w0 : 0u) | (Lp >= 2 ? KAS_RELAX_F1_ONE << w1 : 0u);
+            relax_pairs<3>(pp, padr, padd, it > 0);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-              rank[q] = 0;
+            for (int q = 0; q < 3; ++q) x[q] = mine[q];
+            oc_prev = oc;
+          }
+          if (active && oc_prev >= 0) {
+            const int32_t w0 = oc_prev & 3, w1 = (oc_prev >> 2) & 3, w2 = 3 - w0 - w1;
+            const int32_t w[3] = {w0, w1, w2};
 #pragma unroll
-              for (int j = 0; j < 3; ++j) rank[q] += (j != q && valid[j] && c[j] < c[q]) ? 1 : 0;
-            }
-            rows1 += (uint32_t)kasw::popc(kasw::ballot(Lp >= 1)); rows2 += (uint32_t)kasw::popc(kasw::ballot(Lp >= 2));
-            int32_t oc_prev = -1;
-            for (int32_t it = 0;; ++it) {
-              n_evals += 1;
-              if (it > 66) { stuck = true; break; }
-              const int32_t oc = relax_eval_generic(x, valid, rank, Lp, rt);
-              if (kasw::ballot(oc != oc_prev) == 0ull) break;
-              const uint32_t w0 = (uint32_t)oc & 3u, w1 = ((uint32_t)oc >> 2) & 3u;
-              rbuf[lane] = (Lp >= 1 ? KAS_RELAX_F0_ONE << w0 : 0u) | (Lp >= 2 ? KAS_RELAX_F1_ONE << w1 : 0u);
-              relax_pairs<3>(pp, padr, padd, it > 0);
-#pragma unroll
-              for (int q = 0; q < 3; ++q) x[q] = mine[q];
-              oc_prev = oc;
-            }
-            if (active && oc_prev >= 0) {
-              const int32_t w0 = oc_prev & 3, w1 = (oc_prev >> 2) & 3, w2 = 3 - w0 - w1;
-              const int32_t w[3] = {w0, w1, w2};
-#pragma unroll
-              for (int r = 0; r < W; ++r) {
-                if (r < ow) {
-                  const uint32_t cell = w[r] == 0 ? c[0] : (w[r] == 1 ? c[1] : c[2]);
-                  const int32_t id = r < Lp ? (C16 ? (int32_t)cell : (LDSIDS ? (int32_t)idt[cell] : g_node_id[cell])) : -1;
-                  if constexpr (CTX) { if (r == 2 && r < Lp) kasw::lds_add_u32(cnt2 + cell, 1u); }
-                  if constexpr (C16) out16[(int64_t)p * ow + r] = (uint16_t)id;
-                  else out[(int64_t)p * ow + r] = id;
-                  if (r < Lp) dtop += kas_digest_cell((uint32_t)k, (uint32_t)p, (uint32_t)r, id);
-                }
+            for (int r = 0; r < W; ++r) {
+              if (r < ow) {
+                const uint32_t cell = w[r] == 0 ? c[0] : (w[r] == 1 ? c[1] : c[2]);
+                const int32_t id = r < Lp ? (C16 ? (int32_t)cell : (LDSIDS ? (int32_t)idt[cell] : g_node_id[cell])) : -1;
+                if constexpr (CTX) { if (r == 2 && r < Lp) kasw::lds_add_u32(cnt2 + cell, 1u); }
+                if constexpr (C16) out16[(int64_t)p * ow + r] = (uint16_t)id;
+                else out[(int64_t)p * ow + r] = id;
+                if (r < Lp) dtop += kas_digest_cell((uint32_t)k, (uint32_t)p, (uint32_t)r, id);
               }
             }
           }
@@ -781,22 +750,15 @@ KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, 
 #pragma unroll
           for (int q = 0; q < 3; ++q) kasw::arrived(pend.id[b][q]);
         }
-        // ... the next rows move up,
-        if constexpr (NB == 1) {
-          raw[0] = mid_take<W, FULLW, M32>(nx[0], ow, row_exists(tile));
-        } else if constexpr (NB == 4) {
-          if (step == 4) {
+        // ... the next rows move up: a step that took all NB tiles takes all of nx[]; a step of one tile (of an instance
+        // with NB > 1) shifts its rows down by one and takes the tile behind them from nx[0],
+        if (step == NB) {                                      // (wave-uniform; NB == 1: always)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) raw[b] = mid_take<W, FULLW, M32>(nx[b], ow, row_exists(tile + b));
-          } else {
-            raw[0] = raw[1]; raw[1] = raw[2]; raw[2] = raw[3]; raw[3] = mid_take<W, FULLW, M32>(nx[0], ow, row_exists(tile + 3));
-          }
+          for (int b = 0; b < NB; ++b) raw[b] = mid_take<W, FULLW, M32>(nx[b], ow, row_exists(tile + b));
         } else {
-          if (step == 2) {
-            raw[0] = mid_take<W, FULLW, M32>(nx[0], ow, row_exists(tile)); raw[1] = mid_take<W, FULLW, M32>(nx[1], ow, row_exists(tile + 1));
-          } else {
-            raw[0] = raw[1]; raw[1] = mid_take<W, FULLW, M32>(nx[0], ow, row_exists(tile + 1));
-          }
+#pragma unroll
+          for (int b = 0; b + 1 < NB; ++b) raw[b] = raw[b + 1];
+          raw[NB - 1] = mid_take<W, FULLW, M32>(nx[0], ow, row_exists(tile + NB - 1));
         }
         // the previous step's final rows go out,
         dtop += relax_flush<NB, C16>(pend, out, out16, (uint32_t)k);

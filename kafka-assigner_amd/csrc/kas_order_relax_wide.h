@@ -23,8 +23,8 @@
 //                  into the addend 1 << 16 c (c <= 3) or 0.
 //
 // Per tile: sort (9 compare-exchanges at W = 5), then per evaluation W picks of ~12 vector instructions per candidate, W pair
-// instructions each way (ds_sub_u64 of the previous addends, ds_add_rtn_u64 of the new ones) and W 8-byte staging words per
-// lane.  That is 4-5 times the work of the 3-wide form per evaluation, which is why DESIGN.md section 4.3 had declined to
+// instructions each way (ds_sub_u64 of the previous addends, ds_add_rtn_u64 of the new ones: relax_exchange of
+// kas_order_relax.h on 8-byte words — only the addends are made here) and W 8-byte staging words per lane.  That is 4-5 times the work of the 3-wide form per evaluation, which is why DESIGN.md section 4.3 had declined to
 // build it on an estimate; VERDICT r5 asked for the measurement (profiles/r06_*config5*).
 //
 // Applicable (KasShape::relaxw_ok): lists 4 or 5 wide, no Context handed in, no topic hash of Integer.MIN_VALUE, fewer than
@@ -170,21 +170,7 @@ KAS_DEV void order_relax_wide(const KasLaunch& a, int32_t s, unsigned char* lds_
           const uint32_t code = (*prow[t] >> pcell[t]) & 7u;
           nadd[t] = code < 4u ? (1ull << (16 * code)) : 0ull;
         }
-        if (it > 0) {                                        // (wave-uniform) take the previous additions back
-#pragma unroll
-          for (int t = 0; t < W; ++t) kasw::lds_sub_u64(padr[t], padd[t]);
-        }
-        kasw::lockstep();
-        uint64_t got[W];
-#pragma unroll
-        for (int t = 0; t < W; ++t) {
-          got[t] = kasw::lds_add_rtn_u64(padr[t], nadd[t]);
-          kasw::lockstep();                                  // (one instruction at a time, lanes in order: the hardware's order)
-          padd[t] = nadd[t];
-        }
-#pragma unroll
-        for (int t = 0; t < W; ++t) pslot[64 * t] = got[t];
-        kasw::lockstep();
+        relax_exchange<W, uint64_t>(pslot, padr, padd, nadd, it > 0);   // (kas_order_relax.h: the 3-wide form's, on 8-byte words)
 #pragma unroll
         for (int i = 0; i < W; ++i) x[i] = mine[i];
         oc_prev = oc;

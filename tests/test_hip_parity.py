@@ -111,6 +111,40 @@ def test_hip_dword_mid_rows_where_they_apply():
         plan.close()
 
 
+def test_hip_relaxation_steps_of_1_2_and_4_tiles_at_their_edges():
+    """The emulator's batch of tests/test_emu_parity.py (topics of one, two and four tiles of rows less one, exactly and plus one, a
+    narrower topic, a topic whose every row is an orphan) under the same plan flag words: steps of 64, 128 and 256 rows, the order
+    kernel of its own and beside first fit in one workgroup, the sampled verification, int32 and 16-bit cells — the kernel each
+    word names, and the lists against the oracle."""
+    from kafka_assigner_amd.flatten import index_form
+    from test_emu_parity import relax_step_edge_cases
+    ctx = native.default_context()
+    fb, flag_words = relax_step_edge_cases()
+    want = oracle_solve(fb)
+    assert (want.topic_results["status"] == abi.KAS_OK).all()
+    # (as the emulator does for a word that names no place for first fit: kas_p4_kernel, so that the order kernel of its own runs
+    # too — by itself a batch this small takes kas_p4_order_kernel under every word)
+    own_p4 = lambda flags: flags if flags & abi.KAS_PLAN_P4_WITH_ORDER else flags | abi.KAS_PLAN_SPLIT_P4
+    for flags in map(own_p4, flag_words):
+        plan = native.Plan(ctx, fb)
+        plan.set_flags(flags)
+        what = plan.describe()
+        plan.close()
+        rows = 64 << (((flags >> 17) & 3) - 1)
+        assert "tiles of %d rows" % rows in what, (hex(flags), what)
+        assert ("kas_p4_order_kernel<3>" in what) == ((flags & abi.KAS_PLAN_P4_WITH_ORDER) == abi.KAS_PLAN_P4_WITH_ORDER), (hex(flags), what)
+        assert ("sampled verification" in what) == (flags >> 24 != 0) and ("dword mid rows" in what) == (not flags & abi.KAS_PLAN_NO_MID32), (hex(flags), what)
+        got = native.solve_host_with_flags(fb, flags, ctx)
+        assert_same_outputs(fb, want, got, f"hip relaxation steps at their edges, plan flags {flags:#x}")
+        assert (got.scenario_results["status"] == abi.KAS_OK).all(), hex(flags)
+    want16 = oracle_solve(index_form(fb))
+    want16.out = np.where(want16.out < 0, 0xFFFF, want16.out).astype(np.uint16)
+    for flags in map(own_p4, (TILES_64, TILES_128)):
+        got16 = native.solve_device16_with_flags(fb, flags, ctx)
+        assert "[16-bit cells]" in got16.describe and "tiles of %d rows" % (64 if flags & TILES_128 == 0 else 128) in got16.describe, got16.describe
+        assert_same_outputs(fb, want16, got16, f"hip relaxation steps at their edges, 16-bit cells, plan flags {flags:#x}")
+
+
 def test_hip_rack_awareness_disabled_cyclic_and_sparse_ids():
     fb = _batch(99, 4, 1500, 50, 10, 3, G.ACTIONS, rack_aware=False)
     assert_same_outputs(fb, oracle_solve(fb), native.solve_host(fb), "hip norack")
