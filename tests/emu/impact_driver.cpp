@@ -28,7 +28,14 @@ template <bool C16> run_fn item_for(int32_t wc) {   // (the instances kas_impact
   return wc <= 3 ? run_item<3, C16> : (wc <= 5 ? run_item<5, C16> : run_item<8, C16>);
 }
 
+uint32_t g_lds_fill = 0xCDCDCDCDu;
+
 }  // namespace
+
+// The word every workgroup finds all over its LDS when it starts (default 0xCDCDCDCD).  LDS is uninitialised on hardware: it holds
+// what the workgroup before left there, an id table for instance, and a test may want exactly that behind this launch's tables.
+extern "C" __attribute__((visibility("default")))
+void kas_emu_impact_lds_fill(uint32_t word) { g_lds_fill = word; }
 
 // t->cur / t->out: int32 pools, or uint16 pools (cells16; b->node_id is then not read).  node_cap_limit >= 0: count scenarios
 // above that many nodes in global scratch; rows_per_item > 0: rows of an item instead of the product's rule.
@@ -77,7 +84,7 @@ int kas_emu_impact(const kas_batch_desc* b, const kas_tables* t, int cells16, in
   int32_t global_items = 0;
   for (int32_t i = 0; i < a.n_items; ++i) {
     global_items += ip.items[(size_t)i].mode == KAS_IMPACT_GLOBAL ? 1 : 0;
-    memset(lds.data(), 0xCD, bytes);                   // LDS is uninitialised on hardware too
+    for (size_t k = 0; k + 4 <= bytes; k += 4) memcpy(lds.data() + k, &g_lds_fill, 4);   // LDS is uninitialised on hardware too
     memset(lds.data() + bytes, 0xA5, 4096);
     ItemArgs r{&a, i, lds.data()};
     if (kasw::run_block(item, &r, KAS_IMPACT_BLOCK / 64) != 0) return bad("impact item: divergence / deadlock", i);

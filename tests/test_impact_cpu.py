@@ -4,7 +4,9 @@
 - The kernel body (kafka-assigner_amd/csrc/kas_impact_body.h) compiled with g++ against tests/emu/kas_wave.h and stepped on
   CPU fibers (tests/emu/impact_driver.cpp) over oracle-produced out tables: equal to the checker for one- and multi-item
   scenarios (the merge kernel), ragged lists, in_partitions flags, a failing topic followed by a skipped one, multi-topic
-  scenarios, two scenarios on one node range, both cell layouts and the counters beyond the LDS budget.
+  scenarios, two scenarios on one node range, both cell layouts and the counters beyond the LDS budget; lists 4-8 wide with
+  the replication factor raised and lowered, the binary-search lookup, the row loop's and the items' edges, scenarios without
+  topics or brokers.  The batches come from tests/impact_batches.py, whose assert_exercises() keeps them counting rows.
 - The ABI: the new entry points are declared and exported, the records are 32 bytes.
 """
 import ctypes as C
@@ -16,6 +18,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from impact_batches import (ROW_COUNTS, STALE_ID, assert_exercises, lookup_kind, many_brokers_batch, mixed_batch, shared_node_range_batch,
+                            solved)
 from impact_ref import assert_same_impact, check_invariants, impact_ref
 from kafka_assigner_amd import abi, native
 from kafka_assigner_amd import generator as G
@@ -50,12 +54,15 @@ def _emu_lib():
     L.kas_emu_impact.restype = C.c_int
     L.kas_emu_impact.argtypes = [C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.c_int, C.c_int, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int]
+    L.kas_emu_impact_lds_fill.restype = None
+    L.kas_emu_impact_lds_fill.argtypes = [C.c_uint32]
     _LIB = L
     return L
 
 
-def emu_impact(fb, ho, cells16=False, cur16=None, node_cap=-1, rows_per_item=0):
-    """kas_emu_impact over the tables a solve left in `ho`: ((nodes, scenarios), {items, merges, global_items, node_cap})."""
+def emu_impact(fb, ho, cells16=False, cur16=None, node_cap=-1, rows_per_item=0, lds_fill=0xCDCDCDCD):
+    """kas_emu_impact over the tables a solve left in `ho`: ((nodes, scenarios), {items, merges, global_items, node_cap}).
+    lds_fill: the word every workgroup finds all over its LDS (what the workgroup before left there)."""
     bd = batch_desc(fb)
     t = abi.Tables()
     if cells16:
@@ -72,8 +79,12 @@ def emu_impact(fb, ho, cells16=False, cur16=None, node_cap=-1, rows_per_item=0):
     scen[...] = -7
     info = (C.c_int32 * 4)()
     err = C.create_string_buffer(512)
-    rc = _emu_lib().kas_emu_impact(C.byref(bd), C.byref(t), int(cells16), int(node_cap), int(rows_per_item),
-                                   nodes.ctypes.data, scen.ctypes.data, info, err, 512)
+    _emu_lib().kas_emu_impact_lds_fill(lds_fill)
+    try:
+        rc = _emu_lib().kas_emu_impact(C.byref(bd), C.byref(t), int(cells16), int(node_cap), int(rows_per_item),
+                                       nodes.ctypes.data, scen.ctypes.data, info, err, 512)
+    finally:
+        _emu_lib().kas_emu_impact_lds_fill(0xCDCDCDCD)
     assert rc == 0, (rc, err.value.decode())
     return (nodes, scen), dict(zip(("items", "merges", "global_items", "node_cap"), list(info)))
 
@@ -101,32 +112,10 @@ def _appendix_b_batch():
     return flatten(scs)
 
 
-def _random_batch(seed, n_scen=4, max_p=600, ragged=True, flags=True):
-    """Sparse broker ids (some of the current replicas name brokers outside the set), ragged lists, partition sets that are not
-    the keys of the current assignment, one to three topics per scenario."""
-    rng = np.random.default_rng(seed)
-    scs = []
-    for _ in range(n_scen):
-        N = int(rng.integers(6, 40))
-        R = int(rng.integers(2, 6))
-        brokers = sorted(int(b) for b in rng.choice(60, N, replace=False))
-        racks = {b: "r%d" % (b % R) for b in brokers}
-        topics = []
-        for t in range(int(rng.integers(1, 4))):
-            P = int(rng.integers(1, max_p))
-            rf = int(rng.integers(2, 4))
-            cur = {}
-            for p in range(P):
-                reps = [int(x) for x in rng.choice(70, rf, replace=False)]
-                if ragged and rng.random() < 0.15:
-                    reps = reps[:int(rng.integers(0, rf))]
-                cur[p] = reps
-            parts = None
-            if flags and rng.random() < 0.5:
-                parts = set(range(P)) - {int(x) for x in rng.choice(P, P // 5, replace=False)} | {P + 3, P + 7}
-            topics.append(Topic("t%d" % t, cur, rf, partitions=parts))
-        scs.append(Scenario(brokers=brokers, racks=racks, topics=topics))
-    return flatten(scs)
+def _random_batch(seed, n_scen=4):
+    """remove / add / replace / as is, one to three topics per scenario, ragged lists, partition sets that are not the keys of
+    the current assignment, replicas on brokers outside the set (impact_batches.mixed_batch: topics that solve)"""
+    return mixed_batch(seed, n_scen=n_scen)
 
 
 def _failing_then_skipped_batch():
@@ -140,23 +129,16 @@ def _failing_then_skipped_batch():
                     Scenario(brokers, racks, [Topic("a", a, 3), Topic("b", b, 3)])])
 
 
-def _shared_node_range_batch():
-    """two scenarios that read one node range (node_off equal): each gets a block of records of its own"""
-    cur = G.random_assignment(5, 400, 20, 5, 3)
-    brokers = [b for b in range(22) if b != 4]
-    racks = {b: "r%d" % (b % 5) for b in brokers}
-    fb = flatten([Scenario(brokers, racks, [Topic("x", {p: cur[p].tolist() for p in range(400)}, 3)]),
-                  Scenario(brokers, racks, [Topic("y", {p: cur[(p * 7) % 400].tolist() for p in range(400)}, 3)])])
-    fb.scen["node_off"][1] = fb.scen["node_off"][0]
-    return fb
+_shared_node_range_batch = shared_node_range_batch
+_many_brokers_batch = many_brokers_batch
 
 
-def _many_brokers_batch():
-    """7,000 brokers: N x 24 bytes of counters do not fit the LDS next to the id table (the global-scratch path)"""
-    N, P = 7000, 300
-    cur = G.random_assignment(11, P, N + 50, 20, 3)
-    brokers = list(range(N))
-    return flatten([Scenario(brokers, {b: "r%d" % (b % 20) for b in brokers}, [Topic("big", {p: cur[p].tolist() for p in range(P)}, 3)])])
+def guarded(fb, ho=None, **claims):
+    """(ho, want): the oracle's solve of `fb` and the checker's records of it, after assert_exercises has found rows in them"""
+    ho = oracle_solve(fb) if ho is None else ho
+    want = impact_ref(fb, ho)
+    assert_exercises(fb, ho, want, **claims)
+    return ho, want
 
 
 # ---- the checker on the oracle's outputs ----------------------------------------------------------------------------------
@@ -166,6 +148,8 @@ def test_checker_invariants_on_oracle_outputs(name):
           "failing_then_skipped": _failing_then_skipped_batch, "shared_node_range": _shared_node_range_batch}[name]()
     ho = oracle_solve(fb)
     imp = impact_ref(fb, ho)
+    if name in ("random0", "random1", "shared_node_range"):
+        assert_exercises(fb, ho, imp)
     check_invariants(fb, ho, imp)
     nodes, scen = imp
     base = native.node_blocks(fb)
@@ -199,8 +183,7 @@ def test_checker_sees_the_appendix_b_replacement():
 @pytest.mark.parametrize("seed", [7, 8])
 def test_emulated_kernel_equals_checker_random_batches(seed):
     fb = _random_batch(seed)
-    ho = oracle_solve(fb)
-    want = impact_ref(fb, ho)
+    ho, want = guarded(fb, merge=True, widths=[(2, 3), (3, 3)])
     got, info = emu_impact(fb, ho)
     assert info["merges"] > 0 and info["items"] > info["merges"]      # (multi-topic scenarios merge, single-topic ones do not)
     assert_same_impact(want, got, "emulated impact, one item per topic")
@@ -211,11 +194,16 @@ def test_emulated_kernel_equals_checker_random_batches(seed):
 
 def test_emulated_kernel_one_item_scenarios_write_directly():
     fb = _shared_node_range_batch()
-    ho = oracle_solve(fb)
+    ho, want = guarded(fb, must_solve=[0, 1])
     got, info = emu_impact(fb, ho)
-    assert info == {"items": 2, "merges": 0, "global_items": 0, "node_cap": 21}
-    assert_same_impact(impact_ref(fb, ho), got, "one item per scenario, two scenarios on one node range")
-    assert native.node_blocks(fb)[-1] == 42
+    assert info == {"items": 2, "merges": 0, "global_items": 0, "node_cap": 29}
+    assert_same_impact(want, got, "one item per scenario, two scenarios on one node range")
+    assert native.node_blocks(fb)[-1] == 58
+    nodes, scen = got
+    for s in (0, 1):                                          # both blocks hold counts, and not the same ones
+        assert int(nodes["replicas_after"][29 * s:29 * s + 29].sum()) > 0 and int(scen["leaders_moved"][s]) > 0
+    assert any((nodes[f][:29] != nodes[f][29:]).any() for f in abi.NODE_IMPACT_FIELDS)
+    assert any(int(scen[f][0]) != int(scen[f][1]) for f in abi.SCENARIO_IMPACT_FIELDS)
 
 
 def test_emulated_kernel_failing_then_skipped_topic():
@@ -232,8 +220,7 @@ def test_emulated_kernel_failing_then_skipped_topic():
 @pytest.mark.parametrize("seed", [21, 22])
 def test_emulated_kernel_cells16_equals_int32(seed):
     fb = _random_batch(seed, n_scen=3)
-    ho = oracle_solve(fb)
-    want = impact_ref(fb, ho)
+    ho, want = guarded(fb, merge=True)
     ho16, cur16 = solved16(fb)
     assert_same_impact(want, impact_ref(fb, ho16, cells16=True, cur16=cur16), "checker, 16-bit cells")
     for rows in (0, 150):
@@ -246,20 +233,122 @@ def test_emulated_kernel_cells16_equals_int32(seed):
 def test_emulated_kernel_global_counters():
     """the counters in global scratch: forced on a small batch, and for real beyond the LDS budget (7,000 brokers)"""
     fb = _random_batch(31, n_scen=3)
-    ho = oracle_solve(fb)
+    ho, want = guarded(fb, merge=True)
     got, info = emu_impact(fb, ho, node_cap=0)
     assert info["global_items"] == info["items"] and info["merges"] == fb.n_scenarios
-    assert_same_impact(impact_ref(fb, ho), got, "global counters (forced)")
+    assert_same_impact(want, got, "global counters (forced)")
     fb = _many_brokers_batch()
-    ho = oracle_solve(fb)
+    ho, want = guarded(fb, must_solve=[0])
     assert int(ho.topic_results["status"][0]) == abi.KAS_OK
-    want = impact_ref(fb, ho)
     assert int(want[1]["departed_replicas"][0]) > 0
     for cells16 in (False, True):
         h = solved16(fb)[0] if cells16 else ho
         got, info = emu_impact(fb, h, cells16=cells16)
         assert info["global_items"] == 1 and info["node_cap"] < 7000, info
         assert_same_impact(want, got, "beyond the LDS budget, cells16=%s" % cells16)
+
+
+# ---- the paths no other test counts a row on ------------------------------------------------------------------------------
+def _emulator_matrix(name, rows_per_item=(0, 97), cells16=True):
+    """The named batch (impact_batches.BATCHES, guard passed) on the emulator: one item per topic and items of 97 rows, counters
+    in the LDS and in global scratch, int32 and 16-bit cells -- every run equal to the checker on the oracle's rows."""
+    fb, ho, want = solved(name)
+    runs = [(False, ho, None)]
+    if cells16:
+        ho16, cur16 = solved16(fb)
+        assert_same_impact(want, impact_ref(fb, ho16, cells16=True, cur16=cur16), f"{name}: checker, 16-bit cells")
+        runs.append((True, ho16, cur16))
+    infos = []
+    for c16, h, cur16 in runs:
+        for rows in rows_per_item:
+            for cap in (-1, 0):
+                got, info = emu_impact(fb, h, cells16=c16, cur16=cur16, node_cap=cap, rows_per_item=rows)
+                assert_same_impact(want, got, f"{name}: cells16={c16}, rows per item {rows}, node_cap {cap}")
+                assert (got[0]["reserved"] == 0).all()
+                assert (info["global_items"] > 0) == (cap == 0)
+                infos.append(info)
+    return fb, ho, want, infos
+
+
+def _width_class(fb):
+    """kas_width_class (kas_plan_math.h) of the batch: the instance of kas_impact_kernel its launch takes"""
+    w = int(fb.topics["out_width"].max())
+    return 2 if w <= 2 else (w if w <= 5 else 8)
+
+
+def test_emulated_kernel_lists_4_and_5_wide():
+    """kas_impact_kernel<5>: (cur_width, rf) = (5,5), (4,4), (2,4) RF raised, (5,3) RF lowered (pads in out), (3,3)"""
+    fb, ho, want, _ = _emulator_matrix("widths_4_5")
+    assert _width_class(fb) == 5
+    t = [i for i in range(fb.n_topics) if (int(fb.topics["cur_width"][i]), int(fb.topics["rf"][i])) == (5, 3)][0]
+    td = fb.topics[t]
+    rows = ho.out[int(td["out_off"]):][:int(td["n_partitions"]) * 5].reshape(-1, 5)
+    assert (rows[:, 3] == -1).any() and (rows[:, 0] != -1).all()          # RF lowered: rows with pads behind the list
+
+
+def test_emulated_kernel_lists_6_to_8_wide():
+    """kas_impact_kernel<8>: (cur_width, rf) = (7,7), (8,8), (3,6) RF raised, (8,2) RF lowered"""
+    fb, _, _, _ = _emulator_matrix("widths_6_8")
+    assert _width_class(fb) == 8
+
+
+@pytest.mark.parametrize("name", ["sparse", "dense_and_sparse", "id_range_edge", "beyond_the_table"])
+def test_emulated_kernel_binary_search_lookup(name):
+    """node_of's binary search over the sorted ids in the LDS: id ranges beyond KAS_IDMAP_CAP alone, next to a dense scenario
+    whose direct table shares the LDS region, on either side of the cap (ranges of 16384 and 16385 ids), and for a departed
+    broker whose id stands in the LDS right behind the table (the search's bound)"""
+    fb, _, _, _ = _emulator_matrix(name)
+    kinds = [lookup_kind(fb, s) for s in range(fb.n_scenarios)]
+    assert kinds == {"sparse": ["bsearch"] * 2, "dense_and_sparse": ["direct", "bsearch", "direct"],
+                     "id_range_edge": ["direct", "bsearch"], "beyond_the_table": ["bsearch"]}[name]
+    if name == "beyond_the_table":
+        fb, ho, want = solved(name)
+        assert STALE_ID > int(fb.node_id.max()) and int((fb.cur == STALE_ID).sum()) > 0      # departed, above every id of the set
+        for cap in (-1, 0):
+            got, _ = emu_impact(fb, ho, node_cap=cap, lds_fill=STALE_ID)
+            assert_same_impact(want, got, f"the departed broker's id all over the LDS, node_cap {cap}")
+
+
+def test_emulated_kernel_row_loop_edges():
+    """P = 1, 511, 512, 513, 1025 around the row loop's stride of ROWS_PER_LANE * KAS_IMPACT_BLOCK = 512 rows, and items of
+    P - 1, P and P + 1 rows for P = 513"""
+    fb, ho, want, _ = _emulator_matrix("row_counts", rows_per_item=(0, 97, 512, 513, 514), cells16=True)
+    assert tuple(int(p) for p in fb.topics["n_partitions"]) == ROW_COUNTS
+    items = {rows: emu_impact(fb, ho, rows_per_item=rows)[1]["items"] for rows in (512, 513, 514)}
+    assert items == {512: 1 + 1 + 1 + 2 + 3, 513: 1 + 1 + 1 + 1 + 2, 514: 1 + 1 + 1 + 1 + 2}
+    base = native.node_blocks(fb)
+    for s, P in enumerate(ROW_COUNTS):                           # every row of every scenario is counted once
+        assert int(want[0]["replicas_after"][base[s]:base[s + 1]].sum()) == 3 * P
+
+
+def test_emulated_kernel_scenarios_without_topics_or_brokers():
+    """a scenario without topics (work-list item with topic == -1) and a scenario without brokers beside a normal one: flatten
+    and kas_shape_batch take both, and both records are written as zeros"""
+    fb, ho, want, infos = _emulator_matrix("degenerate")
+    assert fb.scen["topic_count"].tolist() == [3, 0, 1] and fb.scen["n_nodes"].tolist() == [29, 12, 0]
+    assert int(ho.topic_results["status"][3]) == abi.KAS_FAIL_RF_GT_BROKERS
+    assert infos[0]["items"] == 3 + 1 + 1
+    nodes, scen = emu_impact(fb, ho)[0]
+    assert nodes.shape[0] == 41 and not any(nodes[f][29:].any() for f in abi.NODE_IMPACT_FIELDS)
+    for s in (1, 2):
+        assert not any(int(scen[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS)
+    assert int(scen["min_replicas_after"][0]) > 0
+
+
+
+
+@pytest.mark.parametrize("name,items,global_items", [("rows_4096", 1, 0), ("rows_4097", 2, 0), ("rows_10000", 3, 0),
+                                                     ("many_brokers_10000", 3, 3)])
+def test_emulated_kernel_items_cut_by_the_library_rule(name, items, global_items):
+    """the GPU tests' shapes under kas_impact_rows_per_item (items of KAS_IMPACT_MIN_ITEM_ROWS = 4096 rows): 4096 rows are one
+    DIRECT item, 4097 two FLUSH items and a merge, 10000 three -- and with 7,000 brokers three items adding into one region"""
+    fb, ho, want = solved(name)
+    ho16, cur16 = solved16(fb)
+    assert_same_impact(want, impact_ref(fb, ho16, cells16=True, cur16=cur16), f"{name}: checker, 16-bit cells")
+    for c16, h in ((False, ho), (True, ho16)):
+        got, info = emu_impact(fb, h, cells16=c16, cur16=cur16 if c16 else None)
+        assert (info["items"], info["merges"], info["global_items"]) == (items, int(items > 1), global_items), info
+        assert_same_impact(want, got, f"{name}: cells16={c16}")
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------

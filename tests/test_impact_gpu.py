@@ -7,13 +7,14 @@ import subprocess
 import numpy as np
 import pytest
 
+from impact_batches import assert_exercises, replan_batches, solved, whatif_inputs
 from impact_ref import assert_same_impact, check_invariants, impact_ref
 from kafka_assigner_amd import abi, native
 from kafka_assigner_amd import generator as G
 from kafka_assigner_amd.flatten import HostOutputs, Scenario, Topic, flatten, host_tables, node_set_batch, to_cells16
 from oracle_lib import oracle_solve
 from test_impact_cpu import (GOLD, _failing_then_skipped_batch, _many_brokers_batch, _random_batch,
-                             _shared_node_range_batch)
+                             _shared_node_range_batch, _width_class, guarded)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,14 +36,23 @@ def _same_solve(a, b, what):
     assert np.array_equal(a.out, b.out), what
 
 
-BATCHES = {"random": lambda: _random_batch(41, n_scen=6), "failing_then_skipped": _failing_then_skipped_batch,
+BATCHES = {"random": lambda: _random_batch(42, n_scen=6), "failing_then_skipped": _failing_then_skipped_batch,
            "shared_node_range": _shared_node_range_batch, "many_brokers": _many_brokers_batch}
+CLAIMS = {"random": dict(merge=True, widths=[(2, 3), (3, 3)]), "shared_node_range": dict(must_solve=[0, 1]),
+          "many_brokers": dict(must_solve=[0])}
+
+
+def _guard(name, fb):
+    """assert_exercises on the oracle's solve of the batch (not for the batch whose subject is failure)"""
+    if name in CLAIMS:
+        guarded(fb, **CLAIMS[name])
 
 
 @pytest.mark.parametrize("cells16", [False, True], ids=["int32", "cells16"])
 @pytest.mark.parametrize("name", list(BATCHES))
 def test_host_impact_equals_checker(ctx, name, cells16):
     fb = BATCHES[name]()
+    _guard(name, fb)
     if cells16:
         plain = native.solve_host16(fb, ctx)
     else:
@@ -98,9 +108,161 @@ def _device_impact(ctx, fb, cells16):
 @pytest.mark.parametrize("name", ["random", "failing_then_skipped", "many_brokers"])
 def test_device_impact_equals_checker(ctx, name, cells16):
     fb = BATCHES[name]()
+    _guard(name, fb)
     ho, got = _device_impact(ctx, fb, cells16)
     assert (got[0]["reserved"] == 0).all()
     assert_same_impact(impact_ref(fb, ho, cells16=cells16), got, f"{name}, kas_impact_device{'16' if cells16 else ''}")
+
+
+# ---- the paths no other test counts a row on (impact_batches.BATCHES: small shapes, the oracle's solve shared) --------------
+NAMED = ["widths_4_5", "widths_6_8", "rf_4", "rf_4_5", "rf_7_8", "sparse", "dense_and_sparse", "id_range_edge", "beyond_the_table",
+         "row_counts", "degenerate", "rows_4096", "rows_4097", "rows_10000", "many_brokers_10000"]
+WIDTH_CLASS = {"widths_4_5": 5, "widths_6_8": 8, "rf_4": 4, "rf_4_5": 5, "rf_7_8": 8}
+
+
+@pytest.mark.parametrize("name", NAMED)
+def test_host_and_device_impact_on_the_named_batches(ctx, name):
+    """kas_solve_host_impact and kas_impact_device on int32 cells: lists 4-8 wide (RF raised and lowered among them), the binary
+    search alone / beside a direct table / on either side of KAS_IDMAP_CAP, the row loop's edges, scenarios without topics or
+    brokers, a scenario cut into row-range items at 4096 rows (one, two and three items; FLUSH + merge) and three workgroups
+    adding into one region of global counters (7,000 brokers) -- against the checker on the GPU's own rows and on the oracle's"""
+    fb, _, want = solved(name)
+    if name in WIDTH_CLASS:
+        plan = native.Plan(ctx, fb)
+        try:
+            assert _width_class(fb) == WIDTH_CLASS[name] and f"kas_fill_kernel<{WIDTH_CLASS[name]}," in plan.describe(), plan.describe()
+        finally:
+            plan.close()
+    ho, nodes, scen = native.solve_host_impact(fb, ctx=ctx)
+    assert_same_impact(impact_ref(fb, ho), (nodes, scen), f"{name}, kas_solve_host_impact on its own rows")
+    assert_same_impact(want, (nodes, scen), f"{name}, kas_solve_host_impact against the oracle's rows")
+    check_invariants(fb, ho, (nodes, scen))
+    hd, got = _device_impact(ctx, fb, False)
+    assert (got[0]["reserved"] == 0).all()
+    assert_same_impact(impact_ref(fb, hd), got, f"{name}, kas_impact_device on its own rows")
+    assert_same_impact(want, got, f"{name}, kas_impact_device against the oracle's rows")
+
+
+@pytest.mark.parametrize("name", ["row_counts", "rows_10000", "many_brokers_10000"])
+def test_host_and_device_impact16_on_the_named_batches(ctx, name):
+    """the same on 16-bit cells: the row loop's edges, FLUSH items + merge, GLOBAL counters shared by three workgroups"""
+    fb, _, want = solved(name)
+    ho, nodes, scen = native.solve_host_impact(fb, cells16=True, ctx=ctx)
+    assert ho.out.dtype == np.uint16
+    assert_same_impact(impact_ref(fb, ho, cells16=True), (nodes, scen), f"{name}, kas_solve_host16_impact on its own rows")
+    assert_same_impact(want, (nodes, scen), f"{name}, kas_solve_host16_impact against the oracle's int32 solve")
+    hd, got = _device_impact(ctx, fb, True)
+    assert_same_impact(impact_ref(fb, hd, cells16=True), got, f"{name}, kas_impact_device16 on its own rows")
+    assert_same_impact(want, got, f"{name}, kas_impact_device16 against the oracle's int32 solve")
+
+
+def test_host16_impact_widened_to_int32_cells(ctx):
+    """kas_solve_host16_impact at RF 5 and 4: kas_cells16_ok admits lists up to 3 wide, so the call is widened to int32 cells and
+    the pass runs over the widened tables; a 16-bit plan of that batch is refused"""
+    fb, _, want = solved("rf_4_5")
+    h32, n32, s32 = native.solve_host_impact(fb, ctx=ctx)
+    h16, n16, s16 = native.solve_host_impact(fb, cells16=True, ctx=ctx)
+    assert h16.out.dtype == np.uint16
+    assert_same_impact((n32, s32), (n16, s16), "RF 5: 16-bit call against the int32 call")
+    assert_same_impact(want, (n16, s16), "RF 5: 16-bit call against the oracle")
+    assert_same_impact(impact_ref(fb, h16, cells16=True), (n16, s16), "RF 5: 16-bit call on the rows it returned")
+    with pytest.raises(native.KasError) as e:
+        native.Plan(ctx, fb, cells16=True)
+    assert e.value.code == abi.KAS_E_UNSUPPORTED and "16-bit cells: lists up to 3 wide" in e.value.detail
+
+
+def test_host_impact_on_a_plan_rebuilt_in_place_for_other_broker_sets():
+    """Three kas_solve_host_impact calls of one shape on one context whose broker sets differ in size (1, 2 and 3 brokers taken
+    out): the cached plan is rebuilt in place (no hit, no allocation) and node_base, region_off and the work list with it"""
+    ctx = native.DeviceContext(0)
+    try:
+        fbs = replan_batches()
+        assert len({tuple(fb.scen["n_nodes"].tolist()) for fb in fbs}) == 3
+        stats = []
+        for k, fb in enumerate(fbs + fbs[:1]):
+            assert fb.topics.tobytes() == fbs[0].topics.tobytes() and np.array_equal(fb.cur, fbs[0].cur)
+            _, want = guarded(fb, merge=True)
+            ho, nodes, scen = native.solve_host_impact(fb, ctx=ctx)
+            assert_same_impact(impact_ref(fb, ho), (nodes, scen), f"call {k}, on its own rows")
+            assert_same_impact(want, (nodes, scen), f"call {k}, against the oracle's rows")
+            stats.append(ctx.host_stats())
+        assert [s[0] for s in stats] == [1, 2, 3, 4] and all(s[1] == 0 for s in stats[:3])     # every call a miss ...
+        assert stats[0][2] > 0 and all(s[2] == stats[0][2] for s in stats[1:]), stats           # ... and yet no allocation
+    finally:
+        ctx.close()
+
+
+def _whatif_check(w, variants, ctx):
+    """WhatIf.solve(impact=True, rows=False) against the checker on the oracle's solve of the same batch"""
+    res = w.solve(variants, impact=True, rows=False)
+    fb = w.flat_batch(variants)
+    ho, (nodes, scen) = guarded(fb, merge=True)
+    base = native.node_blocks(fb)
+    for s, r in enumerate(res):
+        for f in abi.SCENARIO_IMPACT_FIELDS:
+            assert getattr(r, f) == int(scen[f][s]), (s, f)
+        ids = fb.node_id[int(fb.scen["node_off"][s]):][:int(fb.scen["n_nodes"][s])]
+        assert r.broker_impact() == {int(b): {f: int(nodes[f][base[s] + i]) for f in abi.NODE_IMPACT_FIELDS} for i, b in enumerate(ids)}
+        assert r.moved_replicas == int(ho.scenario_results["moved_replicas"][s]) and r.status == int(ho.scenario_results["status"][s])
+    return res
+
+
+def test_whatif_impact_twice_with_other_variants(ctx):
+    """what the what-if caller does on every call after its first: other broker sets over the same snapshot"""
+    from kafka_assigner_amd.whatif import Variant, WhatIf
+    w = WhatIf(*whatif_inputs())
+    first = _whatif_check(w, [Variant(label="as is"), Variant(remove=[3]), Variant(remove=[1, 2, 5]),
+                              Variant(add={60: "r0", 61: "r1"}), Variant(rack_aware=False)], ctx)
+    second = _whatif_check(w, [Variant(remove=[7, 40]), Variant(remove=[11]), Variant(remove=[0, 59], rack_aware=False),
+                               Variant(remove=[20, 21, 22]), Variant(remove=[33])], ctx)
+    assert 3 not in first[1].broker_impact() and 60 in first[3].broker_impact()
+    assert 7 not in second[0].broker_impact() and len(second[3].broker_impact()) == 57
+
+
+def _device_impact_twice(ctx, fb):
+    """_device_impact's sequence with a second kas_impact_device on another stream, no host synchronisation in between and
+    output arrays of its own: (HostOutputs, first (nodes, scenarios), second (nodes, scenarios))"""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    plan = native.Plan(ctx, fb)
+    try:
+        _, ho = host_tables(fb)
+        d_cur = torch.from_numpy(fb.cur.copy()).to(dev)
+        d_aux = torch.from_numpy(fb.aux).to(dev) if fb.aux.size else None
+        d_out = torch.full((max(fb.out_len, 1),), -2, dtype=torch.int32, device=dev)
+        d_tr = torch.zeros(max(fb.n_topics, 1) * 16, dtype=torch.uint8, device=dev)
+        d_sr = torch.zeros(max(fb.n_scenarios, 1) * 32, dtype=torch.uint8, device=dev)
+        n_nodes = int(native.node_blocks(fb)[-1])
+        outs = [(torch.full((max(n_nodes, 1) * 32,), 0x5A, dtype=torch.uint8, device=dev),
+                 torch.full((max(fb.n_scenarios, 1) * 32,), 0x5A, dtype=torch.uint8, device=dev)) for _ in range(2)]
+        streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+        for st in streams:
+            st.wait_stream(torch.cuda.current_stream(dev))
+        aux = d_aux.data_ptr() if d_aux is not None else 0
+        plan.solve_device(d_cur.data_ptr(), d_out.data_ptr(), d_tr.data_ptr(), d_sr.data_ptr(), aux=aux, stream=streams[0].cuda_stream)
+        for st, (d_nodes, d_scen) in zip(streams, outs):
+            plan.impact_device(d_cur.data_ptr(), d_out.data_ptr(), d_tr.data_ptr(), d_nodes.data_ptr(), d_scen.data_ptr(), aux=aux,
+                               stream=st.cuda_stream)
+        for st in streams:
+            st.synchronize()
+        ho.out = d_out.cpu().numpy()
+        ho.topic_results = d_tr.cpu().numpy().view(abi.TOPIC_RESULT_DTYPE)
+        ho.scenario_results = d_sr.cpu().numpy().view(abi.SCENARIO_RESULT_DTYPE)
+        got = [(n.cpu().numpy().view(abi.NODE_IMPACT_DTYPE)[:n_nodes], s.cpu().numpy().view(abi.SCENARIO_IMPACT_DTYPE)[:fb.n_scenarios])
+               for n, s in outs]
+        return ho, got[0], got[1]
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("name", ["rows_10000", "many_brokers_10000"], ids=["flush", "global"])
+def test_two_impact_passes_on_one_plan(ctx, name):
+    """the plan's counters are zeroed again before the second pass, which waits for the first (ev_impact) on its own stream"""
+    fb, _, want = solved(name)
+    ho, first, second = _device_impact_twice(ctx, fb)
+    assert_same_impact(impact_ref(fb, ho), first, f"{name}: first pass")
+    assert_same_impact(want, first, f"{name}: first pass against the oracle's rows")
+    assert_same_impact(want, second, f"{name}: second pass, other stream")
 
 
 def _headline(seed=5, S=1000, P=100_000, N=1000, R=20):
