@@ -1,5 +1,7 @@
 // kas_solver_body.h — the per-scenario solver: device code of the fill kernel (one workgroup of
 // NW 64-lane wavefronts per scenario, the scenario's node state in LDS) and of the order kernels.
+// (First fit is kas_first_fit.h, included before fill_topic; the order kernels other than the ticket and round forms are
+// kas_order_*.h, included at the end.)
 //
 // Computes exactly what KafkaAssignmentStrategy.getRackAwareAssignment computes
 // (KafkaAssignmentStrategy.java:40-63, "KAS"), for every topic of a scenario in order, with the
@@ -29,7 +31,8 @@
 //  P4  first fit (KAS:162-186): orphans in ascending row order, 64 per window, evaluated
 //      position-major over the compacted list of non-full nodes in processing order (a full
 //      node never becomes non-full; the reference spends >99% of its probes on them); the windows
-//      go round-robin to all wavefronts, one step apart.
+//      go round-robin to all wavefronts, one step apart.  kas_first_fit.h: the windows, the per-topic
+//      driver (first_fit_topic) and its pieces, and kas_p4_kernel's scenario.
 //  P5  preference order (KAS:202-239), a kernel of its own (the order kernel): its only state
 //      is count[node][replica index], so it runs with a fraction of the fill kernel's LDS and
 //      many more scenarios per CU.  Row p reads count[n][0..L) of its own nodes, picks, then
@@ -1179,201 +1182,89 @@ KAS_DEV int32_t fill_pass_b(const LdsView& L, const TopicView& T, const NodeMap&
   return fill_pass_b_range<W, DIRECT, QS, RTN, INPLACE>(L, T, nm, t0, t1, qc, moved_r, moved_p, st);
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// P4 of the rack-diverse fill (KAS:162-186) on ALL wavefronts of the workgroup.  The orphan rows
-// were listed per chunk by pass B; windows of 64 orphans (lane = orphan, ascending row order,
-// position-major first fit as in p4_window) go to the waves round-robin.  Window w + 1 may look
-// at live-list positions [j, j + U) as soon as window w is done with them (cell (orphan, node
-// position) of the reference's double loop depends only on earlier orphans at that position and
-// on earlier positions of that orphan), so consecutive windows run one step apart.
-// prog[wave] = window << 32 | positions done (monotone; a finished window counts as the start of
-// the next one).  A window waits for EVERY earlier window that may still be running (the latest
-// window of each other wave; earlier windows of its own wave are finished), not only for its
-// predecessor: that one can finish early while an older window still walks the list.  The earliest window that cannot place an orphan decides the failure
-// (KAS:183-184): everything before it completed exactly as in the sequential order; later
-// windows stop when they see it.  LDS words other waves write are read through a ballot or a
-// broadcast, so a wave always acts on one answer.
-// ---------------------------------------------------------------------------------------------
-// node positions per hand-over step of the parallel P4.  The step is the chain (window w + 1 takes a
-// position group when window w has published it) and its cost grows with the group: lists 5 wide test
-// five holder racks per position and at configs[4] nearly every orphan lands on the first or second
-// node of the group, so 2 positions (fill 3.4 ms) beat 4 (4.3) and 8 (5.2); at the headline shape
-// (lists 3 wide, rack-conflict stragglers walking a list of few nodes) 4 is best (365k against 360k
-// scenarios/s at 2 or 8).
-#ifndef KAS_P4_U
-#define KAS_P4_U 4
-#endif
-#ifndef KAS_P4_U_WIDE
-#define KAS_P4_U_WIDE 1
-#endif
-// (NC: chunk lists the orphans come in — the fill's wavefronts — where that is not the number of wavefronts running the
-// windows: kas_p4_kernel)
-// (fin != nullptr — first fit in the order kernel's workgroup, kas_p4_order_kernel, NW == 1: behind every finished window the word
-//  gets fin_hi | rows of the topic that are FINAL — every row below the next window's first orphan; the order wavefront of the
-//  same workgroup follows it)
-template <int W, int NW, int NC = NW>
-KAS_DEV void p4_lists_parallel(const LdsView& L, const TopicView& T, int32_t live_count, int32_t wave,
-                               int64_t (&st)[8], int32_t& fail_win, int32_t& fail_row, uint64_t* fin = nullptr, uint64_t fin_hi = 0ull) {
-  const int lane = kasw::lane();
-  uint64_t* prog = (uint64_t*)&L.ctl[KAS_CTL_PROG];
-  int32_t oc[NC], total = 0;
-#pragma unroll
-  for (int w = 0; w < NC; ++w) { oc[w] = L.ctl[KAS_CTL_OC + w]; total += oc[w]; }
-  // row index of the g-th orphan of the topic (chunk lists concatenated), or -1 past the end
-  // row index of the g-th orphan of the topic (chunk lists concatenated), or -1 past the end
-  auto orphan_row = [&](int32_t g) -> int32_t {
-    int32_t w = 0, base = 0;
-#pragma unroll
-    for (int k = 0; k < NC - 1; ++k) {
-      const bool next = w == k && g >= base + oc[k];
-      base += next ? oc[k] : 0;
-      w += next ? 1 : 0;
-    }
-    return g < total ? T.orph[((int64_t)chunk_begin<NC>(T.nt, w) << 6) + (g - base)] : -1;
-  };
-  auto row_cells = [&](int32_t p) -> MidRaw<W> {
-    return mid_load_raw<W>(T.mid, T.ow, p >= 0 ? p : 0, p >= 0, T.m32);
-  };
-  const int32_t n_win = (total + 63) >> 6;
-  // Window w may touch live-list positions [j, j + U) once EVERY earlier window is done with them.
-  // Waiting for window w - 1 alone is not enough: it may finish early (its orphans all placed on the
-  // first nodes) while window w - 2 still walks the list with an orphan whose racks were taken, and
-  // window w would then overtake that orphan and take a slot that is not its turn (round 2: one
-  // scenario solve in ~70,000 of the bench mix ended with a broker one over its cap).  Windows
-  // w - NW and earlier ran on this wave and are finished; lane d (1 <= d < NW) watches the wave that
-  // has window w - d.
-  const int32_t dw = (lane >= 1 && lane < NW) ? lane : 1;
-  const int32_t xw = (wave + NW - dw) % NW;
-  const int32_t cap = T.cap, mw = mid_width(T.ow);
-  constexpr int U = W >= 4 ? KAS_P4_U_WIDE : KAS_P4_U;      // node positions fetched per LDS round trip
-  int32_t p_nxt = orphan_row(64 * wave + lane);
-  MidRaw<W> c_nxt = row_cells(p_nxt);
-  for (int32_t w = wave; w < n_win; w += NW) {
-    const int32_t p = p_nxt;
-    int32_t c_cur[W];
-    mid_unpack<W>(c_nxt, T.ow, c_cur, T.m32);
-    p_nxt = orphan_row(64 * (w + NW) + lane);              // my next window's rows: read ahead
-    c_nxt = row_cells(p_nxt);
-    kasw::repoll();
-    if (kasw::ballot(L.ctl[KAS_CTL_FAILWIN] < w) != 0) break;   // an earlier window failed: so has the topic
-    int32_t hc = 0, hr[W];                                  // holders are a prefix of the row
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      hr[k] = (p >= 0 && c_cur[k] >= 0) ? (int32_t)lds_rack(L, c_cur[k]) : -1;
-      hc += (p >= 0 && c_cur[k] >= 0) ? 1 : 0;
-    }
-    int32_t need = p >= 0 ? T.rf - hc : 0;
-    int32_t j = kasw::shfl(L.ctl[KAS_CTL_HEAD], 0);
-    if (lane == 0) prog[wave] = ((uint64_t)(uint32_t)w << 32) | (uint32_t)j;
-    KAS_COUNT(st[4]);
-    bool stop = false;
-    bool placed = false;                                    // (dword mid rows) my row took a broker in this window
-    for (;;) {
-      uint64_t pend = kasw::ballot(need > 0);
-      if (pend == 0) break;
-      if (j >= live_count) {                                // KAS:183-184: this orphan cannot be placed
-        if (lane == 0) kasw::lds_atomic_min(&L.ctl[KAS_CTL_FAILWIN], w);
-        stop = true;
-        break;
-      }
-      // (the nodes of the position group and their racks do not change: read before the wait, so that what
-      // follows it — the chain from window to window — is one LDS round trip for the loads)
-      int32_t n[U], slots[U], rk[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) n[u] = (int32_t)L.live[j + u < live_count ? j + u : j];
-#pragma unroll
-      for (int u = 0; u < U; ++u) rk[u] = (int32_t)lds_rack(L, n[u]);
-      if (w > 0 && NW > 1) {                                // until every earlier window is done with [j, j + U)
-        const int32_t upto = j + U < live_count ? j + U : live_count;
-        const bool watch = lane >= 1 && lane < NW && w - dw >= 0;
-        const uint64_t want = ((uint64_t)(uint32_t)(w - dw) << 32) + (uint32_t)upto;
-        bool abandoned = false;
-        int32_t idle = 0;
-        for (;;) {
-          kasw::repoll();
-          if (kasw::ballot(watch && prog[xw] < want) == 0) break;
-          if (kasw::ballot(L.ctl[KAS_CTL_FAILWIN] < w) != 0) { abandoned = true; break; }
-          if (watchdog_poll((uint32_t*)&L.ctl[KAS_CTL_WATCHDOG], false, idle)) {
-            if (lane == 0) kasw::lds_atomic_min(&L.ctl[KAS_CTL_FAILWIN], -1);   // every later window stops
-            abandoned = true;
-            break;
-          }
-          // (no s_sleep between polls: the hand-over from window to window is the chain of P4, and the
-          // poll is one LDS read; in flight 362.4k against 358.2k scenarios/s with the pause in round 3, 634k against
-          // 653k in round 5)
-        }
-        if (abandoned) { stop = true; break; }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) slots[u] = cap - lds_load(L, n[u]);
-      int32_t taken[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        taken[u] = 0;
-        if (j + u < live_count && pend != 0) {             // wave-uniform
-          KAS_COUNT(st[5]);
-          if (slots[u] > 0) {
-            bool want = need > 0;
-#pragma unroll
-            for (int k = 0; k < W; ++k) want = want && !(k < hc && hr[k] == rk[u]);
-            const uint64_t wm = kasw::ballot(want);
-            if (wm != 0) {
-              const int32_t rank = kasw::count_below(wm);
-              if (want && rank < slots[u]) {               // accept (KAS:178-181)
-                if (W == 3 && T.m32) {                       // (dword mid rows: the row is stored again, sorted, when its window is through)
-                  put<W>(c_cur, hc, n[u]);
-                  placed = true;
-                } else {
-                  T.mid[(int64_t)p * mw + hc] = (uint16_t)n[u];
-                }
-                put<W>(hr, hc, rk[u]);
-                hc += 1;
-                need -= 1;
-              }
-              const int32_t takers = kasw::popc(wm);
-              taken[u] = takers < slots[u] ? takers : slots[u];
-              pend = kasw::ballot(need > 0);
-            }
-          }
-        }
-      }
-      if (lane == 0) {
-#pragma unroll
-        // (only this wave touches these nodes now: the new load follows from the slots read above, no re-read)
-        for (int u = 0; u < U; ++u) if (taken[u] > 0) lds_load(L, n[u]) = cap - slots[u] + taken[u];
-      }
-      kasw::lockstep();
-      j += U;
-      if (lane == 0) prog[wave] = ((uint64_t)(uint32_t)w << 32) | (uint32_t)(j < live_count ? j : live_count);
-    }
-    if constexpr (W == 3) {
-      if (T.m32 && placed) reinterpret_cast<uint32_t*>(T.mid)[p] = mid32_pack(c_cur[0], c_cur[1], c_cur[2]);
-    }
-    if (stop) {
-      // failed or abandoned: whoever waits on this window must not hang
-      if (j >= live_count) {
-        const uint64_t left = kasw::ballot(need > 0);
-        fail_win = w;
-        fail_row = kasw::shfl(p, left != 0 ? kasw::first_lane(left) : 0);
-      }
-      if (lane == 0) prog[wave] = (uint64_t)(uint32_t)(w + 1) << 32;
-      break;
-    }
-    // done: full nodes at the front of the live list need not be looked at again
-    if (lane == 0) {
-      int32_t head = L.ctl[KAS_CTL_HEAD];
-      while (head < live_count && lds_load(L, (int32_t)L.live[head]) >= cap) ++head;
-      kasw::lds_atomic_max(&L.ctl[KAS_CTL_HEAD], head);
-      prog[wave] = (uint64_t)(uint32_t)(w + 1) << 32;
-    }
-    if (fin != nullptr) {                                    // (wave-uniform) this window's mid-row cells are out: publish
-      const int32_t nxt0 = kasw::shfl(p_nxt, 0);             // the next window's first orphan (ascending rows), or none
-      kasw::wave_sync();                                     // (release: the stores above before the word)
-      if (lane == 0) kasw::store_shared_u64_lds(fin, fin_hi | (uint64_t)(uint32_t)(nxt0 >= 0 ? nxt0 : T.P));
-    }
-  }
+// ---- what the fill kernel, first fit (kas_first_fit.h) and the spread fill derive and write the same way ----
+// The topic as the phases see it.  orph and cap are the caller's to set.  m32c: the mid-row layout where the caller has it as a compile-time
+// constant (1: dword mid rows, 0: 16-bit rows), -1: what the launch's flags say.
+KAS_DEV TopicView topic_view(const KasLaunch& a, const kas_topic_desc& td, int32_t N, int m32c = -1) {
+  TopicView T;
+  T.c16 = cells16(a);
+  T.cur = topic_cur(a, td);
+  T.len_arr = td.cur_len_off >= 0 ? a.aux + td.cur_len_off : nullptr;
+  T.inp_arr = td.in_partitions_off >= 0 ? a.aux + td.in_partitions_off : nullptr;
+  T.pid_arr = td.part_id_off >= 0 ? a.aux + td.part_id_off : nullptr;
+  T.P = td.n_partitions; T.cw = td.cur_width; T.rf = td.rf; T.ow = td.out_width;
+  T.hash = td.name_hash; T.nt = (T.P + 63) >> 6; T.N = N;
+  T.mid = topic_mid(a, td);
+  T.m32 = m32c < 0 ? mid32(a) : (m32c != 0);
+  return T;
 }
+
+// Node table check: strictly ascending, non-negative ids; racks in int16 range.  This thread's share of the table (nodes first,
+// first + stride, ...): a workgroup gathers the answers through its LDS, one wavefront with a ballot.
+KAS_DEV bool nodes_bad(const int32_t* ids, const int32_t* racks, int32_t N, int32_t first, int32_t stride) {
+  bool bad = false;
+  for (int32_t i = first; i < N; i += stride) {
+    const int32_t id = ids[i];
+    const int32_t prev = i > 0 ? ids[i - 1] : -1;
+    const int32_t rk = racks[i];
+    bad = bad || id <= prev || rk < 0 || rk > 32767;
+  }
+  return bad;
+}
+
+// The broker id -> node index lookup of a node table: a direct table when the id range fits idmap_entries, else binary search.
+// (checked: the table has passed nodes_bad; the spread fill asks before that, and ids that do not ascend may give any range)
+KAS_DEV NodeMap node_map_of(const int32_t* ids, int32_t N, int32_t idmap_entries, bool checked) {
+  NodeMap nm;
+  nm.n = N; nm.min_id = 0; nm.range = 0u;
+  if (N > 0) {
+    const int64_t lo = ids[0], hi = ids[N - 1];
+    const int64_t range = hi - lo + 1;
+    nm.min_id = (int32_t)lo;
+    if ((checked || range >= 1) && range <= (int64_t)idmap_entries) nm.range = (uint32_t)range;
+  }
+  return nm;
+}
+
+// a KasLds layout carved out of the workgroup's LDS (dense node arrays; fill_scenario points load / ns / rs elsewhere)
+KAS_DEV LdsView lds_view(const KasLds& lay, unsigned char* lds_raw) {
+  LdsView L;
+  L.x = (int32_t*)(lds_raw + lay.off_x);
+  L.load = (int32_t*)(lds_raw + lay.off_load);
+  L.qrs = (int32_t*)(lds_raw + lay.off_qrs);
+  L.rack = (int16_t*)(lds_raw + lay.off_rack);
+  L.live = (int16_t*)(lds_raw + lay.off_live);
+  L.ns = 1; L.rs = 1;
+  L.idmap = (int16_t*)(lds_raw + lay.off_idmap);
+  L.ids = (int32_t*)(lds_raw + lay.off_ids);
+  L.ring_p = (int32_t*)(lds_raw + lay.off_ring);
+  L.ring_meta = L.ring_p + KAS_RING_CAP;
+  L.ring_rack = (int16_t*)(L.ring_meta + KAS_RING_CAP);
+  L.ctl = (int32_t*)(lds_raw + lay.off_ctl);
+  return L;
+}
+
+// the result records (one thread writes; digest 0: the order kernel completes it)
+KAS_DEV void put_topic_result(const KasLaunch& a, int32_t ti, const TopicOutcome& o) {
+  kas_topic_result tr;
+  tr.status = o.status; tr.fail_partition = o.fail_partition;
+  tr.moved_replicas = o.moved_replicas; tr.moved_partitions = o.moved_partitions;
+  a.topic_results[ti] = tr;
+}
+KAS_DEV void put_scenario_result(const KasLaunch& a, int32_t s, int32_t status, int32_t fail_topic, int32_t fail_partition,
+                                 int32_t moved_r, int32_t moved_p) {
+  kas_scenario_result sr;
+  sr.status = status; sr.fail_topic = fail_topic; sr.fail_partition = fail_partition;
+  sr.moved_replicas = moved_r; sr.moved_partitions = moved_p; sr.reserved = 0;
+  sr.digest = 0;
+  a.scenario_results[s] = sr;
+}
+
+}  // namespace kas
+
+#include "kas_first_fit.h"   // P4: the windows, the per-topic driver and kas_p4_kernel's scenario
+
+namespace kas {
 
 // ---------------------------------------------------------------------------------------------
 // P5 helpers
@@ -1432,6 +1323,51 @@ KAS_DEV void sort_holders(const int32_t (&cells)[W], int32_t (&h)[W], int32_t& L
   }
 }
 
+// ---- pieces of fill_topic ----
+// the end of phase k of kas_plan_stats(): its ticks since the previous mark
+KAS_DEV void phase_tick(int64_t (&st)[8], int k, int64_t& tmark) {
+  const int64_t now = kasw::clock_ticks();
+  st[k] += now - tmark;
+  tmark = now;
+}
+
+// this wavefront's movement counts of the row scans into the topic's sums (KAS_CTL_MOVED_R / _P; read behind a barrier)
+KAS_DEV void publish_moved(const LdsView& L, int32_t moved_r, int32_t moved_p) {
+  const int32_t mr = kasw::wave_sum(moved_r), mp = kasw::wave_sum(moved_p);
+  if (kasw::lane() == 0 && (mr | mp) != 0) {
+    kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_R], mr);
+    kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_P], mp);
+  }
+}
+
+// Pass B of the lane-order form reads ONE 16-bit word per cell: node index | r* << 14 (no node has index 0x3fff: the LDS ends at
+// 13,492 brokers; an id that is no broker keeps 0xffff).  The id table is rewritten to that — P4 works on node indices, the broker
+// ids are not looked up again for this topic — under the key the rows hold: the broker id (BY_ID), or the node index itself
+// (index rows).  Ends with the barrier pass B needs.
+template <int NT, bool BY_ID>
+KAS_DEV void pack_idmap_with_rstar(const LdsView& L, int32_t N, const int32_t* ids, int32_t min_id) {
+  for (int32_t i = kasw::tid(); i < N; i += NT)
+    L.idmap[BY_ID ? (uint32_t)ids[i] - (uint32_t)min_id : (uint32_t)i] =
+        (int16_t)(uint16_t)((uint32_t)i | (((uint32_t)lds_qrs(L, i) >> 28) << 14));
+  kasw::sync();
+}
+
+// Split first fit (KAS_FLAG_SPLIT_P4): a rack-diverse topic ends in the fill kernel here — loads, cap and the chunks' orphan counts
+// go to kas_p4_kernel, which runs P4 on a quarter of this workgroup's LDS and registers; the topic's result says OK until then.
+template <int NW>
+KAS_DEV void hand_over_to_p4(const LdsView& L, int32_t N, int32_t cap, int32_t* p4s, int32_t moved_r, int32_t moved_p,
+                             TopicOutcome& res, int64_t (&st)[8], int64_t& tmark) {
+  const int tid = kasw::tid();
+  for (int32_t i = tid; i < N; i += 64 * NW) p4s[KAS_P4S_HEAD + i] = lds_load(L, i);
+  if (tid == 0) { p4s[0] = 1; p4s[1] = cap; }
+  if (tid < NW) p4s[2 + tid] = L.ctl[KAS_CTL_OC + tid];
+  publish_moved(L, moved_r, moved_p);
+  kasw::sync();
+  phase_tick(st, 3, tmark);
+  res.moved_replicas = L.ctl[KAS_CTL_MOVED_R];
+  res.moved_partitions = L.ctl[KAS_CTL_MOVED_P];
+}
+
 // ---------------------------------------------------------------------------------------------
 // fill kernel: one topic == P0-P4 of one getRackAwareAssignment call (+ tickets).  Executed by
 // the whole workgroup.  Leaves the out rows holding node indices (holders in acceptance order,
@@ -1455,17 +1391,8 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
   const int32_t wave = kasw::wave_id();
   const uint64_t lt = kasw::lanemask_lt();
   const int32_t N = nm.n;
-  TopicView T;
-  T.c16 = cells16(a);
-  T.cur = topic_cur(a, td);
+  TopicView T = topic_view(a, td, N, M32C);
   T.orph = orph;
-  T.len_arr = td.cur_len_off >= 0 ? a.aux + td.cur_len_off : nullptr;
-  T.inp_arr = td.in_partitions_off >= 0 ? a.aux + td.in_partitions_off : nullptr;
-  T.pid_arr = td.part_id_off >= 0 ? a.aux + td.part_id_off : nullptr;
-  T.P = td.n_partitions; T.cw = td.cur_width; T.rf = td.rf; T.ow = td.out_width;
-  T.hash = td.name_hash; T.nt = (T.P + 63) >> 6; T.N = N;
-  T.mid = topic_mid(a, td);
-  T.m32 = M32C < 0 ? mid32(a) : (M32C != 0);
   const int32_t P = T.P, hash = T.hash;
 
   TopicOutcome res;
@@ -1511,12 +1438,12 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
   } else {
     for (int32_t i = tid; i < N; i += NT) L.ids[i] = g_node_id[i];
   }
-  if (tid < KAS_CTL_INTS) L.ctl[tid] = tid == KAS_CTL_FAILROW ? -1 : (tid == KAS_CTL_FAILWIN ? 0x7fffffff : 0);
+  first_fit_reset_ctl(L, tid);
   kasw::sync();
   if (nm.range != 0u)
     for (int32_t i = tid; i < N; i += NT) L.idmap[(uint32_t)g_node_id[i] - (uint32_t)nm.min_id] = (int16_t)i;
   kasw::sync();
-  { const int64_t now = kasw::clock_ticks(); st[0] += now - tmark; tmark = now; }
+  phase_tick(st, 0, tmark);
 
   // ---- P2: sticky fill (KAS:49, 101-131) ----------------------------------------------------
   if constexpr (SLIM) {
@@ -1530,29 +1457,15 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
     if (L.ctl[KAS_CTL_VIOL] != 0) { res.status = KAS_TOPIC_NEEDS_FULL_FILL; return res; }   // rows not rack-diverse: the general fill's case
     fill_quota_fused<W, NW>(L, T, tid);
     kasw::sync();
-    { const int64_t now = kasw::clock_ticks(); st[1] += now - tmark; tmark = now; }
-    for (int32_t i = tid; i < N; i += NT)                     // (pass B's one 16-bit word per cell: node index | r* << 14, as below)
-      L.idmap[(uint32_t)g_node_id[i] - (uint32_t)nm.min_id] =
-          (int16_t)(uint16_t)((uint32_t)i | (((uint32_t)lds_qrs(L, i) >> 28) << 14));
-    kasw::sync();
+    phase_tick(st, 1, tmark);
+    pack_idmap_with_rstar<NT, true>(L, N, g_node_id, nm.min_id);
     int32_t moved_r = 0, moved_p = 0;
     const int32_t oc = fill_pass_b<W, NW, true, true, true>(L, T, nm, wave, moved_r, moved_p, st);
     if (lane == 0) L.ctl[KAS_CTL_OC + wave] = oc;
     kasw::sync();
-    { const int64_t now = kasw::clock_ticks(); st[2] += now - tmark; tmark = now; }
+    phase_tick(st, 2, tmark);
     if (java_abs_mod(hash, N) < 0) { res.status = KAS_FAIL_HASH_INDEX; return res; }   // KAS:168 (workgroup-uniform)
-    for (int32_t i = tid; i < N; i += NT) p4s[KAS_P4S_HEAD + i] = lds_load(L, i);     // the hand-over to first fit, as below
-    if (tid == 0) { p4s[0] = 1; p4s[1] = cap; }
-    if (tid < NW) p4s[2 + tid] = L.ctl[KAS_CTL_OC + tid];
-    const int32_t mr = kasw::wave_sum(moved_r), mp = kasw::wave_sum(moved_p);
-    if (lane == 0 && (mr | mp) != 0) {
-      kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_R], mr);
-      kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_P], mp);
-    }
-    kasw::sync();
-    { const int64_t now = kasw::clock_ticks(); st[3] += now - tmark; tmark = now; }
-    res.moved_replicas = L.ctl[KAS_CTL_MOVED_R];
-    res.moved_partitions = L.ctl[KAS_CTL_MOVED_P];
+    hand_over_to_p4<NW>(L, N, cap, p4s, moved_r, moved_p, res, st, tmark);
     return res;
   } else {
   bool fast = false;
@@ -1588,14 +1501,12 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
       if (fused) {                                          // workgroup-uniform
         fill_quota_fused<W, NW>(L, T, tid);
         kasw::sync();
-        { const int64_t now = kasw::clock_ticks(); st[1] += now - tmark; tmark = now; }
+        phase_tick(st, 1, tmark);
         if (ixrows) {                                          // (workgroup-uniform)
           st[6] += 1;                                            // (kas_plan_stats()[6] of a fill launch: topics that took index rows)
           // pass B over the index rows pass A left in the mid region, as a topic of 16-bit cells whose node i has id i: the
           // table it looks into is node index -> node index | r* << 14 (the broker ids are not needed again for this topic)
-          for (int32_t i = tid; i < N; i += NT)
-            L.idmap[i] = (int16_t)(uint16_t)((uint32_t)i | (((uint32_t)lds_qrs(L, i) >> 28) << 14));
-          kasw::sync();
+          pack_idmap_with_rstar<NT, false>(L, N, nullptr, 0);
           TopicView T2 = T;
           T2.c16 = true;
           T2.cur = reinterpret_cast<const int32_t*>(T.mid);
@@ -1605,13 +1516,7 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
         }
         else if (a.flags & KAS_FLAG_LANE_ORDER) {              // (workgroup-uniform)
           if (nm.range != 0u) {
-            // pass B reads ONE 16-bit word per cell: node index | r* << 14 (no node has index 0x3fff: the LDS ends
-            // at 13,492 brokers; an id that is no broker keeps 0xffff) — the id table is not looked up again for
-            // this topic (P4 works on node indices)
-            for (int32_t i = tid; i < N; i += NT)
-              L.idmap[(uint32_t)g_node_id[i] - (uint32_t)nm.min_id] =
-                  (int16_t)(uint16_t)((uint32_t)i | (((uint32_t)lds_qrs(L, i) >> 28) << 14));
-            kasw::sync();
+            pack_idmap_with_rstar<NT, true>(L, N, g_node_id, nm.min_id);
             oc = fill_pass_b<W, NW, true, true, true>(L, T, nm, wave, moved_r, moved_p, st);
           } else {
             oc = fill_pass_b<W, NW, false, true, true>(L, T, nm, wave, moved_r, moved_p, st);
@@ -1633,57 +1538,31 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
         fill_chunk_prefix<NW>(L, T, tid);
         kasw::sync();
       }
-      { const int64_t now = kasw::clock_ticks(); st[1] += now - tmark; tmark = now; }
+      phase_tick(st, 1, tmark);
       oc = nm.range != 0u ? fill_pass_b<W, NW, true>(L, T, nm, wave, moved_r, moved_p, st)
                           : fill_pass_b<W, NW, false>(L, T, nm, wave, moved_r, moved_p, st);
     }
     if (lane == 0) L.ctl[KAS_CTL_OC + wave] = oc;
   } else if (wave == 0) {
     fill_generic_sweeps<W>(L, T, nm, accmask, st);
-    { const int64_t now = kasw::clock_ticks(); st[1] += now - tmark; tmark = now; }
+    phase_tick(st, 1, tmark);
   }
   kasw::sync();
-  { const int64_t now = kasw::clock_ticks(); st[2] += now - tmark; tmark = now; }
+  phase_tick(st, 2, tmark);
 
   // ---- KAS:168: getNodeProcessingOrder(topic, all nodes); runs even with zero orphans -------
   const int32_t idxN = java_abs_mod(hash, N);
   if (idxN < 0) { res.status = KAS_FAIL_HASH_INDEX; return res; }      // workgroup-uniform
-  // ---- split first fit (KAS_FLAG_SPLIT_P4): a rack-diverse topic ends here — the brokers' loads, the orphan counts of the
-  // chunks and cap go to kas_p4_kernel, which runs P4 (KAS:56, 162-186) on a quarter of this workgroup's LDS and registers
-  // and reports a partition that cannot be placed; the topic's result says OK until then
-  if (p4s != nullptr) {                                      // (workgroup-uniform)
+  if (p4s != nullptr) {                                      // (workgroup-uniform) split first fit
     if (fast) {
-      for (int32_t i = tid; i < N; i += NT) p4s[KAS_P4S_HEAD + i] = lds_load(L, i);
-      if (tid == 0) { p4s[0] = 1; p4s[1] = cap; }
-      if (tid < NW) p4s[2 + tid] = L.ctl[KAS_CTL_OC + tid];
-      const int32_t mr = kasw::wave_sum(moved_r), mp = kasw::wave_sum(moved_p);
-      if (lane == 0 && (mr | mp) != 0) {
-        kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_R], mr);
-        kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_P], mp);
-      }
-      kasw::sync();
-      { const int64_t now = kasw::clock_ticks(); st[3] += now - tmark; tmark = now; }
-      res.moved_replicas = L.ctl[KAS_CTL_MOVED_R];
-      res.moved_partitions = L.ctl[KAS_CTL_MOVED_P];
+      hand_over_to_p4<NW>(L, N, cap, p4s, moved_r, moved_p, res, st, tmark);
       return res;
     }
     if (tid == 0) p4s[0] = 0;                                // (the general fill: first fit below, in this workgroup)
   }
+  // ---- P3 + P4: orphans (KAS:52, 133-160) and first fit (KAS:56, 162-186): first_fit_topic's pieces around the general fill's
   if (wave == 0) {
-    const int32_t start = (N - idxN) % N;        // order[j] = sorted[(j + start) % N]
-    // non-full nodes in processing order (full nodes can never accept again)
-    int32_t live_count = 0;
-    for (int32_t base = 0; base < N; base += 64) {
-      const int32_t j = base + lane;
-      int32_t n = j + start; if (n >= N) n -= N;
-      const bool is_live = j < N && lds_load(L, n) < cap;
-      const uint64_t m = kasw::ballot(is_live);
-      if (is_live) L.live[live_count + kasw::count_below(m)] = (int16_t)n;
-      live_count += kasw::popc(m);
-    }
-    kasw::lockstep();
-    if (lane == 0) L.ctl[KAS_CTL_LIVE] = live_count;
-    // ---- P3 + P4: orphans (KAS:52, 133-160) and first fit (KAS:56, 162-186) -----------------
+    const int32_t live_count = first_fit_live_list(L, T, idxN);
     if (!fast) {
       const int32_t fail_row = p3p4_generic<W>(L, T, nm, accmask, live_count, moved_r, moved_p, st);
       if (lane == 0) L.ctl[KAS_CTL_FAILROW] = fail_row;
@@ -1691,29 +1570,14 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
   }
   if (fast) {                                                // workgroup-uniform: every wave takes windows
     kasw::sync();
-    int32_t fail_win = -1, fail_row = -1;
-    p4_lists_parallel<W, NW>(L, T, L.ctl[KAS_CTL_LIVE], wave, st, fail_win, fail_row);
-    kasw::sync();                                            // KAS_CTL_FAILWIN is final: its wave reports the row
-    if (fail_win >= 0 && fail_win == L.ctl[KAS_CTL_FAILWIN] && lane == 0) L.ctl[KAS_CTL_FAILROW] = fail_row;
-    if (KAS_SPIN_BOUND > 0 && L.ctl[KAS_CTL_WATCHDOG] != 0) { res.status = KAS_FAIL_WATCHDOG; return res; }   // workgroup-uniform
+    first_fit_windows<W, NW>(L, T, wave, st);
+    if (first_fit_hung(L)) { res.status = KAS_FAIL_WATCHDOG; return res; }   // workgroup-uniform
   }
-  {
-    const int32_t mr = kasw::wave_sum(moved_r), mp = kasw::wave_sum(moved_p);
-    if (lane == 0 && (mr | mp) != 0) {
-      kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_R], mr);
-      kasw::lds_atomic_add(&L.ctl[KAS_CTL_MOVED_P], mp);
-    }
-  }
+  publish_moved(L, moved_r, moved_p);
   kasw::sync();   // out rows of P3/P4 are visible to every wave; load/qrs are dead from here
-  { const int64_t now = kasw::clock_ticks(); st[3] += now - tmark; tmark = now; }
-  {
-    const int32_t fail_row = L.ctl[KAS_CTL_FAILROW];
-    if (fail_row >= 0) {                                       // KAS:183-184
-      res.status = KAS_FAIL_UNASSIGNABLE;
-      res.fail_partition = T.pid_arr ? T.pid_arr[fail_row] : fail_row;
-      return res;
-    }
-  }
+  phase_tick(st, 3, tmark);
+  const TopicOutcome ff = first_fit_outcome(L, T, false);
+  if (ff.status != KAS_OK) { res.status = ff.status; res.fail_partition = ff.fail_partition; return res; }
   res.moved_replicas = L.ctl[KAS_CTL_MOVED_R];
   res.moved_partitions = L.ctl[KAS_CTL_MOVED_P];
 
@@ -1736,50 +1600,28 @@ KAS_DEV void fill_scenario(const KasLaunch& a, int32_t s, unsigned char* lds_raw
   const KasLds lay = SLIM ? kas_fill_slim_lds(a.n_max, W, a.idmap_entries)
                           : kas_fill_lds_layout(a.n_max, W, NW, a.idmap_entries, a.need_bsearch,
                                                 (a.flags & KAS_FLAG_GENERIC_FILL) ? 0 : ((a.flags & KAS_FLAG_FUSED_HIST) ? 2 : 1));
-  LdsView L;
-  L.x = (int32_t*)(lds_raw + lay.off_x);
+  LdsView L = lds_view(lay, lds_raw);
   // (wide lists: load[] takes the place of histogram row NW of THIS scenario's node count once the
   // quota pass has consumed it, see kas_fill_lds_layout)
-  L.load = (W > NW && !(a.flags & (KAS_FLAG_GENERIC_FILL | KAS_FLAG_FUSED_HIST))) ? L.x + NW * N : (int32_t*)(lds_raw + lay.off_load);
-  L.qrs = (int32_t*)(lds_raw + lay.off_qrs);
-  L.rack = (int16_t*)(lds_raw + lay.off_rack);
-  L.live = (int16_t*)(lds_raw + lay.off_live);
+  L.load = (W > NW && !(a.flags & (KAS_FLAG_GENERIC_FILL | KAS_FLAG_FUSED_HIST))) ? L.x + NW * N : L.load;
   // fused layout: load, qrs and rack are words of the node's own block (kas_fill_lds_layout)
   L.ns = (W <= 3 && NW > 1 && (a.flags & KAS_FLAG_FUSED_HIST) && !(a.flags & KAS_FLAG_GENERIC_FILL)) ? kas_fused_block_words(W, NW) : 1;
   L.rs = L.ns > 1 ? 2 * L.ns : 1;
-  L.idmap = (int16_t*)(lds_raw + lay.off_idmap);
-  L.ids = (int32_t*)(lds_raw + lay.off_ids);
-  L.ring_p = (int32_t*)(lds_raw + lay.off_ring);
-  L.ring_meta = L.ring_p + KAS_RING_CAP;
-  L.ring_rack = (int16_t*)(L.ring_meta + KAS_RING_CAP);
-  L.ctl = (int32_t*)(lds_raw + lay.off_ctl);
 
   const int32_t* g_node_id = a.node_id + sd.node_off;
   const int32_t* g_node_rack = a.node_rack + sd.node_off;
 
   int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int64_t t_begin = kasw::clock_ticks();
-  // node table checks: strictly ascending, non-negative ids; racks in int16 range
-  bool bad = false;
-  for (int32_t i = tid; i < N; i += NT) {
-    const int32_t id = g_node_id[i];
-    const int32_t prev = i > 0 ? g_node_id[i - 1] : -1;
-    const int32_t rk = g_node_rack[i];
-    bad = bad || id <= prev || rk < 0 || rk > 32767;
-  }
+  const bool bad = nodes_bad(g_node_id, g_node_rack, N, tid, NT);
   if (tid == 0) L.ctl[KAS_CTL_VIOL] = 0;
   kasw::sync();
   if (kasw::ballot(bad) != 0 && kasw::lane() == 0) L.ctl[KAS_CTL_VIOL] = 1;
   kasw::sync();
-  const bool nodes_bad = L.ctl[KAS_CTL_VIOL] != 0;
+  const bool table_bad = L.ctl[KAS_CTL_VIOL] != 0;
   NodeMap nm;
   nm.n = N; nm.min_id = 0; nm.range = 0u;
-  if (N > 0 && !nodes_bad) {
-    const int64_t lo = g_node_id[0], hi = g_node_id[N - 1];
-    const int64_t range = hi - lo + 1;
-    nm.min_id = (int32_t)lo;
-    if (range <= (int64_t)a.idmap_entries) nm.range = (uint32_t)range;
-  }
+  if (N > 0 && !table_bad) nm = node_map_of(g_node_id, N, a.idmap_entries, true);
   kasw::sync();
 
   st[0] += kasw::clock_ticks() - t_begin;
@@ -1797,7 +1639,7 @@ KAS_DEV void fill_scenario(const KasLaunch& a, int32_t s, unsigned char* lds_raw
     TopicOutcome o;
     o.status = KAS_OK; o.fail_partition = -1; o.moved_replicas = 0; o.moved_partitions = 0;
     if (scen_status != KAS_OK) o.status = KAS_SKIPPED;                 // KAG:173-184 aborted
-    else if (nodes_bad) o.status = KAS_FAIL_BAD_NODES;
+    else if (table_bad) o.status = KAS_FAIL_BAD_NODES;
     else if (!(td.rf > 0)) o.status = KAS_FAIL_RF_NOT_POSITIVE;        // KTA:65-66
     else if (!(td.rf <= N)) o.status = KAS_FAIL_RF_GT_BROKERS;         // KTA:67-69
     else o = fill_topic<W, NW, SLIM, M32C>(a, td, L, nm, g_node_id, g_node_rack, accmask, orph_topic, p4s, st);
@@ -1814,21 +1656,12 @@ KAS_DEV void fill_scenario(const KasLaunch& a, int32_t s, unsigned char* lds_raw
       o.moved_replicas = 0; o.moved_partitions = 0;
       if (scen_status == KAS_OK) { scen_status = o.status; fail_topic = k; fail_part = o.fail_partition; }
     }
-    if (tid == 0) {
-      kas_topic_result tr;
-      tr.status = o.status; tr.fail_partition = o.fail_partition;
-      tr.moved_replicas = o.moved_replicas; tr.moved_partitions = o.moved_partitions;
-      a.topic_results[ti] = tr;
-    }
+    if (tid == 0) put_topic_result(a, ti, o);
     moved_r += o.moved_replicas; moved_p += o.moved_partitions;
     kasw::sync();
   }
   if (tid == 0) {
-    kas_scenario_result sr;
-    sr.status = scen_status; sr.fail_topic = fail_topic; sr.fail_partition = fail_part;
-    sr.moved_replicas = moved_r; sr.moved_partitions = moved_p; sr.reserved = 0;
-    sr.digest = 0;
-    a.scenario_results[s] = sr;
+    put_scenario_result(a, s, scen_status, fail_topic, fail_part, moved_r, moved_p);
     if (a.stats) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + i] = st[i];
@@ -1883,153 +1716,6 @@ KAS_DEV void fill_block(const KasLaunch& a, int32_t block, int32_t grid, unsigne
 }
 
 // ---------------------------------------------------------------------------------------------
-// kas_p4_kernel, one scenario (KAS_FLAG_SPLIT_P4): first fit (P4, KAS:56, 162-186) of the topics the fill kernel handed
-// over, in order, on four wavefronts — p4_lists_parallel exactly as the fill workgroup ran it, on the loads the sticky
-// fill left (KasLaunch::p4s), the topic's orphan lists and its mid rows.  A partition that cannot be placed fails its
-// topic (KAS:183-184), the topics behind it are skipped (KAG:173-184 aborted) and emit nothing, and the scenario's
-// record says so — what fill_scenario does when first fit runs inside it.
-// ---------------------------------------------------------------------------------------------
-// FS (kas_p4_order_kernel: first fit as ONE wavefront of the order kernel's workgroup, whatever its index there): the workgroup
-// barriers become wavefront barriers, and fs[] carries what the order wavefront follows —
-//   fs[0]  topic << 32 | rows of that topic that are final (first fit done with them; a topic that needs none: all its rows)
-//   fs[1]  the topic first fit failed at (KAS:183-184), or 0x7fffffff;  fs[2]  the order wavefront's answer: it has stopped writing
-// — and a failed topic's padding waits for that answer (the order wavefront may have emitted rows of it already).
-// (M32C: the mid-row layout as a compile-time constant, as in fill_topic — 1: dword mid rows, 0: 16-bit rows, -1: the launch's flags)
-template <int W, int PW, bool FS = false, int M32C = -1>
-KAS_DEV void p4_scenario(const KasLaunch& a, int32_t s, unsigned char* lds_raw, uint64_t* fs = nullptr) {
-  constexpr int NW = PW, NT = 64 * NW, NC = KAS_P4_WAVES;    // PW wavefronts run the windows over the fill's NC chunk lists
-  static_assert(!FS || PW == 1, "first fit inside the order kernel's workgroup is one wavefront");
-  const int lane = kasw::lane();
-  const int tid = FS ? lane : kasw::tid();
-  const int32_t wave = FS ? 0 : kasw::wave_id();
-  auto barrier = [&]() { if constexpr (FS) kasw::wave_sync(); else kasw::sync(); };
-  const kas_scenario_desc sd = a.scen[s];
-  const int32_t N = sd.n_nodes;
-  // (a scenario the fill kernel failed at topic k2 still has its rack-diverse topics before k2 waiting for their first fit)
-  const KasP4Lds lay = kas_p4_lds_layout(a.n_max);
-  LdsView L;
-  L.x = nullptr; L.qrs = nullptr; L.idmap = nullptr; L.ids = nullptr; L.ring_p = nullptr; L.ring_meta = nullptr; L.ring_rack = nullptr;
-  L.load = (int32_t*)(lds_raw + lay.off_load);
-  L.rack = (int16_t*)(lds_raw + lay.off_rack);
-  L.live = (int16_t*)(lds_raw + lay.off_live);
-  L.ctl = (int32_t*)(lds_raw + lay.off_ctl);
-  L.ns = 1; L.rs = 1;
-  const int32_t* g_node_rack = a.node_rack + sd.node_off;
-  const int64_t t_begin = kasw::clock_ticks();
-  int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t* orph = a.orph + a.orph_off[s];
-  bool failed = false;
-  int32_t fail_topic = -1, fail_part = -1, moved_r = 0, moved_p = 0;   // (moved: over the topics before a failure)
-  for (int32_t k = 0; k < sd.topic_count; ++k) {
-    const int32_t ti = sd.topic_begin + k;
-    const kas_topic_desc td = a.topics[ti];
-    int32_t* const orph_topic = orph;
-    orph += (int64_t)((td.n_partitions > 0 ? td.n_partitions : 0) + 63) / 64 * 64;
-    if (failed) {                                            // KAG:173-184 aborted: nothing is returned for this topic
-      // (FS: the order wavefront skips every topic behind fs[1] and never writes there)
-      out_pad(topic_out(a, td), (int64_t)td.n_partitions * td.out_width, tid, NT);
-      if (tid == 0) {
-        kas_topic_result tr;
-        tr.status = KAS_SKIPPED; tr.fail_partition = -1; tr.moved_replicas = 0; tr.moved_partitions = 0;
-        a.topic_results[ti] = tr;
-      }
-      continue;
-    }
-    const kas_topic_result tr0 = a.topic_results[ti];
-    moved_r += tr0.moved_replicas; moved_p += tr0.moved_partitions;
-    const int32_t* p4s = a.p4s + (int64_t)ti * (KAS_P4S_HEAD + a.n_max);
-    if (tr0.status != KAS_OK || p4s[0] == 0) {               // (workgroup-uniform: nothing handed over)
-      if constexpr (FS) {                                    // every row of the topic is final as the fill kernel left it
-        if (lane == 0) kasw::store_shared_u64_lds(&fs[0], ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)(td.n_partitions > 0 ? td.n_partitions : 0));
-      }
-      continue;
-    }
-    TopicView T;
-    T.c16 = cells16(a); T.cur = nullptr; T.orph = orph_topic; T.len_arr = nullptr; T.inp_arr = nullptr;
-    T.pid_arr = td.part_id_off >= 0 ? a.aux + td.part_id_off : nullptr;
-    T.P = td.n_partitions; T.cw = td.cur_width; T.rf = td.rf; T.ow = td.out_width;
-    T.hash = td.name_hash; T.nt = (T.P + 63) >> 6; T.N = N;
-    T.mid = topic_mid(a, td);
-    T.m32 = M32C < 0 ? mid32(a) : (M32C != 0);
-    T.cap = p4s[1];
-    const int32_t cap = T.cap;
-    barrier();                                            // (the previous topic's node state has been read)
-    for (int32_t i = tid; i < N; i += NT) { L.load[i] = p4s[KAS_P4S_HEAD + i]; L.rack[i] = (int16_t)g_node_rack[i]; }
-    if (tid < KAS_CTL_INTS) L.ctl[tid] = tid == KAS_CTL_FAILROW ? -1 : (tid == KAS_CTL_FAILWIN ? 0x7fffffff : 0);
-    barrier();
-    if (tid < NC) L.ctl[KAS_CTL_OC + tid] = p4s[2 + tid];
-    if (wave == 0) {                                         // non-full nodes in processing order (KAS:168, 188-200), as fill_topic
-      const int32_t idxN = java_abs_mod(T.hash, N);          // (>= 0: the fill kernel checked)
-      const int32_t start = (N - idxN) % N;
-      int32_t live_count = 0;
-      for (int32_t base = 0; base < N; base += 64) {
-        const int32_t j = base + lane;
-        int32_t n = j + start; if (n >= N) n -= N;
-        const bool is_live = j < N && lds_load(L, n) < cap;
-        const uint64_t m = kasw::ballot(is_live);
-        if (is_live) L.live[live_count + kasw::count_below(m)] = (int16_t)n;
-        live_count += kasw::popc(m);
-      }
-      kasw::lockstep();
-      if (lane == 0) L.ctl[KAS_CTL_LIVE] = live_count;
-    }
-    barrier();
-    int32_t fail_win = -1, fail_row = -1;
-    if constexpr (FS) {
-      // rows below the topic's first orphan are final already
-      const int32_t total_o = L.ctl[KAS_CTL_OC] + L.ctl[KAS_CTL_OC + 1] + L.ctl[KAS_CTL_OC + 2] + L.ctl[KAS_CTL_OC + 3];
-      int32_t first = T.P;
-      if (total_o > 0) {
-        int32_t w0 = 0;
-        while (w0 < NC - 1 && L.ctl[KAS_CTL_OC + w0] == 0) ++w0;
-        first = T.orph[(int64_t)chunk_begin<NC>(T.nt, w0) << 6];
-      }
-      if (lane == 0) kasw::store_shared_u64_lds(&fs[0], ((uint64_t)(uint32_t)k << 32) | (uint64_t)(uint32_t)first);
-      p4_lists_parallel<W, NW, NC>(L, T, L.ctl[KAS_CTL_LIVE], wave, st, fail_win, fail_row, &fs[0], (uint64_t)(uint32_t)k << 32);
-    } else {
-      p4_lists_parallel<W, NW, NC>(L, T, L.ctl[KAS_CTL_LIVE], wave, st, fail_win, fail_row);
-    }
-    barrier();                                            // KAS_CTL_FAILWIN is final: its wave reports the row
-    if (fail_win >= 0 && fail_win == L.ctl[KAS_CTL_FAILWIN] && lane == 0) L.ctl[KAS_CTL_FAILROW] = fail_row;
-    barrier();
-    const bool hung = KAS_SPIN_BOUND > 0 && L.ctl[KAS_CTL_WATCHDOG] != 0;
-    const int32_t frow = L.ctl[KAS_CTL_FAILROW];
-    if (hung || frow >= 0) {                                 // (workgroup-uniform)
-      failed = true; fail_topic = k;
-      fail_part = hung ? -1 : (T.pid_arr ? T.pid_arr[frow] : frow);
-      moved_r -= tr0.moved_replicas; moved_p -= tr0.moved_partitions;
-      if constexpr (FS) {
-        // the order wavefront may have emitted rows of this topic: it stops when it sees fs[1], says so in fs[2], and only
-        // then is the topic padded (bounded like every wait between wavefronts: kas_solver_body.h, "Hang containment")
-        if (lane == 0) kasw::store_shared_u64_lds(&fs[1], (uint64_t)(uint32_t)k);
-        int32_t idle = 0;
-        for (;;) {
-          kasw::repoll();
-          if (kasw::ballot(kasw::load_shared_u64_lds(&fs[2]) != 0ull) != 0ull) break;
-          if (watchdog_poll(reinterpret_cast<uint32_t*>(&fs[3]), false, idle)) break;
-        }
-      }
-      out_pad(topic_out(a, td), (int64_t)td.n_partitions * td.out_width, tid, NT);   // nothing is returned for a failed topic
-      if (tid == 0) {
-        kas_topic_result tr;
-        tr.status = hung ? KAS_FAIL_WATCHDOG : KAS_FAIL_UNASSIGNABLE; tr.fail_partition = fail_part;
-        tr.moved_replicas = 0; tr.moved_partitions = 0;
-        a.topic_results[ti] = tr;
-        kas_scenario_result sr;
-        sr.status = tr.status; sr.fail_topic = fail_topic; sr.fail_partition = fail_part;
-        sr.moved_replicas = moved_r; sr.moved_partitions = moved_p; sr.reserved = 0; sr.digest = 0;
-        a.scenario_results[s] = sr;
-      }
-    }
-  }
-  if constexpr (FS) {
-    kasw::wave_sync();                                       // (the records above before the word)
-    if (lane == 0) kasw::store_shared_u64_lds(&fs[0], (uint64_t)(uint32_t)sd.topic_count << 32);
-  }
-  if (tid == 0 && a.stats) a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + 3] += kasw::clock_ticks() - t_begin;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Spread fill.  One workgroup streams a 1M-row scenario in ~10 ms (four wavefronts, each waiting on
 // its own HBM round trips); the two row scans of the rack-diverse fill only meet at the quota, so for
 // batches of few large single-topic scenarios they run over `sp_chunks` one-wavefront workgroups per
@@ -2063,49 +1749,25 @@ KAS_DEV SpreadTopic spread_topic(const KasLaunch& a, int32_t s) {
   S.td = a.topics[S.ok ? sd.topic_begin : 0];
   const kas_topic_desc& td = S.td;
   TopicView& T = S.T;
-  T.c16 = false;                                          // (the spread fill is not launched for 16-bit cells)
-  T.cur = a.cur + td.cur_off;
-  T.orph = a.orph + a.orph_off[s];
+  T = topic_view(a, td, N, 0);                            // (the spread fill's kernels write 16-bit mid rows)
+  // what the row scans of this path are compiled for: int32 cells (it is not launched for 16-bit cells) and full rows (S.ok below)
+  T.c16 = false; T.cur = a.cur + td.cur_off; T.mid = mid_base(a.out + td.out_off, T.P, T.ow);
   T.len_arr = nullptr; T.inp_arr = nullptr;
-  T.pid_arr = td.part_id_off >= 0 ? a.aux + td.part_id_off : nullptr;
-  T.P = td.n_partitions; T.cw = td.cur_width; T.rf = td.rf; T.ow = td.out_width;
-  T.hash = td.name_hash; T.nt = (T.P + 63) >> 6; T.N = N;
-  T.mid = mid_base(a.out + td.out_off, T.P, T.ow);
+  T.orph = a.orph + a.orph_off[s];
   T.cap = S.ok ? max_replicas_per_node(N, T.P, T.rf) : 0;
   // rows exactly W wide without length / membership arrays (what the full-row stream reads), the
   // reference's pre-checks passed, a quota word that holds cap, a valid rotation (KAS:190)
   S.ok = S.ok && td.cur_width == W && td.out_width == W && td.cur_len_off < 0 && td.in_partitions_off < 0 &&
          td.rf > 0 && td.rf <= N && T.P > 0 && T.cap >= 0 && T.cap < (1 << 28) && java_abs_mod(td.name_hash, N) >= 0 &&
          !(a.flags & KAS_FLAG_GENERIC_FILL);
-  S.nm.n = N; S.nm.min_id = 0; S.nm.range = 0u;
-  if (N > 0) {
-    const int64_t lo = a.node_id[sd.node_off], hi = a.node_id[sd.node_off + N - 1];
-    const int64_t range = hi - lo + 1;
-    S.nm.min_id = (int32_t)lo;
-    if (range >= 1 && range <= (int64_t)a.idmap_entries) S.nm.range = (uint32_t)range;
-  }
+  S.nm = node_map_of(a.node_id + sd.node_off, N, a.idmap_entries, false);
   S.ok = S.ok && S.nm.range != 0u;            // (sparse ids: the one-workgroup kernel's binary search)
   return S;
 }
 
-// mode 0: the layout of the one-workgroup fill (spread_p4); 1, 2: the slim layouts of the scans (kas_spread_scan_lds)
-KAS_DEV LdsView spread_lds(const KasLaunch& a, unsigned char* lds_raw, int W, int NW, int mode = 0) {
-  const KasLds lay = mode == 0 ? kas_fill_lds_layout(a.n_max, W, NW, a.idmap_entries, a.need_bsearch, 1)
-                               : kas_spread_scan_lds(a.n_max, W, a.idmap_entries, a.need_bsearch, mode);
-  LdsView L;
-  L.x = (int32_t*)(lds_raw + lay.off_x);
-  L.load = (int32_t*)(lds_raw + lay.off_load);
-  L.qrs = (int32_t*)(lds_raw + lay.off_qrs);
-  L.rack = (int16_t*)(lds_raw + lay.off_rack);
-  L.live = (int16_t*)(lds_raw + lay.off_live);
-  L.ns = 1; L.rs = 1;
-  L.idmap = (int16_t*)(lds_raw + lay.off_idmap);
-  L.ids = (int32_t*)(lds_raw + lay.off_ids);
-  L.ring_p = (int32_t*)(lds_raw + lay.off_ring);
-  L.ring_meta = L.ring_p + KAS_RING_CAP;
-  L.ring_rack = (int16_t*)(L.ring_meta + KAS_RING_CAP);
-  L.ctl = (int32_t*)(lds_raw + lay.off_ctl);
-  return L;
+// mode 1, 2, 3: the slim layouts of pass A, pass B and first fit (spread_p4) — kas_spread_scan_lds
+KAS_DEV LdsView spread_lds(const KasLaunch& a, unsigned char* lds_raw, int W, int mode) {
+  return lds_view(kas_spread_scan_lds(a.n_max, W, a.idmap_entries, a.need_bsearch, mode), lds_raw);
 }
 
 // rack[] and the broker id -> node index table of a scenario (every thread of the workgroup; two barriers)
@@ -2121,31 +1783,19 @@ KAS_DEV void spread_node_tables(const KasLaunch& a, int32_t s, const LdsView& L,
   kasw::sync();
 }
 
-// node table checks of fill_scenario (strictly ascending non-negative ids, racks in int16 range)
-KAS_DEV bool spread_nodes_bad(const KasLaunch& a, int32_t s) {
-  const kas_scenario_desc sd = a.scen[s];
-  bool bad = false;
-  for (int32_t i = kasw::lane(); i < sd.n_nodes; i += 64) {
-    const int32_t id = a.node_id[sd.node_off + i];
-    const int32_t prev = i > 0 ? a.node_id[sd.node_off + i - 1] : -1;
-    const int32_t rk = a.node_rack[sd.node_off + i];
-    bad = bad || id <= prev || rk < 0 || rk > 32767;
-  }
-  return kasw::ballot(bad) != 0ull;
-}
-
 // phase A: one wavefront, chunk c of scenario s
 template <int W>
 KAS_DEV void spread_pass_a(const KasLaunch& a, int32_t s, int32_t c, unsigned char* lds_raw) {
   const int lane = kasw::lane();
   const int32_t CH = a.sp_chunks;
   SpreadTopic S = spread_topic<W>(a, s);
-  if (S.ok && spread_nodes_bad(a, s)) S.ok = false;               // (before the id table is built from it)
+  const int64_t node_off = a.scen[s].node_off;                    // fill_scenario's node table check, before the id table is built from it
+  if (S.ok && kasw::ballot(nodes_bad(a.node_id + node_off, a.node_rack + node_off, S.T.N, lane, 64)) != 0ull) S.ok = false;
   if (!S.ok) {
     if (lane == 0) a.sp_flag[s] = 1;
     return;
   }
-  const LdsView L = spread_lds(a, lds_raw, W, 1, 1);
+  const LdsView L = spread_lds(a, lds_raw, W, 1);
   const TopicView& T = S.T;
   const int32_t N = T.N;
   spread_node_tables(a, s, L, S.nm, 64);
@@ -2202,7 +1852,7 @@ KAS_DEV void spread_pass_b(const KasLaunch& a, int32_t s, int32_t c, unsigned ch
   if (a.sp_flag[s] != 0) return;                                 // (written by an earlier kernel: uniform)
   const int32_t CH = a.sp_chunks;
   SpreadTopic S = spread_topic<W>(a, s);
-  const LdsView L = spread_lds(a, lds_raw, W, 1, 2);
+  const LdsView L = spread_lds(a, lds_raw, W, 2);
   const TopicView& T = S.T;
   const int32_t N = T.N;
   spread_node_tables(a, s, L, S.nm, 64);
@@ -2228,21 +1878,19 @@ KAS_DEV void spread_pass_b(const KasLaunch& a, int32_t s, int32_t c, unsigned ch
 template <int W, int NW>
 KAS_DEV void spread_p4(const KasLaunch& a, int32_t s, unsigned char* lds_raw) {
   constexpr int NT = 64 * NW;
-  const int lane = kasw::lane();
   const int tid = kasw::tid();
-  const int32_t wave = kasw::wave_id();
   if (a.sp_flag[s] != 0) return;
   const int32_t CH = a.sp_chunks;
   SpreadTopic S = spread_topic<W>(a, s);
-  const LdsView L = spread_lds(a, lds_raw, W, NW, 3);
-  TopicView& T = S.T;
-  const int32_t N = T.N, cap = T.cap;
+  const LdsView L = spread_lds(a, lds_raw, W, 3);
+  const TopicView& T = S.T;
+  const int32_t N = T.N;
   const int64_t t_begin = kasw::clock_ticks();
   for (int32_t i = tid; i < N; i += NT) {
     lds_load(L, i) = a.sp_node[((int64_t)s * 2 + 0) * a.n_max + i];
     lds_rack(L, i) = (int16_t)a.node_rack[a.scen[s].node_off + i];
   }
-  if (tid < KAS_CTL_INTS) L.ctl[tid] = tid == KAS_CTL_FAILROW ? -1 : (tid == KAS_CTL_FAILWIN ? 0x7fffffff : 0);
+  first_fit_reset_ctl(L, tid);
   kasw::sync();
   // the chunks' orphan lists, moved together at the start of the scenario's list region (ascending, so
   // a list only ever moves down; 64 * NW entries at a time: read, barrier, write, barrier)
@@ -2262,36 +1910,9 @@ KAS_DEV void spread_p4(const KasLaunch& a, int32_t s, unsigned char* lds_raw) {
     total += len;
   }
   if (tid == 0) L.ctl[KAS_CTL_OC] = total;                      // one list: chunk 0 of p4_lists_parallel holds them all
-  // KAS:168 getNodeProcessingOrder + the non-full nodes in that order, as in fill_topic
-  const int32_t idxN = java_abs_mod(T.hash, N);
-  if (wave == 0) {
-    const int32_t start = (N - idxN) % N;
-    int32_t live_count = 0;
-    for (int32_t base = 0; base < N; base += 64) {
-      const int32_t j = base + lane;
-      int32_t n = j + start; if (n >= N) n -= N;
-      const bool is_live = j < N && lds_load(L, n) < cap;
-      const uint64_t m = kasw::ballot(is_live);
-      if (is_live) L.live[live_count + kasw::count_below(m)] = (int16_t)n;
-      live_count += kasw::popc(m);
-    }
-    kasw::lockstep();
-    if (lane == 0) L.ctl[KAS_CTL_LIVE] = live_count;
-  }
-  kasw::sync();
   int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t fail_win = -1, fail_row = -1;
-  p4_lists_parallel<W, NW>(L, T, L.ctl[KAS_CTL_LIVE], wave, st, fail_win, fail_row);
-  kasw::sync();
-  if (fail_win >= 0 && fail_win == L.ctl[KAS_CTL_FAILWIN] && lane == 0) L.ctl[KAS_CTL_FAILROW] = fail_row;
-  kasw::sync();
-  TopicOutcome o;
-  o.status = KAS_OK; o.fail_partition = -1; o.moved_replicas = oc[CH]; o.moved_partitions = oc[CH + 1];
-  if (KAS_SPIN_BOUND > 0 && L.ctl[KAS_CTL_WATCHDOG] != 0) o.status = KAS_FAIL_WATCHDOG;
-  else if (L.ctl[KAS_CTL_FAILROW] >= 0) {                       // KAS:183-184
-    o.status = KAS_FAIL_UNASSIGNABLE;
-    o.fail_partition = T.pid_arr ? T.pid_arr[L.ctl[KAS_CTL_FAILROW]] : L.ctl[KAS_CTL_FAILROW];
-  }
+  TopicOutcome o = first_fit_topic<W, NW>(L, T, st);             // (a valid rotation, KAS:190: spread_topic's S.ok)
+  o.moved_replicas = oc[CH]; o.moved_partitions = oc[CH + 1];
   if (o.status != KAS_OK) {                                     // nothing is returned for a failed topic
     int32_t* out = a.out + S.td.out_off;
     const int64_t cells = (int64_t)S.td.n_partitions * S.td.out_width;
@@ -2299,15 +1920,8 @@ KAS_DEV void spread_p4(const KasLaunch& a, int32_t s, unsigned char* lds_raw) {
     o.moved_replicas = 0; o.moved_partitions = 0;
   }
   if (tid == 0) {
-    kas_topic_result tr;
-    tr.status = o.status; tr.fail_partition = o.fail_partition;
-    tr.moved_replicas = o.moved_replicas; tr.moved_partitions = o.moved_partitions;
-    a.topic_results[S.ti] = tr;
-    kas_scenario_result sr;
-    sr.status = o.status; sr.fail_topic = o.status != KAS_OK ? 0 : -1; sr.fail_partition = o.fail_partition;
-    sr.moved_replicas = o.moved_replicas; sr.moved_partitions = o.moved_partitions; sr.reserved = 0;
-    sr.digest = 0;
-    a.scenario_results[s] = sr;
+    put_topic_result(a, S.ti, o);
+    put_scenario_result(a, s, o.status, o.status != KAS_OK ? 0 : -1, o.fail_partition, o.moved_replicas, o.moved_partitions);
     if (a.stats) {
       for (int i = 0; i < 8; ++i) a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + i] = 0;
       a.stats[(int64_t)s * KAS_STATS_PER_SCENARIO + 3] = kasw::clock_ticks() - t_begin;   // [3] P4 (with the list moves)
