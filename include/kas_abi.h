@@ -59,6 +59,8 @@
 extern "C" {
 #endif
 
+/* (the choose entries below — kas_rank_device, kas_choose_device / 16, kas_solve_host_choose / 16 — were added under
+ * version 6: purely additive, no existing struct, entry or behaviour changed) */
 #define KAS_ABI_VERSION 6
 
 /* Longest replica list the kernels keep in registers: max(cur_width, rf) <= KAS_MAX_WIDTH. */
@@ -377,6 +379,88 @@ int kas_solve_host_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_t
                           const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact);
 int kas_solve_host16_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
                             const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact);
+
+/* ---- choosing the best scenarios on the device (added under ABI v6) ------------------------------------------------
+ * A what-if caller compares the variants by their records and wants the rows of the best ones only.  A *criterion* is a
+ * non-negative int32 taken from a scenario's kas_scenario_result and kas_scenario_impact: */
+#define KAS_KEY_MOVED_REPLICAS     0  /* kas_scenario_result.moved_replicas                       */
+#define KAS_KEY_MOVED_PARTITIONS   1  /* kas_scenario_result.moved_partitions                     */
+#define KAS_KEY_LEADERS_MOVED      2  /* kas_scenario_impact.leaders_moved                        */
+#define KAS_KEY_DEPARTED_REPLICAS  3  /* kas_scenario_impact.departed_replicas                    */
+#define KAS_KEY_MAX_INBOUND        4  /* kas_scenario_impact.max_inbound                          */
+#define KAS_KEY_MAX_OUTBOUND       5  /* kas_scenario_impact.max_outbound                         */
+#define KAS_KEY_REPLICA_SPREAD     6  /* max_replicas_after - min_replicas_after                  */
+#define KAS_KEY_LEADER_SPREAD      7  /* max_leaders_after - min_leaders_after                    */
+#define KAS_KEY_MAX_REPLICAS_AFTER 8  /* kas_scenario_impact.max_replicas_after                   */
+#define KAS_KEY_MAX_LEADERS_AFTER  9  /* kas_scenario_impact.max_leaders_after                    */
+#define KAS_KEY_COUNT             10
+#define KAS_CHOOSE_MAX_KEYS        4
+
+/* What to rank by and how many to return.  The key of scenario s is (key[0](s), ..., key[n_keys - 1](s), s), compared
+ * lexicographically, smaller is better: the scenario index makes the order total and the result deterministic.  Only
+ * scenarios with kas_scenario_result.status == KAS_OK take part; n_ok is their number. */
+typedef struct kas_choose_spec {
+  int32_t n_keys;                       /* 1 .. KAS_CHOOSE_MAX_KEYS                                */
+  int32_t key[KAS_CHOOSE_MAX_KEYS];     /* KAS_KEY_*, most significant first                       */
+  int32_t k;                            /* scenarios to return, 0 <= k <= S; 0 ranks only          */
+} kas_choose_spec;
+
+/* Where a choice goes (device pointers for kas_choose_device / 16, host pointers for kas_solve_host_choose / 16):
+ *   rank[S]        number of OK scenarios with a smaller key; -1 for a scenario that is not OK
+ *   chosen[k]      chosen[j] = the scenario of rank j for j < min(k, n_ok), -1 for the remaining j < k
+ *   row_off[k+1]   prefix sum in cells: chosen scenario j has its topics' out rows, in descriptor order, packed exactly as
+ *                  kas_solve_host_select packs a selected scenario, at rows[row_off[j] .. row_off[j + 1])
+ *   node_off[k+1]  the same prefix sum in records for its block of n_nodes kas_node_impact records in nodes[]
+ *                  (entries of either array past min(k, n_ok) repeat the last offset)
+ *   n_ok[1]
+ *   rows           int32 cells (uint16 cells for the 16 forms), rows_cap cells of room
+ *   nodes          nodes_cap records of room
+ * Every entry of rank, chosen, row_off, node_off and n_ok is written; rows and nodes only below row_off[k] / node_off[k].
+ * The arrays a call writes must not be NULL: rank (S > 0), chosen (k > 0), row_off, node_off, n_ok, and rows / nodes where
+ * rows_cap / nodes_cap must be positive. */
+typedef struct kas_choice {
+  int32_t* rank;
+  int32_t* chosen;
+  int64_t* row_off;
+  int64_t* node_off;
+  int32_t* n_ok;
+  void*    rows;
+  int64_t  rows_cap;                    /* cells                                                   */
+  kas_node_impact* nodes;
+  int64_t  nodes_cap;                   /* records                                                 */
+} kas_choice;
+
+/* Rank n_scenarios records alone (device pointers; no plan): rank[S], chosen[spec->k] and n_ok[1] as above.  Asynchronous
+ * on `hip_stream` (NULL = the context's own stream); the records must be complete on that stream. */
+int kas_rank_device(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                    int32_t n_scenarios, const kas_choose_spec* spec, int32_t* rank, int32_t* chosen, int32_t* n_ok,
+                    void* hip_stream);
+
+/* Rank the plan's previous solve and impact pass (device_tables->scenario_results, device_impact->scenarios) and gather the
+ * chosen scenarios' rows (from device_tables->out) and node blocks (from device_impact->nodes) into device_choice.
+ * Asynchronous, and ordered behind that solve and impact pass as kas_impact_device is ordered behind a solve — except a plan's
+ * first choice, which first allocates and uploads (blocking copies) the plan's two small tables; later calls only enqueue.
+ * Refused with KAS_E_INVALID_ARG before any GPU work: the spec and capacities as kas_solve_host_choose refuses them, and
+ * pointers that are not aligned — rows and device_tables->out to the cell size, node records to 4 bytes, row_off / node_off
+ * to 8 (the gather copies with the widest accesses the two addresses share, at least 2 bytes wide).
+ * kas_choose_device16: the same for a plan of kas_plan_create16 (rows are uint16 cells). */
+int kas_choose_device(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                      const kas_choose_spec* spec, const kas_choice* device_choice, void* hip_stream);
+int kas_choose_device16(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                        const kas_choose_spec* spec, const kas_choice* device_choice, void* hip_stream);
+
+/* The what-if call that returns only the winners: the solve and the impact pass of kas_solve_host_impact for every
+ * scenario; every topic record, every scenario record and every kas_scenario_impact (host_impact->scenarios) come back, and
+ * so do rank[S] and chosen[k]; rows and node blocks come back for the chosen only, in host_choice.  host_tables->out and
+ * host_impact->nodes are not used and may be NULL.  The ranking is over the whole call, whatever scenario ranges the call is
+ * cut into.  kas_solve_host16_choose: 16-bit cells as kas_solve_host16 (rows are uint16 cells whichever cells the batch is
+ * solved on).  Refused with KAS_E_INVALID_ARG before any GPU work, in this order: n_keys outside 1..4; an unknown
+ * criterion; k < 0 or k > S; rows_cap below the packed size of the k largest scenarios; nodes_cap below the sum of the k
+ * largest n_nodes; a NULL array that the call writes. */
+int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                          const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact);
+int kas_solve_host16_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                            const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact);
 
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */

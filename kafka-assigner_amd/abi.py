@@ -174,7 +174,47 @@ class ImpactTables(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("scenarios", C.c_void_p)]
 
 
+# choosing the best scenarios on the device (kas_choose_spec / kas_choice): criterion name -> KAS_KEY_*
+KAS_CHOOSE_MAX_KEYS = 4
+KEY_NAMES = ("moved_replicas", "moved_partitions", "leaders_moved", "departed_replicas", "max_inbound", "max_outbound",
+             "replica_spread", "leader_spread", "max_replicas_after", "max_leaders_after")
+KEYS = {name: i for i, name in enumerate(KEY_NAMES)}
+(KAS_KEY_MOVED_REPLICAS, KAS_KEY_MOVED_PARTITIONS, KAS_KEY_LEADERS_MOVED, KAS_KEY_DEPARTED_REPLICAS, KAS_KEY_MAX_INBOUND,
+ KAS_KEY_MAX_OUTBOUND, KAS_KEY_REPLICA_SPREAD, KAS_KEY_LEADER_SPREAD, KAS_KEY_MAX_REPLICAS_AFTER, KAS_KEY_MAX_LEADERS_AFTER) = range(10)
+KAS_KEY_COUNT = 10
+CHOOSE_ENTRIES = ("kas_rank_device", "kas_choose_device", "kas_choose_device16", "kas_solve_host_choose", "kas_solve_host16_choose")
+
+
+class ChooseSpec(C.Structure):
+    _fields_ = [("n_keys", C.c_int32), ("key", C.c_int32 * KAS_CHOOSE_MAX_KEYS), ("k", C.c_int32)]
+
+
+class Choice(C.Structure):
+    _fields_ = [("rank", C.c_void_p), ("chosen", C.c_void_p), ("row_off", C.c_void_p), ("node_off", C.c_void_p),
+                ("n_ok", C.c_void_p), ("rows", C.c_void_p), ("rows_cap", C.c_int64), ("nodes", C.c_void_p),
+                ("nodes_cap", C.c_int64)]
+
+
+def choose_spec(keys, k: int) -> "ChooseSpec":
+    """kas_choose_spec from criterion names (KEY_NAMES) or KAS_KEY_* numbers; unknown names raise ValueError."""
+    keys = [keys] if isinstance(keys, (str, int)) else list(keys)
+    ids = []
+    for name in keys:
+        if isinstance(name, str):
+            if name not in KEYS:
+                raise ValueError("unknown criterion %r (one of %s)" % (name, ", ".join(KEY_NAMES)))
+            name = KEYS[name]
+        ids.append(int(name))
+    spec = ChooseSpec()
+    spec.n_keys = len(ids)
+    for i, v in enumerate(ids[:KAS_CHOOSE_MAX_KEYS]):
+        spec.key[i] = v
+    spec.k = int(k)
+    return spec
+
+
 assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32
+assert C.sizeof(ChooseSpec) == 24 and C.sizeof(Choice) == 72
 assert TOPIC_RESULT_DTYPE.itemsize == C.sizeof(TopicResult) == 16
 assert SCENARIO_RESULT_DTYPE.itemsize == C.sizeof(ScenarioResult) == 32
 assert TOPIC_DESC_DTYPE.itemsize == C.sizeof(TopicDesc) == 64

@@ -29,6 +29,7 @@
 #include "kas_launch_plan.h"   // which kernels a solve launches: the resolver the emulator shares
 #include "kas_host_call.h"     // what a host call does: ranges, cell width, buffer sizes, the plan cache's choice
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
+#include "kas_choose.h"   // ranking and gathering the best scenarios: its kernels are kas_choose.hip's
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -394,7 +395,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_COUNT];            // device pools, record staging, impact records (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_TOTAL];            // device pools, record staging, impact records, a choice and its staging (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -444,6 +445,10 @@ struct kas_plan {
   hipEvent_t ev_impact = nullptr;       // recorded behind the plan's last impact pass
   hipStream_t impact_stream = nullptr;
   int impact_pending = 0;               // ev_impact has been recorded
+  // choosing on the device (kas_choose_device / 16): the size and segment tables, built at the plan's first such call
+  int choose_ready = 0;
+  KasChoosePlan choose;
+  KasBuf b_ch_sizes, b_ch_segs;
 };
 
 static int kas_buf_reserve(KasBuf* b, size_t bytes, uint64_t* allocs, const char* what) {
@@ -609,7 +614,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_COUNT; ++i) {
+  for (int i = 0; i < KAS_HB_TOTAL; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -643,7 +648,7 @@ void kas_plan_destroy(kas_plan* p) {
   (void)hipStreamSynchronize(p->ctx->stream);
   if (p->last_slot >= 0) (void)hipEventSynchronize(p->ev_stop[p->last_slot]);
   if (p->impact_pending) (void)hipEventSynchronize(p->ev_impact);
-  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region}) kas_buf_free(b);
+  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs}) kas_buf_free(b);
   if (p->ev_impact) (void)hipEventDestroy(p->ev_impact);
   for (KasBuf* b : {&p->b_scen, &p->b_topics, &p->b_node_id, &p->b_node_rack, &p->b_accmask_off, &p->b_accmask,
                     &p->b_orph_off, &p->b_orph, &p->b_perm, &p->b_stats, &p->b_ord_flag, &p->b_sp_hist, &p->b_sp_quota,
@@ -720,7 +725,8 @@ static int kas_plan_build(kas_plan* p, const kas_batch_desc* batch) {
   // a rebuilt plan may still have its last solve in flight on some stream
   if (p->last_slot >= 0) KAS_HIP_TRY(hipEventSynchronize(p->ev_stop[p->last_slot]));
   if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));   // (its work list is about to go)
-  p->impact_ready = 0; p->impact_pending = 0;
+  p->impact_ready = 0; p->impact_pending = 0; p->choose_ready = 0;
+  kas_choose_plan_build(batch, &p->choose);                    // (host arithmetic over the descriptors: kas_choose_device refuses from it before any GPU work)
   p->shape = sh;
   p->Wc = sh.Wc; p->NW = sh.NW; p->G = sh.G;
   p->tickets = sh.tickets_ok; p->fused = sh.fused_ok;
@@ -1043,6 +1049,102 @@ int kas_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_t
   return kas_impact_impl(p, &t, imp, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
 }
 
+// ---- choosing the best scenarios (kernels: kas_choose.hip) --------------------------------------------------------------
+int kas_rank_device(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                    int32_t n_scenarios, const kas_choose_spec* spec, int32_t* rank, int32_t* chosen, int32_t* n_ok, void* hip_stream) {
+  if (!ctx) return set_error(KAS_E_INVALID_ARG, "ctx == NULL");
+  if (n_scenarios < 0) return set_error(KAS_E_INVALID_ARG, "n_scenarios < 0");
+  const char* bad = kas_choose_spec_error(spec, n_scenarios);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (!n_ok || (n_scenarios > 0 && (!scenario_results || !scenario_impact || !rank)) || (spec->k > 0 && !chosen))
+    return set_error(KAS_E_INVALID_ARG, "kas_rank_device: an array the call reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(ctx->device));
+  KasChooseLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.sr = scenario_results; a.si = scenario_impact;
+  kas_choose_fill_spec(&a, spec, n_scenarios);
+  a.rank = rank; a.chosen = chosen; a.n_ok = n_ok;
+  const int e = kas_rank_launch(&a, hip_stream ? hip_stream : (void*)ctx->stream);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("kas_rank_kernel: ") + hipGetErrorString((hipError_t)e));
+  return KAS_E_OK;
+}
+
+// The plan's size and segment tables (built on the host with the plan) on the device: allocated and uploaded at the plan's first
+// choice — blocking copies, once — and kept until the plan is rebuilt.
+static int kas_choose_prepare(kas_plan* p) {
+  if (p->choose_ready) return KAS_E_OK;
+  const KasChoosePlan& cp = p->choose;
+  int rc;
+  if ((rc = kas_buf_reserve(&p->b_ch_sizes, sizeof(KasChooseSize) * cp.sizes.size(), p->allocs, "choose size table")) != KAS_E_OK) return rc;
+  if ((rc = kas_buf_reserve(&p->b_ch_segs, sizeof(KasChooseSeg) * cp.segs.size(), p->allocs, "choose segment table")) != KAS_E_OK) return rc;
+  if (!cp.sizes.empty()) KAS_HIP_TRY(hipMemcpy(p->b_ch_sizes.p, cp.sizes.data(), sizeof(KasChooseSize) * cp.sizes.size(), hipMemcpyHostToDevice));
+  if (!cp.segs.empty()) KAS_HIP_TRY(hipMemcpy(p->b_ch_segs.p, cp.segs.data(), sizeof(KasChooseSeg) * cp.segs.size(), hipMemcpyHostToDevice));
+  p->choose_ready = 1;
+  return KAS_E_OK;
+}
+
+static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_choose_spec* spec,
+                           const kas_choice* ch, hipStream_t st) {
+  const int32_t S = p->n_scenarios;
+  const char* bad = kas_choose_spec_error(spec, S);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  const KasChoosePlan& cp = p->choose;
+  int64_t rows_need = 0, nodes_need = 0;
+  kas_choose_k_largest(cp, spec->k, &rows_need, &nodes_need);
+  if (ch->rows_cap < rows_need) return set_error(KAS_E_INVALID_ARG, "kas_choice: rows_cap below the packed rows of the k largest scenarios");
+  if (ch->nodes_cap < nodes_need) return set_error(KAS_E_INVALID_ARG, "kas_choice: nodes_cap below the node records of the k largest scenarios");
+  if ((S > 0 && !ch->rank) || (spec->k > 0 && !ch->chosen) || !ch->row_off || !ch->node_off || !ch->n_ok || (rows_need > 0 && !ch->rows) ||
+      (nodes_need > 0 && !ch->nodes))
+    return set_error(KAS_E_INVALID_ARG, "kas_choice: an array the call writes is NULL");
+  if (S > 0 && (!t->scenario_results || !imp->scenarios || (rows_need > 0 && !t->out) || (nodes_need > 0 && !imp->nodes)))
+    return set_error(KAS_E_INVALID_ARG, "a table the choice reads is NULL");
+  if (S > 0 && (p->last_slot < 0 || !p->impact_pending))
+    return set_error(KAS_E_INVALID_ARG, "kas_choose_device: the plan has no solve and impact pass to choose from");
+  const int32_t cell = p->cells16 ? 2 : 4;
+  if (((uintptr_t)ch->rows | (uintptr_t)t->out) % (uintptr_t)cell != 0 || ((uintptr_t)ch->nodes | (uintptr_t)imp->nodes) % 4 != 0 ||
+      ((uintptr_t)ch->row_off | (uintptr_t)ch->node_off) % 8 != 0)
+    return set_error(KAS_E_INVALID_ARG, "kas_choice: rows / out must be cell-aligned, node records 4-byte aligned, the offset arrays 8-byte aligned");
+  const int64_t chunks = kas_choose_chunks(cp, cell);
+  if ((int64_t)spec->k * chunks > INT32_MAX) return set_error(KAS_E_UNSUPPORTED, "kas_choice: k scenarios of this size are more than one gather launch takes");
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  const int rc = kas_choose_prepare(p);
+  if (rc != KAS_E_OK) return rc;
+  // ordered behind the plan's previous solve and its impact pass; a later solve waits for the gather as it waits for that pass
+  if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->impact_pending && p->impact_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
+  KasChooseLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.sr = t->scenario_results; a.si = imp->scenarios;
+  a.sizes = (const KasChooseSize*)p->b_ch_sizes.p; a.segs = (const KasChooseSeg*)p->b_ch_segs.p;
+  kas_choose_fill_spec(&a, spec, S);
+  a.rank = ch->rank; a.chosen = ch->chosen; a.row_off = ch->row_off; a.node_off = ch->node_off; a.n_ok = ch->n_ok;
+  a.out = t->out; a.src_nodes = imp->nodes; a.rows = ch->rows; a.nodes = ch->nodes;
+  a.src_cell = a.dst_cell = cell; a.chunks = (int32_t)chunks;
+  int e = kas_rank_launch(&a, st);
+  if (e == 0) e = kas_gather_launch(&a, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("choose kernels: ") + hipGetErrorString((hipError_t)e));
+  if (p->impact_pending) {
+    KAS_HIP_TRY(hipEventRecord(p->ev_impact, st));
+    p->impact_stream = st;
+  }
+  return KAS_E_OK;
+}
+
+int kas_choose_device(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_choose_spec* spec, const kas_choice* ch,
+                      void* hip_stream) {
+  if (!p || !t || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_choose_device16");
+  return kas_choose_impl(p, t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+int kas_choose_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const kas_choose_spec* spec, const kas_choice* ch,
+                        void* hip_stream) {
+  if (!p || !t16 || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_choose_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_choose_impl(p, &t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
 static int kas_plan_times(kas_plan* p, double* fill_us, double* order_us, int* launches) {
   *fill_us = 0.0; *order_us = 0.0; *launches = 0;
   KAS_HIP_TRY(hipSetDevice(p->ctx->device));
@@ -1308,7 +1410,8 @@ struct KasCellPool {
 // One host call: plan it (kas_host_call.h: validation, cell width, offsets, scenario ranges, buffer sizes), reserve, fetch the
 // ranges' plans, enqueue, drain, copy the records.
 static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select,
-                                 int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr) {
+                                 int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr,
+                                 const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1321,6 +1424,12 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   in.select = select; in.n_select = n_select;
   in.cells16 = c16 != nullptr; in.ident_ids = &ctx->ident_ids; in.ident_stamp = &ctx->ident_stamp;
   in.impact = himp != nullptr; in.have_imp_nodes = himp && himp->nodes; in.have_imp_scenarios = himp && himp->scenarios;
+  if (hch) {                                                   // kas_solve_host_choose / 16: rows and node blocks of the chosen only
+    in.choose = spec; in.rows_cap = hch->rows_cap; in.nodes_cap = hch->nodes_cap;
+    in.have_ch_rank = hch->rank != nullptr; in.have_ch_chosen = hch->chosen != nullptr; in.have_ch_row_off = hch->row_off != nullptr;
+    in.have_ch_node_off = hch->node_off != nullptr; in.have_ch_n_ok = hch->n_ok != nullptr;
+    in.have_ch_rows = hch->rows != nullptr; in.have_ch_nodes = hch->nodes != nullptr;
+  }
   in.lane_order_ok = ctx->lds_lane_order_ok;
   for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
   if (const char* e = getenv("KAS_HOST_RANGES")) in.ranges_override = atoi(e);
@@ -1339,7 +1448,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_COUNT; ++i)
+  for (int i = 0; i < KAS_HB_TOTAL; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -1446,8 +1555,48 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (i >= lag) download(i - lag);
   }
   for (int i = K - lag < 0 ? 0 : K - lag; i < K && he == hipSuccess && fail_rc == KAS_E_OK; ++i) download(i);
+  // a choice: rank and gather on s0 behind every range (one range: s0 solved it; several: their done events), then its header
+  const int64_t ch_k = hch ? spec->k : 0;
+  char* const d_head = (char*)ctx->hbuf[KAS_HB_CH_HEAD].p;
+  char* const p_head = (char*)ctx->hbuf[KAS_HB_CH_HEAD_PIN].p;
+  if (hch && he == hipSuccess && fail_rc == KAS_E_OK) {
+    const KasChoosePlan& cp = hc.choose;
+    if (!cp.sizes.empty()) copy(ctx->hbuf[KAS_HB_CH_SIZES].p, cp.sizes.data(), sizeof(KasChooseSize) * cp.sizes.size(), hipMemcpyHostToDevice, s0, "upload size table");
+    if (!cp.segs.empty()) copy(ctx->hbuf[KAS_HB_CH_SEGS].p, cp.segs.data(), sizeof(KasChooseSeg) * cp.segs.size(), hipMemcpyHostToDevice, s0, "upload segment table");
+    for (int i = 0; K > 1 && i < K; ++i) hip_ok(hipStreamWaitEvent(s0, ctx->hev_done[i], 0), "wait");
+    KasChooseLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.sr = d_sr; a.si = (const kas_scenario_impact*)ctx->hbuf[KAS_HB_IMP_SCEN].p;
+    a.sizes = (const KasChooseSize*)ctx->hbuf[KAS_HB_CH_SIZES].p; a.segs = (const KasChooseSeg*)ctx->hbuf[KAS_HB_CH_SEGS].p;
+    kas_choose_fill_spec(&a, spec, (int32_t)S);
+    a.row_off = (int64_t*)(d_head + hc.ch_head.row_off); a.node_off = (int64_t*)(d_head + hc.ch_head.node_off);
+    a.rank = (int32_t*)(d_head + hc.ch_head.rank); a.chosen = (int32_t*)(d_head + hc.ch_head.chosen); a.n_ok = (int32_t*)(d_head + hc.ch_head.n_ok);
+    a.out = native16 ? (const void*)d_out16 : (const void*)d_out;            // the pool the solve wrote
+    a.src_nodes = (const kas_node_impact*)ctx->hbuf[KAS_HB_IMP_NODES].p;
+    a.rows = ctx->hbuf[KAS_HB_CH_ROWS].p; a.nodes = (kas_node_impact*)ctx->hbuf[KAS_HB_CH_NODES].p;
+    a.src_cell = native16 ? 2 : 4; a.dst_cell = (int32_t)out.cell;            // (a widened call: narrowed on the way)
+    a.chunks = (int32_t)hc.ch_chunks;
+    if (he == hipSuccess) {
+      int e = kas_rank_launch(&a, s0);
+      if (e == 0) e = kas_gather_launch(&a, s0);
+      hip_ok((hipError_t)e, "choose kernels");
+    }
+    copy(p_head, d_head, hc.ch_head.bytes, hipMemcpyDeviceToHost, s0, "download the choice");
+  }
   drain();
   if (he != hipSuccess || fail_rc != KAS_E_OK) return fail_rc != KAS_E_OK ? fail_rc : KAS_E_HIP;
+  if (hch) {                                                   // exactly the chosen scenarios' rows and node blocks, through the staging
+    const int64_t cells = ((const int64_t*)(p_head + hc.ch_head.row_off))[ch_k], recs = ((const int64_t*)(p_head + hc.ch_head.node_off))[ch_k];
+    if (cells < 0 || cells > hc.ch_rows_need || recs < 0 || recs > hc.ch_nodes_need)
+      return set_error(KAS_E_HIP, "internal: the rank kernel left offsets beyond the k largest scenarios");
+    if (cells > 0) copy(ctx->hbuf[KAS_HB_CH_ROWS_PIN].p, ctx->hbuf[KAS_HB_CH_ROWS].p, out.cell * (size_t)cells, hipMemcpyDeviceToHost, s0, "download chosen rows");
+    if (recs > 0) copy(ctx->hbuf[KAS_HB_CH_NODES_PIN].p, ctx->hbuf[KAS_HB_CH_NODES].p, sizeof(kas_node_impact) * (size_t)recs, hipMemcpyDeviceToHost, s0, "download chosen node records");
+    if (S > 0) memcpy(hch->rank, p_head + hc.ch_head.rank, 4 * (size_t)S);
+    if (ch_k > 0) memcpy(hch->chosen, p_head + hc.ch_head.chosen, 4 * (size_t)ch_k);
+    memcpy(hch->row_off, p_head + hc.ch_head.row_off, 8 * (size_t)(ch_k + 1));
+    memcpy(hch->node_off, p_head + hc.ch_head.node_off, 8 * (size_t)(ch_k + 1));
+    memcpy(hch->n_ok, p_head + hc.ch_head.n_ok, 4);
+  }
   for (const KasHostRange& r : hc.ranges) {                    // (only what the ranges own: as the direct copies did)
     const KasExtent& t = r.own[KAS_POOL_TOPICS];
     if (t.hi > t.lo) memcpy(h->topic_results + t.lo, p_tr + t.lo, sizeof(kas_topic_result) * (size_t)(t.hi - t.lo));
@@ -1469,11 +1618,16 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     }
   }
   if (himp) {
-    const int64_t nodes = hc.imp_base[(size_t)S];
+    const int64_t nodes = hch ? 0 : hc.imp_base[(size_t)S];      // (a choice leaves the node table on the device)
     if (nodes > 0) copy(himp->nodes, ctx->hbuf[KAS_HB_IMP_NODES].p, sizeof(kas_node_impact) * (size_t)nodes, hipMemcpyDeviceToHost, s0, "download node impact");
     if (S > 0) copy(himp->scenarios, ctx->hbuf[KAS_HB_IMP_SCEN].p, sizeof(kas_scenario_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario impact");
   }
   hip_ok(hipStreamSynchronize(s0), "hipStreamSynchronize");
+  if (hch && he == hipSuccess) {
+    const int64_t cells = hch->row_off[ch_k], recs = hch->node_off[ch_k];
+    if (cells > 0) memcpy(hch->rows, ctx->hbuf[KAS_HB_CH_ROWS_PIN].p, out.cell * (size_t)cells);
+    if (recs > 0) memcpy(hch->nodes, ctx->hbuf[KAS_HB_CH_NODES_PIN].p, sizeof(kas_node_impact) * (size_t)recs);
+  }
   return he == hipSuccess ? KAS_E_OK : fail_rc;
 }
 
@@ -1509,6 +1663,22 @@ int kas_solve_host16_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas
   const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp);
+}
+
+int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,
+                          const kas_impact_tables* himp) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, spec, hch);
+}
+
+int kas_solve_host16_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_choose_spec* spec, const kas_choice* hch,
+                            const kas_impact_tables* himp) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, spec, hch);
 }
 
 int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_desc* batch, const kas_tables* h) {

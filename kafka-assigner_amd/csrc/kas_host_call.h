@@ -14,6 +14,7 @@
 
 #include "kas_plan_math.h"
 #include "kas_launch_plan.h"   // kas_cells16_ok, KAS_BUILT_*
+#include "kas_choose.h"        // the size and segment tables of kas_solve_host_choose
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -184,9 +185,16 @@ enum KasHostBuf {
   KAS_HB_TR, KAS_HB_SR,                             // result records on the device
   KAS_HB_TR_PIN, KAS_HB_SR_PIN,                     // ... and their pinned HOST staging
   KAS_HB_IMP_NODES, KAS_HB_IMP_SCEN,                // the impact records of kas_solve_host_impact / 16 on the device
-  KAS_HB_COUNT
+  KAS_HB_COUNT,                                     // the buffers any host call may use end here
+  // kas_solve_host_choose / 16 alone (behind KAS_HB_COUNT: whoever lists the buffers above still lists all of them)
+  KAS_HB_CH_SIZES = KAS_HB_COUNT, KAS_HB_CH_SEGS,   // the size and segment tables (kas_choose.h) on the device
+  KAS_HB_CH_HEAD, KAS_HB_CH_ROWS, KAS_HB_CH_NODES,  // row_off, node_off, rank, chosen, n_ok; the chosen scenarios' packed rows and node blocks
+  KAS_HB_CH_HEAD_PIN, KAS_HB_CH_ROWS_PIN, KAS_HB_CH_NODES_PIN,   // ... and their pinned HOST staging
+  KAS_HB_TOTAL
 };
-static inline bool kas_host_buf_pinned(int32_t id) { return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN; }
+static inline bool kas_host_buf_pinned(int32_t id) {
+  return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN;
+}
 
 // everything the decisions read
 struct KasHostCallIn {
@@ -199,10 +207,28 @@ struct KasHostCallIn {
   std::vector<int32_t>* ident_ids = nullptr;    // ... the identity id table of such a call and its stamp (kas_ident_batch): the context's
   uint64_t* ident_stamp = nullptr;
   bool impact = false, have_imp_nodes = false, have_imp_scenarios = false;   // kas_impact_tables
+  // kas_solve_host_choose / 16: rows and node blocks come back for the spec's k best scenarios only (n_select is then 0 and impact set)
+  const kas_choose_spec* choose = nullptr;
+  int64_t rows_cap = 0, nodes_cap = 0;          // kas_choice
+  bool have_ch_rank = false, have_ch_chosen = false, have_ch_row_off = false, have_ch_node_off = false, have_ch_n_ok = false,
+       have_ch_rows = false, have_ch_nodes = false;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
   KasHostCallIn() { for (uint32_t& m : built16) m = KAS_BUILT_ALL; }
+};
+
+// The header of a choice as it lies in KAS_HB_CH_HEAD and its staging: byte offsets, the int64 arrays first.
+struct KasChooseHead {
+  size_t row_off = 0, node_off = 0, rank = 0, chosen = 0, n_ok = 0, bytes = 0;
+  void lay_out(int64_t S, int64_t k) {
+    row_off = 0;
+    node_off = row_off + 8 * (size_t)(k + 1);
+    rank = node_off + 8 * (size_t)(k + 1);
+    chosen = rank + 4 * (size_t)S;
+    n_ok = chosen + 4 * (size_t)k;
+    bytes = n_ok + 4;
+  }
 };
 
 struct KasHostCall {
@@ -215,7 +241,12 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_COUNT] = {};              // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_TOTAL] = {};              // what to reserve of each buffer; 0: this call must not touch it
+  // kas_solve_host_choose / 16
+  KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
+  int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
+  int64_t ch_chunks = 0;                        // gather workgroups per chosen scenario
+  KasChooseHead ch_head;                        // where the arrays of the header lie in KAS_HB_CH_HEAD
 };
 
 // Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
@@ -272,8 +303,24 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.impact) {
     hc->imp_base.assign((size_t)S + 1, 0);
     for (int64_t s = 0; s < S; ++s) hc->imp_base[(size_t)s + 1] = hc->imp_base[(size_t)s] + (b->scenarios[s].n_nodes > 0 ? b->scenarios[s].n_nodes : 0);
-    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes))
+    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !in.choose))
       return fail(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
+  }
+  // a choice: the spec, then the room for any k scenarios (which ones win is not known before the solve), then the arrays
+  if (in.choose) {
+    const char* bad = kas_choose_spec_error(in.choose, S);
+    if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
+    const int64_t k = in.choose->k;
+    kas_choose_plan_build(b, &hc->choose);
+    kas_choose_k_largest(hc->choose, (int32_t)k, &hc->ch_rows_need, &hc->ch_nodes_need);
+    if (in.rows_cap < hc->ch_rows_need) return fail(KAS_E_INVALID_ARG, "kas_choice: rows_cap below the packed rows of the k largest scenarios");
+    if (in.nodes_cap < hc->ch_nodes_need) return fail(KAS_E_INVALID_ARG, "kas_choice: nodes_cap below the node records of the k largest scenarios");
+    if ((S > 0 && !in.have_ch_rank) || (k > 0 && !in.have_ch_chosen) || !in.have_ch_row_off || !in.have_ch_node_off || !in.have_ch_n_ok ||
+        (hc->ch_rows_need > 0 && !in.have_ch_rows) || (hc->ch_nodes_need > 0 && !in.have_ch_nodes))
+      return fail(KAS_E_INVALID_ARG, "kas_choice: an array the call writes is NULL");
+    hc->ch_chunks = kas_choose_chunks(hc->choose, in.cells16 ? 2 : 4);
+    if (k * hc->ch_chunks > INT32_MAX) return fail(KAS_E_UNSUPPORTED, "kas_choice: k scenarios of this size are more than one gather launch takes");
+    hc->ch_head.lay_out(S, k);
   }
   // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
   const int64_t cell = in.cells16 ? 2 : 4;                     // bytes of a cur / out cell as it travels
@@ -298,6 +345,13 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   by[KAS_HB_SR] = by[KAS_HB_SR_PIN] = sizeof(kas_scenario_result) * (size_t)(S + 1);
   by[KAS_HB_IMP_NODES] = in.impact ? sizeof(kas_node_impact) * (size_t)(hc->imp_base[(size_t)S] + 1) : 0;
   by[KAS_HB_IMP_SCEN] = in.impact ? sizeof(kas_scenario_impact) * (size_t)(S + 1) : 0;
+  if (in.choose) {
+    by[KAS_HB_CH_SIZES] = sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1);
+    by[KAS_HB_CH_SEGS] = sizeof(KasChooseSeg) * (hc->choose.segs.size() + 1);
+    by[KAS_HB_CH_HEAD] = by[KAS_HB_CH_HEAD_PIN] = hc->ch_head.bytes;
+    by[KAS_HB_CH_ROWS] = by[KAS_HB_CH_ROWS_PIN] = (size_t)cell * (size_t)(hc->ch_rows_need + 8);
+    by[KAS_HB_CH_NODES] = by[KAS_HB_CH_NODES_PIN] = sizeof(kas_node_impact) * (size_t)(hc->ch_nodes_need + 1);
+  }
   return KAS_E_OK;
 }
 

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -27,6 +28,7 @@ SYMBOLS = [
     "kas_shard_range", "kas_batch_slice", "kas_solve_host_sharded", "kas_ctx_lds_lane_order", "kas_solve_host16",
     "kas_plan_create16", "kas_solve_device16", "kas_resolve_replication_factor", "kas_failure_text",
     "kas_impact_device", "kas_impact_device16", "kas_solve_host_impact", "kas_solve_host16_impact",
+    "kas_rank_device", "kas_choose_device", "kas_choose_device16", "kas_solve_host_choose", "kas_solve_host16_choose",
 ]
 
 _LIB = None
@@ -121,6 +123,17 @@ def load():
     L.kas_solve_host16_impact.restype = C.c_int
     L.kas_solve_host16_impact.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables),
                                           C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.ImpactTables)]
+    L.kas_rank_device.restype = C.c_int
+    L.kas_rank_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.ChooseSpec), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]
+    for fn in (L.kas_choose_device, L.kas_choose_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.POINTER(abi.ChooseSpec),
+                       C.POINTER(abi.Choice), C.c_void_p]
+    for fn in (L.kas_solve_host_choose, L.kas_solve_host16_choose):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec),
+                       C.POINTER(abi.Choice), C.POINTER(abi.ImpactTables)]
     if L.kas_abi_version() != abi.KAS_ABI_VERSION:
         raise ImportError("libkas_hip.so ABI version mismatch")
     _LIB = L
@@ -230,6 +243,21 @@ class Plan:
         imp = abi.ImpactTables(nodes or None, scenarios or None)
         fn = self._lib.kas_impact_device16 if self.cells16 else self._lib.kas_impact_device
         _check(fn(self._h, C.byref(t), C.byref(imp), C.c_void_p(stream) if stream else None))
+
+    def choose_device(self, keys, k: int, out: int, scenario_results: int, nodes: int, scenarios: int, rank: int, chosen: int,
+                      row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int, choice_nodes: int, nodes_cap: int,
+                      stream: int = 0):
+        """kas_choose_device / 16: rank this plan's previous solve and impact pass by `keys` (criterion names, abi.KEY_NAMES)
+        and gather the k best scenarios' rows (from `out`) and node blocks (from `nodes`) into `rows` / `choice_nodes`.  Raw
+        device pointers (int): rank int32 [S], chosen int32 [k], row_off / node_off int64 [k + 1], n_ok int32 [1]."""
+        t = abi.Tables()
+        t.out = out or None; t.scenario_results = scenario_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        spec = abi.choose_spec(keys, k)
+        ch = abi.Choice(rank or None, chosen or None, row_off or None, node_off or None, n_ok or None, rows or None, int(rows_cap),
+                        choice_nodes or None, int(nodes_cap))
+        fn = self._lib.kas_choose_device16 if self.cells16 else self._lib.kas_choose_device
+        _check(fn(self._h, C.byref(t), C.byref(imp), C.byref(spec), C.byref(ch), C.c_void_p(stream) if stream else None))
 
     def set_flags(self, flags: int):
         _check(self._lib.kas_plan_set_flags(self._h, flags))
@@ -377,6 +405,76 @@ def solve_host_impact(fb: FlatBatch, select=None, cells16: bool = False, ctx: Op
     _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
               -1 if sel is None else int(sel.size), C.byref(imp)))
     return ho, nodes, scen
+
+
+def rank_device(scenario_results: int, scenario_impact: int, n_scenarios: int, keys, k: int, rank: int, chosen: int, n_ok: int,
+                stream: int = 0, ctx: Optional[DeviceContext] = None):
+    """kas_rank_device: rank n_scenarios records on the device by `keys` (criterion names, abi.KEY_NAMES).  Raw device pointers
+    (int): the two record arrays in, rank int32 [S], chosen int32 [k] and n_ok int32 [1] out.  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    spec = abi.choose_spec(keys, k)
+    _check(load().kas_rank_device(ctx._h, scenario_results or None, scenario_impact or None, int(n_scenarios), C.byref(spec),
+                                  rank or None, chosen or None, n_ok or None, C.c_void_p(stream) if stream else None))
+
+
+def packed_cells(fb: FlatBatch) -> np.ndarray:
+    """int64 [S]: cells of each scenario's out rows when packed (its topics' P x out_width, as kas_solve_host_select packs them)"""
+    per_topic = np.clip(fb.topics["n_partitions"], 0, None).astype(np.int64) * np.clip(fb.topics["out_width"], 0, None)
+    cum = np.concatenate([[0], np.cumsum(per_topic)])
+    b = fb.scen["topic_begin"].astype(np.int64)
+    c = np.clip(fb.scen["topic_count"], 0, None).astype(np.int64)
+    return np.where(c > 0, cum[np.minimum(b + c, fb.n_topics)] - cum[np.minimum(b, fb.n_topics)], 0).astype(np.int64)
+
+
+@dataclass
+class Choice:
+    """What kas_solve_host_choose leaves (include/kas_abi.h, kas_choice): rows holds row_off[k] cells, nodes node_off[k] records."""
+    rank: np.ndarray
+    chosen: np.ndarray
+    row_off: np.ndarray
+    node_off: np.ndarray
+    n_ok: int
+    rows: np.ndarray
+    nodes: np.ndarray
+    scenarios: np.ndarray                # every scenario's kas_scenario_impact
+
+
+def solve_host_choose(fb: FlatBatch, keys, k: int, cells16: bool = False, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_choose / kas_solve_host16_choose: every scenario is solved and reduced to its records on the GPU, which
+    also ranks them by `keys` (criterion names, abi.KEY_NAMES; smaller is better, the scenario index breaks ties); rows and
+    node impact records come back for the k best only.  Returns (HostOutputs without rows, Choice)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    spec = abi.choose_spec(keys, k)
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    S, kk = fb.n_scenarios, max(int(k), 0)
+    rows_cap = int(np.sort(packed_cells(fb))[::-1][:kk].sum())
+    nodes_cap = int(np.sort(np.clip(fb.scen["n_nodes"], 0, None).astype(np.int64))[::-1][:kk].sum())
+    c = Choice(rank=np.full(max(S, 1), -9, np.int32)[:S], chosen=np.full(max(kk, 1), -9, np.int32)[:kk],
+               row_off=np.full(kk + 1, -9, np.int64), node_off=np.full(kk + 1, -9, np.int64), n_ok=-9,
+               rows=np.zeros(max(rows_cap, 1), np.uint16 if cells16 else np.int32)[:rows_cap],
+               nodes=np.zeros(max(nodes_cap, 1), abi.NODE_IMPACT_DTYPE)[:nodes_cap],
+               scenarios=np.zeros(max(S, 1), abi.SCENARIO_IMPACT_DTYPE)[:S])
+    n_ok = np.full(1, -9, np.int32)
+
+    def p(a):
+        return a.ctypes.data if a.size else None
+    ch = abi.Choice(p(c.rank), p(c.chosen), p(c.row_off), p(c.node_off), p(n_ok), p(c.rows), rows_cap, p(c.nodes), nodes_cap)
+    imp = abi.ImpactTables(None, p(c.scenarios))
+    fn = L.kas_solve_host16_choose if cells16 else L.kas_solve_host_choose
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), C.byref(imp)))
+    c.n_ok = int(n_ok[0])
+    c.rows = c.rows[:int(c.row_off[kk])]
+    c.nodes = c.nodes[:int(c.node_off[kk])]
+    return ho, c
 
 
 def solve_host_sharded(fb: FlatBatch, ctxs) -> HostOutputs:

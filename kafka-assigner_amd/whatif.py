@@ -14,6 +14,10 @@ the same rows), so S variants cost S out tables but one cur table.
 With impact=True the same call also reduces every variant, on the GPU, to what it does to each broker (include/kas_abi.h,
 ABI v6): results[0].broker_impact() -> {broker: {"inbound": ..., ...}}, results[0].max_inbound, ...  rows=False leaves the
 variants' rows on the device (kas_solve_host_impact with n_select = 0): only records come back.
+
+best() lets the GPU also compare the variants (kas_solve_host_choose): plan.best(variants, k=3, by=("max_inbound",
+"moved_replicas")) returns the three best variants that solve, best first, each with its rows and its per-broker impact;
+nothing comes back for the others but their records.
 """
 from __future__ import annotations
 
@@ -54,11 +58,13 @@ class VariantResult:
     max_replicas_after: Optional[int] = None
     min_leaders_after: Optional[int] = None
     max_leaders_after: Optional[int] = None
+    rank: Optional[int] = None                   # best(): place among the variants that solve (0 = best); None from solve()
     _plan: "WhatIf" = field(repr=False, default=None)
     _index: int = field(repr=False, default=0)
     _out: np.ndarray = field(repr=False, default=None)
     _nodes: np.ndarray = field(repr=False, default=None)      # this variant's block of kas_node_impact records
     _node_ids: np.ndarray = field(repr=False, default=None)
+    _packed_at: Optional[int] = field(repr=False, default=None)   # best(): _out holds this variant's rows packed from here
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -71,7 +77,7 @@ class VariantResult:
         """partition -> new replica list of `topic` under this variant."""
         if self._out is None:
             raise ValueError("solve(..., rows=False) downloaded no rows: solve with rows=True to read an assignment")
-        return self._plan._rows(self._index, topic, self._out)
+        return self._plan._rows(self._index, topic, self._out, self._packed_at)
 
     def broker_impact(self) -> Dict[int, Dict[str, int]]:
         """broker id -> {replicas_before, replicas_after, leaders_before, leaders_after, inbound, outbound} under this
@@ -181,10 +187,42 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ho.out if rows else None, **extra))
         return res
 
-    def _rows(self, s: int, topic: str, out: np.ndarray) -> Dict[int, List[int]]:
+    def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved")) -> List[VariantResult]:
+        """The k best variants that solve, best first, chosen on the GPU (kas_solve_host_choose): variants are compared by the
+        criteria named in `by` (abi.KEY_NAMES; one to four, smaller is better, the earlier variant wins a tie).  Every variant is
+        solved and reduced to its records, but rows and per-broker impact come back for the winners only: each result has
+        assignment(), broker_impact() and its rank.  Fewer than k results when fewer variants solve."""
+        from . import native
+        by = [by] if isinstance(by, str) else list(by)
+        for name in by:
+            if name not in abi.KEYS:
+                raise ValueError("unknown criterion %r (one of %s)" % (name, ", ".join(abi.KEY_NAMES)))
+        if not 1 <= len(by) <= abi.KAS_CHOOSE_MAX_KEYS:
+            raise ValueError("by: one to four criteria")
+        fb = self.flat_batch(variants)
+        k = max(0, min(int(k), len(variants)))
+        ho, ch = native.solve_host_choose(fb, by, k)
+        self._fb = fb
+        res = []
+        for j in range(min(k, ch.n_ok)):
+            s = int(ch.chosen[j])
+            sr = ho.scenario_results[s]
+            off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
+            extra = {f: int(ch.scenarios[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
+            res.append(VariantResult(label=variants[s].label, status=int(sr["status"]), fail_topic=None,
+                                     fail_partition=int(sr["fail_partition"]), moved_replicas=int(sr["moved_replicas"]),
+                                     moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]), rank=j,
+                                     _plan=self, _index=s, _out=ch.rows, _packed_at=int(ch.row_off[j]),
+                                     _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
+                                     **extra))
+        return res
+
+    def _rows(self, s: int, topic: str, out: np.ndarray, packed_at: Optional[int] = None) -> Dict[int, List[int]]:
         t = self.topic_names.index(topic)
         td = self._fb.topics[s * len(self.topic_names) + t]
         P, ow, off = int(td["n_partitions"]), int(td["out_width"]), int(td["out_off"])
+        if packed_at is not None:                                          # (a scenario's topics are laid out back to back)
+            off = packed_at + off - int(self._fb.topics[s * len(self.topic_names)]["out_off"])
         rows = out[off:off + P * ow].reshape(P, ow)
         return {int(p): [int(b) for b in rows[i] if b >= 0] for i, p in enumerate(self.part_ids[t])
                 if (rows[i] >= 0).any()}
