@@ -59,6 +59,8 @@
 extern "C" {
 #endif
 
+/* (the moves entries below — kas_moves_device / 16, kas_solve_host_moves / 16, kas_solve_host_choose_moves / 16 — were added
+ * under version 6 as well: purely additive) */
 /* (the choose entries below — kas_rank_device, kas_choose_device / 16, kas_solve_host_choose / 16 — were added under
  * version 6: purely additive, no existing struct, entry or behaviour changed) */
 #define KAS_ABI_VERSION 6
@@ -461,6 +463,76 @@ int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_t
                           const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact);
 int kas_solve_host16_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
                             const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact);
+
+/* ---- the move list: a scenario's changed rows, compacted on the device (added under ABI v6) -------------------------
+ * A what-if caller acts on the rows that change.  With C and O of a row exactly as the impact section above defines them
+ * (the first clen cells of cur[p]; the cells of out[p] up to the first pad), and over topics whose kas_topic_result.status ==
+ * KAS_OK only (failed and skipped topics contribute nothing), a row has flags: */
+#define KAS_MOVE_REPLICAS 1   /* olen > 0 and set(O) != set(C)                                                  */
+#define KAS_MOVE_LEADER   2   /* olen > 0 and (clen == 0 or O[0] != C[0]): the row condition of leaders_moved   */
+#define KAS_MOVE_ORDER    4   /* olen > 0, set(O) == set(C), and O != C as lists                                */
+/* A row with olen == 0 has no flags and is never a move.  A row is a *move under mask m* iff flags & m != 0. */
+typedef struct kas_move {
+  int32_t topic;      /* index of the topic within the scenario, 0 .. topic_count-1          */
+  int32_t partition;  /* part_id[row], or the row index without a part_id array              */
+  uint8_t flags;      /* KAS_MOVE_* of the row (all of them, not only those in the mask)     */
+  uint8_t len;        /* olen                                                                 */
+  uint8_t gained;     /* cells of O not in C                                                  */
+  uint8_t lost;       /* cells of C not in O                                                  */
+  int32_t cell_at;    /* its list is cells[cell_off[j] + cell_at .. + len)                    */
+} kas_move;           /* 16 bytes */
+
+/* Where the moves of a list of n scenarios go (device pointers for kas_moves_device / 16, host pointers for the host forms).
+ * Listed scenario j owns moves[move_off[j] .. move_off[j + 1]) — its moves in (topic in descriptor order, row ascending)
+ * order — and cells[cell_off[j] .. cell_off[j + 1]): their new lists, packed without pads.  move_off and cell_off are always
+ * written in full and are the TRUE counts, whatever the capacities; a move is written iff its index is < moves_cap and its
+ * list ends at or before cells_cap, and nothing else in moves / cells is touched: a caller learns of truncation from
+ * move_off[n] > moves_cap or cell_off[n] > cells_cap.  The rows and the packed cells (sum of P x out_width) of the listed
+ * scenarios are always enough room.  A list entry of -1 is an empty slot (zero moves, the offsets repeat); a scenario may be
+ * listed twice, each listing gets a block of its own.  The result is deterministic: the same inputs give the same bytes.
+ * Refused with KAS_E_INVALID_ARG before any GPU work: mask outside 1..7, a NULL array the call writes, pointers that are not
+ * aligned (records 4 bytes, offsets 8, cells to the cell size).  A plan with a scenario whose packed cells reach 2^31 is
+ * refused with KAS_E_UNSUPPORTED (cell_at is an int32). */
+typedef struct kas_moves {
+  int32_t  mask;      /* 1..7 */
+  int32_t  reserved;
+  int64_t* move_off;  /* [n+1] prefix sum of moves per listed scenario  */
+  int64_t* cell_off;  /* [n+1] prefix sum of list cells                  */
+  kas_move* moves;  int64_t moves_cap;   /* records */
+  void*     cells;  int64_t cells_cap;   /* int32 broker ids, uint16 node indices in the 16 forms */
+} kas_moves;
+
+/* The moves of the plan's previous solve, from the tables it used.  select: a DEVICE array of n_select scenario indices (the
+ * chosen[] of a kas_choice is accepted as it is, with its -1 tail).  Asynchronous, and ordered behind the plan's previous
+ * solve as kas_impact_device is; a plan's first moves call allocates and uploads (blocking copies) the plan's small tables
+ * and its scratch, later calls only enqueue (a list longer than any before it grows the scratch).  kas_moves_device16: the
+ * same for a plan of kas_plan_create16 (cells are uint16 node indices). */
+int kas_moves_device(kas_plan* plan, const kas_tables* device_tables, const int32_t* select, int32_t n_select,
+                     const kas_moves* device_moves, void* hip_stream);
+int kas_moves_device16(kas_plan* plan, const kas_tables16* device_tables, const int32_t* select, int32_t n_select,
+                       const kas_moves* device_moves, void* hip_stream);
+
+/* The host call that returns moves instead of rows: the batch is solved, every topic record and scenario record comes back,
+ * no rows do (host_tables->out may be NULL), plus the moves of the scenarios in the HOST list select[0..n_select)
+ * (n_select < 0: every scenario, in order).  The offsets are copied back first, then exactly the records that were written
+ * — min(move_off[n], moves_cap) of them unless cells_cap cut the list earlier — and the cells they use, not the capacities.
+ * Refusals, in this order: what kas_solve_host_select refuses; mask outside 1..7; negative capacities; a NULL array that the
+ * call writes; misaligned pointers; a scenario index out of range; a scenario of 2^31 packed cells (KAS_E_UNSUPPORTED). */
+int kas_solve_host_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables, const int32_t* select,
+                         int32_t n_select, const kas_moves* host_moves);
+int kas_solve_host16_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables, const int32_t* select,
+                           int32_t n_select, const kas_moves* host_moves);
+
+/* Exactly kas_solve_host_choose / 16, except that host_choice->rows may be NULL with rows_cap == 0: then no rows are gathered
+ * (row_off is still the true prefix sum); with room given, rows come back as there.  The moves of the chosen come back in
+ * rank order (the list is chosen[0..k)).  The 16 form returns uint16 cells whichever cells the batch is solved on.  The
+ * moves refusals follow those of kas_solve_host_choose. */
+int kas_solve_host_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                                const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
+                                const kas_moves* host_moves);
+int kas_solve_host16_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                  const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
+                                  const kas_moves* host_moves);
 
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */

@@ -213,6 +213,38 @@ def choose_spec(keys, k: int) -> "ChooseSpec":
     return spec
 
 
+# the move list (kas_move / kas_moves): a row's flags, the 16-byte record, where a list goes
+KAS_MOVE_REPLICAS, KAS_MOVE_LEADER, KAS_MOVE_ORDER = 1, 2, 4
+MOVE_KINDS = {"replicas": KAS_MOVE_REPLICAS, "leader": KAS_MOVE_LEADER, "order": KAS_MOVE_ORDER}
+MOVE_DTYPE = _np.dtype([("topic", "<i4"), ("partition", "<i4"), ("flags", "u1"), ("len", "u1"), ("gained", "u1"), ("lost", "u1"),
+                        ("cell_at", "<i4")])
+MOVES_ENTRIES = ("kas_moves_device", "kas_moves_device16", "kas_solve_host_moves", "kas_solve_host16_moves",
+                 "kas_solve_host_choose_moves", "kas_solve_host16_choose_moves")
+
+
+class Move(C.Structure):
+    _fields_ = [("topic", C.c_int32), ("partition", C.c_int32), ("flags", C.c_uint8), ("len", C.c_uint8), ("gained", C.c_uint8),
+                ("lost", C.c_uint8), ("cell_at", C.c_int32)]
+
+
+class Moves(C.Structure):
+    _fields_ = [("mask", C.c_int32), ("reserved", C.c_int32), ("move_off", C.c_void_p), ("cell_off", C.c_void_p),
+                ("moves", C.c_void_p), ("moves_cap", C.c_int64), ("cells", C.c_void_p), ("cells_cap", C.c_int64)]
+
+
+def move_mask(kinds) -> int:
+    """KAS_MOVE_* mask from kind names (MOVE_KINDS: replicas, leader, order) or a mask number; unknown names raise ValueError."""
+    if isinstance(kinds, int):
+        return int(kinds)
+    mask = 0
+    for name in ([kinds] if isinstance(kinds, str) else list(kinds)):
+        if name not in MOVE_KINDS:
+            raise ValueError("unknown kind of move %r (one of %s)" % (name, ", ".join(MOVE_KINDS)))
+        mask |= MOVE_KINDS[name]
+    return mask
+
+
+assert MOVE_DTYPE.itemsize == C.sizeof(Move) == 16 and C.sizeof(Moves) == 56
 assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32
 assert C.sizeof(ChooseSpec) == 24 and C.sizeof(Choice) == 72
 assert TOPIC_RESULT_DTYPE.itemsize == C.sizeof(TopicResult) == 16

@@ -30,6 +30,7 @@
 #include "kas_host_call.h"     // what a host call does: ranges, cell width, buffer sizes, the plan cache's choice
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
 #include "kas_choose.h"   // ranking and gathering the best scenarios: its kernels are kas_choose.hip's
+#include "kas_moves.h"    // the move list of a solve: its kernels are kas_moves.hip's
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -395,7 +396,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_TOTAL];            // device pools, record staging, impact records, a choice and its staging (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_ALL];              // device pools, record staging, impact records, a choice and its staging, a move list (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -449,6 +450,14 @@ struct kas_plan {
   int choose_ready = 0;
   KasChoosePlan choose;
   KasBuf b_ch_sizes, b_ch_segs;
+  // the move list on the device (kas_moves_device / 16): the scenario and segment tables are built on the host with the plan and
+  // uploaded at the plan's first such call, with the (listed scenario, item) scratch
+  int moves_ready = 0;
+  KasMovesPlan moves;
+  KasBuf b_mv_scen, b_mv_segs, b_mv_scratch;
+  hipEvent_t ev_moves = nullptr;        // recorded behind the plan's last moves pass: it reads the tables a later solve rewrites
+  hipStream_t moves_stream = nullptr;
+  int moves_pending = 0;
 };
 
 static int kas_buf_reserve(KasBuf* b, size_t bytes, uint64_t* allocs, const char* what) {
@@ -614,7 +623,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_TOTAL; ++i) {
+  for (int i = 0; i < KAS_HB_ALL; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -648,6 +657,9 @@ void kas_plan_destroy(kas_plan* p) {
   (void)hipStreamSynchronize(p->ctx->stream);
   if (p->last_slot >= 0) (void)hipEventSynchronize(p->ev_stop[p->last_slot]);
   if (p->impact_pending) (void)hipEventSynchronize(p->ev_impact);
+  if (p->moves_pending) (void)hipEventSynchronize(p->ev_moves);
+  for (KasBuf* b : {&p->b_mv_scen, &p->b_mv_segs, &p->b_mv_scratch}) kas_buf_free(b);
+  if (p->ev_moves) (void)hipEventDestroy(p->ev_moves);
   for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs}) kas_buf_free(b);
   if (p->ev_impact) (void)hipEventDestroy(p->ev_impact);
   for (KasBuf* b : {&p->b_scen, &p->b_topics, &p->b_node_id, &p->b_node_rack, &p->b_accmask_off, &p->b_accmask,
@@ -725,7 +737,9 @@ static int kas_plan_build(kas_plan* p, const kas_batch_desc* batch) {
   // a rebuilt plan may still have its last solve in flight on some stream
   if (p->last_slot >= 0) KAS_HIP_TRY(hipEventSynchronize(p->ev_stop[p->last_slot]));
   if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));   // (its work list is about to go)
-  p->impact_ready = 0; p->impact_pending = 0; p->choose_ready = 0;
+  if (p->moves_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_moves));
+  p->impact_ready = 0; p->impact_pending = 0; p->choose_ready = 0; p->moves_ready = 0; p->moves_pending = 0;
+  kas_moves_plan_build(batch, &p->moves);
   kas_choose_plan_build(batch, &p->choose);                    // (host arithmetic over the descriptors: kas_choose_device refuses from it before any GPU work)
   p->shape = sh;
   p->Wc = sh.Wc; p->NW = sh.NW; p->G = sh.G;
@@ -910,6 +924,8 @@ static int kas_solve_device_impl(kas_plan* p, const kas_tables* t, void* hip_str
     KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
   if (p->impact_pending && p->impact_stream != st)           // (... and behind an impact pass that reads the tables it rewrites)
     KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
+  if (p->moves_pending && p->moves_stream != st)             // (... and a moves pass: the same)
+    KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_moves, 0));
   p->last_stream = st;
   a.n_scenarios = p->n_scenarios; a.n_max = p->shape.n_max;
   a.idmap_entries = p->shape.idmap_entries; a.need_bsearch = p->shape.need_bsearch;
@@ -1143,6 +1159,71 @@ int kas_choose_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_t
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_choose_device16 needs a plan of kas_plan_create16");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_choose_impl(p, &t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+// ---- the move list (kernels: kas_moves.hip) ----------------------------------------------------------------------------
+static int kas_moves_impl(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_moves* mv, hipStream_t st) {
+  const int32_t cell = p->cells16 ? 2 : 4;
+  const char* bad = kas_moves_args_error(mv, cell);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (n_select < 0 || (n_select > 0 && !select)) return set_error(KAS_E_INVALID_ARG, "kas_moves_device: select == NULL / n_select < 0");
+  if (((uintptr_t)t->cur | (uintptr_t)t->out) % (uintptr_t)cell != 0 || (uintptr_t)select % 4 != 0)
+    return set_error(KAS_E_INVALID_ARG, "kas_moves_device: cur / out must be cell-aligned, select 4-byte aligned");
+  const KasMovesPlan& mp = p->moves;
+  bad = kas_moves_shape_error(mp, n_select);
+  if (bad[0]) return set_error(KAS_E_UNSUPPORTED, bad);
+  if (p->n_scenarios > 0 && (!t->out || !t->topic_results || (p->shape.cur_need > 0 && !t->cur) || (p->shape.aux_need > 0 && !t->aux)))
+    return set_error(KAS_E_INVALID_ARG, "a table the moves pass reads is NULL");
+  if (p->n_scenarios > 0 && p->last_slot < 0) return set_error(KAS_E_INVALID_ARG, "kas_moves_device: the plan has no solve to list the moves of");
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  int rc;
+  if (!p->moves_ready) {                                        // blocking copies, once: the plan's tables
+    if ((rc = kas_buf_reserve(&p->b_mv_scen, sizeof(KasMovesScen) * mp.scen.size(), p->allocs, "moves scenario table")) != KAS_E_OK) return rc;
+    if ((rc = kas_buf_reserve(&p->b_mv_segs, sizeof(KasMovesSeg) * mp.segs.size(), p->allocs, "moves segment table")) != KAS_E_OK) return rc;
+    if (!mp.scen.empty()) KAS_HIP_TRY(hipMemcpy(p->b_mv_scen.p, mp.scen.data(), sizeof(KasMovesScen) * mp.scen.size(), hipMemcpyHostToDevice));
+    if (!mp.segs.empty()) KAS_HIP_TRY(hipMemcpy(p->b_mv_segs.p, mp.segs.data(), sizeof(KasMovesSeg) * mp.segs.size(), hipMemcpyHostToDevice));
+    if (!p->ev_moves) KAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_moves, hipEventDisableTiming));
+    p->moves_ready = 1;
+  }
+  // the (listed scenario, item) table: sized at the first call for a list as long as the batch; a longer list grows it, behind
+  // the pass that may still be using it
+  const size_t entries = (size_t)(n_select > p->n_scenarios ? n_select : p->n_scenarios) * (size_t)mp.max_items + 1;
+  if (sizeof(KasMovesCount) * entries > p->b_mv_scratch.cap) {
+    if (p->moves_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_moves));
+    if ((rc = kas_buf_reserve(&p->b_mv_scratch, sizeof(KasMovesCount) * entries, p->allocs, "moves scratch")) != KAS_E_OK) return rc;
+  }
+  // ordered behind the plan's previous solve and its previous moves pass (the scratch is the plan's)
+  if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->moves_pending && p->moves_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_moves, 0));
+  KasMovesLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.scen = (const KasMovesScen*)p->b_mv_scen.p; a.segs = (const KasMovesSeg*)p->b_mv_segs.p;
+  a.select = select;
+  a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.topic_results = t->topic_results;
+  a.scratch = (KasMovesCount*)p->b_mv_scratch.p;
+  a.move_off = mv->move_off; a.cell_off = mv->cell_off; a.moves = mv->moves; a.cells = mv->cells;
+  a.moves_cap = mv->moves_cap; a.cells_cap = mv->cells_cap;
+  a.n = n_select; a.stride = mp.max_items; a.S = p->n_scenarios; a.mask = mv->mask;
+  a.src16 = a.dst16 = p->cells16;
+  const int e = kas_moves_launch(&a, p->Wc, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("moves pass: ") + hipGetErrorString((hipError_t)e));
+  KAS_HIP_TRY(hipEventRecord(p->ev_moves, st));
+  p->moves_stream = st;
+  p->moves_pending = 1;
+  return KAS_E_OK;
+}
+
+int kas_moves_device(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_moves* mv, void* hip_stream) {
+  if (!p || !t || !mv) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_moves_device16");
+  return kas_moves_impl(p, t, select, n_select, mv, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+int kas_moves_device16(kas_plan* p, const kas_tables16* t16, const int32_t* select, int32_t n_select, const kas_moves* mv, void* hip_stream) {
+  if (!p || !t16 || !mv) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_moves_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_moves_impl(p, &t, select, n_select, mv, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
 }
 
 static int kas_plan_times(kas_plan* p, double* fill_us, double* order_us, int* launches) {
@@ -1411,7 +1492,8 @@ struct KasCellPool {
 // ranges' plans, enqueue, drain, copy the records.
 static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select,
                                  int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr,
-                                 const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr) {
+                                 const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
+                                 bool rows_optional = false) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1429,6 +1511,10 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.have_ch_rank = hch->rank != nullptr; in.have_ch_chosen = hch->chosen != nullptr; in.have_ch_row_off = hch->row_off != nullptr;
     in.have_ch_node_off = hch->node_off != nullptr; in.have_ch_n_ok = hch->n_ok != nullptr;
     in.have_ch_rows = hch->rows != nullptr; in.have_ch_nodes = hch->nodes != nullptr;
+  }
+  if (hmv) {                                                   // kas_solve_host_moves / kas_solve_host_choose_moves / 16
+    in.moves = hmv; in.ch_rows_optional = rows_optional;
+    if (!hch) { in.mv_select = select; in.mv_n_select = n_select; in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0; }
   }
   in.lane_order_ok = ctx->lds_lane_order_ok;
   for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
@@ -1448,7 +1534,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_TOTAL; ++i)
+  for (int i = 0; i < KAS_HB_ALL; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -1568,6 +1654,13 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     memset(&a, 0, sizeof(a));
     a.sr = d_sr; a.si = (const kas_scenario_impact*)ctx->hbuf[KAS_HB_IMP_SCEN].p;
     a.sizes = (const KasChooseSize*)ctx->hbuf[KAS_HB_CH_SIZES].p; a.segs = (const KasChooseSeg*)ctx->hbuf[KAS_HB_CH_SEGS].p;
+    std::vector<KasChooseSize> sizes0;                          // a choice without rows: the gather sees scenarios without cells
+    if (!hc.ch_gather_rows && !cp.sizes.empty()) {
+      sizes0 = cp.sizes;
+      for (KasChooseSize& z : sizes0) { z.cells = 0; z.seg_count = 0; }
+      copy(ctx->hbuf[KAS_HB_MV_SIZES0].p, sizes0.data(), sizeof(KasChooseSize) * sizes0.size(), hipMemcpyHostToDevice, s0, "upload size table");
+      hip_ok(hipStreamSynchronize(s0), "hipStreamSynchronize");  // (sizes0 is this block's)
+    }
     kas_choose_fill_spec(&a, spec, (int32_t)S);
     a.row_off = (int64_t*)(d_head + hc.ch_head.row_off); a.node_off = (int64_t*)(d_head + hc.ch_head.node_off);
     a.rank = (int32_t*)(d_head + hc.ch_head.rank); a.chosen = (int32_t*)(d_head + hc.ch_head.chosen); a.n_ok = (int32_t*)(d_head + hc.ch_head.n_ok);
@@ -1578,18 +1671,48 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     a.chunks = (int32_t)hc.ch_chunks;
     if (he == hipSuccess) {
       int e = kas_rank_launch(&a, s0);
+      if (!hc.ch_gather_rows) a.sizes = (const KasChooseSize*)ctx->hbuf[KAS_HB_MV_SIZES0].p;
       if (e == 0) e = kas_gather_launch(&a, s0);
       hip_ok((hipError_t)e, "choose kernels");
     }
     copy(p_head, d_head, hc.ch_head.bytes, hipMemcpyDeviceToHost, s0, "download the choice");
   }
+  // a move list: the three kernels on s0 behind every range (and behind the rank kernel, whose chosen[] is a choice's list)
+  char* const d_mvh = (char*)ctx->hbuf[KAS_HB_MV_HEAD].p;
+  int64_t* const p_mvh = (int64_t*)ctx->hbuf[KAS_HB_MV_HEAD_PIN].p;
+  const int64_t mv_n = hc.mv_n;
+  if (hmv && he == hipSuccess && fail_rc == KAS_E_OK) {
+    const KasMovesPlan& mp = hc.moves;
+    if (!mp.scen.empty()) copy(ctx->hbuf[KAS_HB_MV_SCEN].p, mp.scen.data(), sizeof(KasMovesScen) * mp.scen.size(), hipMemcpyHostToDevice, s0, "upload moves scenario table");
+    if (!mp.segs.empty()) copy(ctx->hbuf[KAS_HB_MV_SEGS].p, mp.segs.data(), sizeof(KasMovesSeg) * mp.segs.size(), hipMemcpyHostToDevice, s0, "upload moves segment table");
+    if (!hch && mv_n > 0) copy(ctx->hbuf[KAS_HB_MV_SELECT].p, hc.mv_list.data(), 4 * (size_t)mv_n, hipMemcpyHostToDevice, s0, "upload the moves list");
+    for (int i = 0; !hch && K > 1 && i < K; ++i) hip_ok(hipStreamWaitEvent(s0, ctx->hev_done[i], 0), "wait");
+    // (records a truncated list leaves unwritten are told from written ones by their len: no written record has 0xff there)
+    if (hc.mv_moves_cap > 0 && hmv->cells_cap < hc.mv_room_cells)
+      hip_ok(hipMemsetAsync(ctx->hbuf[KAS_HB_MV_MOVES].p, 0xff, sizeof(kas_move) * (size_t)hc.mv_moves_cap, s0), "hipMemsetAsync");
+    KasMovesLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.scen = (const KasMovesScen*)ctx->hbuf[KAS_HB_MV_SCEN].p; a.segs = (const KasMovesSeg*)ctx->hbuf[KAS_HB_MV_SEGS].p;
+    a.select = hch ? (const int32_t*)(d_head + hc.ch_head.chosen) : (const int32_t*)ctx->hbuf[KAS_HB_MV_SELECT].p;
+    a.cur = native16 ? (const void*)d_cur16 : (const void*)d_cur;
+    a.out = native16 ? (const void*)d_out16 : (const void*)d_out;
+    a.aux = d_aux; a.topic_results = d_tr;
+    a.scratch = (KasMovesCount*)ctx->hbuf[KAS_HB_MV_SCRATCH].p;
+    a.move_off = (int64_t*)d_mvh; a.cell_off = (int64_t*)d_mvh + (mv_n + 1);
+    a.moves = (kas_move*)ctx->hbuf[KAS_HB_MV_MOVES].p; a.cells = ctx->hbuf[KAS_HB_MV_CELLS].p;
+    a.moves_cap = hc.mv_moves_cap; a.cells_cap = hc.mv_cells_cap;
+    a.n = (int32_t)mv_n; a.stride = mp.max_items; a.S = (int32_t)S; a.mask = hmv->mask;
+    a.src16 = native16 ? 1 : 0; a.dst16 = c16 ? 1 : 0;          // (a widened call: narrowed on the way)
+    if (he == hipSuccess) hip_ok((hipError_t)kas_moves_launch(&a, full.Wc, s0), "moves pass");
+    copy(p_mvh, d_mvh, 16 * (size_t)(mv_n + 1), hipMemcpyDeviceToHost, s0, "download the move offsets");
+  }
   drain();
   if (he != hipSuccess || fail_rc != KAS_E_OK) return fail_rc != KAS_E_OK ? fail_rc : KAS_E_HIP;
   if (hch) {                                                   // exactly the chosen scenarios' rows and node blocks, through the staging
     const int64_t cells = ((const int64_t*)(p_head + hc.ch_head.row_off))[ch_k], recs = ((const int64_t*)(p_head + hc.ch_head.node_off))[ch_k];
-    if (cells < 0 || cells > hc.ch_rows_need || recs < 0 || recs > hc.ch_nodes_need)
+    if (cells < 0 || (hc.ch_gather_rows && cells > hc.ch_rows_need) || recs < 0 || recs > hc.ch_nodes_need)
       return set_error(KAS_E_HIP, "internal: the rank kernel left offsets beyond the k largest scenarios");
-    if (cells > 0) copy(ctx->hbuf[KAS_HB_CH_ROWS_PIN].p, ctx->hbuf[KAS_HB_CH_ROWS].p, out.cell * (size_t)cells, hipMemcpyDeviceToHost, s0, "download chosen rows");
+    if (cells > 0 && hc.ch_gather_rows) copy(ctx->hbuf[KAS_HB_CH_ROWS_PIN].p, ctx->hbuf[KAS_HB_CH_ROWS].p, out.cell * (size_t)cells, hipMemcpyDeviceToHost, s0, "download chosen rows");
     if (recs > 0) copy(ctx->hbuf[KAS_HB_CH_NODES_PIN].p, ctx->hbuf[KAS_HB_CH_NODES].p, sizeof(kas_node_impact) * (size_t)recs, hipMemcpyDeviceToHost, s0, "download chosen node records");
     if (S > 0) memcpy(hch->rank, p_head + hc.ch_head.rank, 4 * (size_t)S);
     if (ch_k > 0) memcpy(hch->chosen, p_head + hc.ch_head.chosen, 4 * (size_t)ch_k);
@@ -1622,10 +1745,42 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (nodes > 0) copy(himp->nodes, ctx->hbuf[KAS_HB_IMP_NODES].p, sizeof(kas_node_impact) * (size_t)nodes, hipMemcpyDeviceToHost, s0, "download node impact");
     if (S > 0) copy(himp->scenarios, ctx->hbuf[KAS_HB_IMP_SCEN].p, sizeof(kas_scenario_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario impact");
   }
+  // the move list: the offsets (they are here already), then exactly the records that were written and the cells they use
+  if (hmv && he == hipSuccess) {
+    const int64_t total = p_mvh[mv_n], total_cells = p_mvh[2 * mv_n + 1];
+    if (total < 0 || total > hc.mv_room_moves || total_cells < 0 || total_cells > hc.mv_room_cells)
+      return set_error(KAS_E_HIP, "internal: the moves pass left offsets beyond the rows of the listed scenarios");
+    memcpy(hmv->move_off, p_mvh, 8 * (size_t)(mv_n + 1));
+    memcpy(hmv->cell_off, p_mvh + (mv_n + 1), 8 * (size_t)(mv_n + 1));
+    int64_t written = total < hc.mv_moves_cap ? total : hc.mv_moves_cap, used = written > 0 ? total_cells : 0;
+    const kas_move* d_moves = (const kas_move*)ctx->hbuf[KAS_HB_MV_MOVES].p;
+    if (written > 0 && (total_cells > hmv->cells_cap || written < total)) {
+      // the written records are a prefix (a list's end grows with its index): find its end by the marker, then the cells it uses
+      kas_move probe;
+      int64_t lo = 0, hi = written;                             // records below lo are written, records from hi on are not
+      while (lo < hi && total_cells > hmv->cells_cap && he == hipSuccess) {
+        const int64_t mid = (lo + hi) >> 1;
+        hip_ok(hipMemcpy(&probe, d_moves + mid, sizeof(probe), hipMemcpyDeviceToHost), "probe a move record");
+        if (probe.len != 0xff) lo = mid + 1; else hi = mid;
+      }
+      if (total_cells > hmv->cells_cap) written = lo;
+      used = 0;
+      if (written > 0 && hip_ok(hipMemcpy(&probe, d_moves + written - 1, sizeof(probe), hipMemcpyDeviceToHost), "probe a move record")) {
+        int64_t j = 0;                                          // its block: the last listed scenario that starts at or before it
+        while (j + 1 < mv_n && p_mvh[j + 1] <= written - 1) ++j;
+        used = p_mvh[(mv_n + 1) + j] + probe.cell_at + probe.len;
+      }
+    }
+    if (written > 0) copy(hmv->moves, d_moves, sizeof(kas_move) * (size_t)written, hipMemcpyDeviceToHost, s0, "download the moves");
+    if (used > 0) copy(hmv->cells, ctx->hbuf[KAS_HB_MV_CELLS].p, out.cell * (size_t)used, hipMemcpyDeviceToHost, s0, "download the moves' cells");
+  }
   hip_ok(hipStreamSynchronize(s0), "hipStreamSynchronize");
-  if (hch && he == hipSuccess) {
+  if (hch && he == hipSuccess && hc.ch_gather_rows) {
     const int64_t cells = hch->row_off[ch_k], recs = hch->node_off[ch_k];
     if (cells > 0) memcpy(hch->rows, ctx->hbuf[KAS_HB_CH_ROWS_PIN].p, out.cell * (size_t)cells);
+    if (recs > 0) memcpy(hch->nodes, ctx->hbuf[KAS_HB_CH_NODES_PIN].p, sizeof(kas_node_impact) * (size_t)recs);
+  } else if (hch && he == hipSuccess) {
+    const int64_t recs = hch->node_off[ch_k];
     if (recs > 0) memcpy(hch->nodes, ctx->hbuf[KAS_HB_CH_NODES_PIN].p, sizeof(kas_node_impact) * (size_t)recs);
   }
   return he == hipSuccess ? KAS_E_OK : fail_rc;
@@ -1679,6 +1834,38 @@ int kas_solve_host16_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas
   const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, spec, hch);
+}
+
+int kas_solve_host_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select, int32_t n_select,
+                         const kas_moves* hmv) {
+  if (!ctx || !batch || !h || !hmv) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, select, n_select < 0 ? -1 : n_select, nullptr, nullptr, nullptr, nullptr, hmv);
+}
+
+int kas_solve_host16_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
+                           const kas_moves* hmv) {
+  if (!ctx || !batch || !h16 || !hmv) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, nullptr, nullptr, nullptr, hmv);
+}
+
+int kas_solve_host_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,
+                                const kas_impact_tables* himp, const kas_moves* hmv) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp || !hmv) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, spec, hch, hmv, true);
+}
+
+int kas_solve_host16_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_choose_spec* spec,
+                                  const kas_choice* hch, const kas_impact_tables* himp, const kas_moves* hmv) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp || !hmv) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, spec, hch, hmv, true);
 }
 
 int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_desc* batch, const kas_tables* h) {

@@ -15,6 +15,7 @@
 #include "kas_plan_math.h"
 #include "kas_launch_plan.h"   // kas_cells16_ok, KAS_BUILT_*
 #include "kas_choose.h"        // the size and segment tables of kas_solve_host_choose
+#include "kas_moves.h"         // the scenario and segment tables of kas_solve_host_moves / kas_solve_host_choose_moves
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -190,10 +191,18 @@ enum KasHostBuf {
   KAS_HB_CH_SIZES = KAS_HB_COUNT, KAS_HB_CH_SEGS,   // the size and segment tables (kas_choose.h) on the device
   KAS_HB_CH_HEAD, KAS_HB_CH_ROWS, KAS_HB_CH_NODES,  // row_off, node_off, rank, chosen, n_ok; the chosen scenarios' packed rows and node blocks
   KAS_HB_CH_HEAD_PIN, KAS_HB_CH_ROWS_PIN, KAS_HB_CH_NODES_PIN,   // ... and their pinned HOST staging
-  KAS_HB_TOTAL
+  KAS_HB_TOTAL,                                     // the buffers of the calls above end here
+  // kas_solve_host_moves / kas_solve_host_choose_moves / 16 alone (behind KAS_HB_TOTAL, for the same reason)
+  KAS_HB_MV_SCEN = KAS_HB_TOTAL, KAS_HB_MV_SEGS,    // the scenario and segment tables (kas_moves.h) on the device
+  KAS_HB_MV_SELECT, KAS_HB_MV_SCRATCH,              // the list (a host list; a choice's list is its chosen[]), the (listed scenario, item) table
+  KAS_HB_MV_HEAD, KAS_HB_MV_MOVES, KAS_HB_MV_CELLS, // move_off and cell_off; the records and their list cells
+  KAS_HB_MV_SIZES0,                                 // a choice without rows: the choose size table with no cells, for the gather
+  KAS_HB_MV_HEAD_PIN,                               // pinned HOST staging of the offsets (records and cells go straight to the caller: exactly what was written)
+  KAS_HB_ALL
 };
 static inline bool kas_host_buf_pinned(int32_t id) {
-  return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN;
+  return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN ||
+         id == KAS_HB_MV_HEAD_PIN;
 }
 
 // everything the decisions read
@@ -212,6 +221,14 @@ struct KasHostCallIn {
   int64_t rows_cap = 0, nodes_cap = 0;          // kas_choice
   bool have_ch_rank = false, have_ch_chosen = false, have_ch_row_off = false, have_ch_node_off = false, have_ch_n_ok = false,
        have_ch_rows = false, have_ch_nodes = false;
+  // kas_solve_host_moves / kas_solve_host_choose_moves / 16: the moves of a list of scenarios come back (defaults: no moves, and
+  // every decision above as it was).  Without `choose` the list is mv_select[0 .. mv_n_select) (host; < 0: every scenario) and
+  // no rows come back (n_select is 0); with `choose` it is the choice's chosen[0 .. k), and ch_rows_optional lets the caller
+  // leave the rows out (rows == NULL with rows_cap == 0)
+  const kas_moves* moves = nullptr;
+  const int32_t* mv_select = nullptr;
+  int32_t mv_n_select = -1;
+  bool ch_rows_optional = false;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -241,12 +258,19 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_TOTAL] = {};              // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_ALL] = {};                // what to reserve of each buffer; 0: this call must not touch it
   // kas_solve_host_choose / 16
   KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
   int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
   int64_t ch_chunks = 0;                        // gather workgroups per chosen scenario
   KasChooseHead ch_head;                        // where the arrays of the header lie in KAS_HB_CH_HEAD
+  bool ch_gather_rows = true;                   // false: kas_solve_host_choose_moves without rows
+  // kas_solve_host_moves / kas_solve_host_choose_moves / 16
+  KasMovesPlan moves;                           // the scenario and segment tables of the whole call, offsets as the device sees the pools
+  std::vector<int32_t> mv_list;                 // the list as it is uploaded (empty for a choice: its chosen[] is on the device)
+  int64_t mv_n = 0;                             // listed scenarios
+  int64_t mv_room_moves = 0, mv_room_cells = 0; // what the list can need at most (a choice: the k largest scenarios)
+  int64_t mv_moves_cap = 0, mv_cells_cap = 0;   // the capacities on the device: the caller's, no more than the room
 };
 
 // Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
@@ -313,6 +337,8 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     const int64_t k = in.choose->k;
     kas_choose_plan_build(b, &hc->choose);
     kas_choose_k_largest(hc->choose, (int32_t)k, &hc->ch_rows_need, &hc->ch_nodes_need);
+    hc->ch_gather_rows = !(in.ch_rows_optional && in.rows_cap == 0 && !in.have_ch_rows);
+    if (!hc->ch_gather_rows) hc->ch_rows_need = 0;
     if (in.rows_cap < hc->ch_rows_need) return fail(KAS_E_INVALID_ARG, "kas_choice: rows_cap below the packed rows of the k largest scenarios");
     if (in.nodes_cap < hc->ch_nodes_need) return fail(KAS_E_INVALID_ARG, "kas_choice: nodes_cap below the node records of the k largest scenarios");
     if ((S > 0 && !in.have_ch_rank) || (k > 0 && !in.have_ch_chosen) || !in.have_ch_row_off || !in.have_ch_node_off || !in.have_ch_n_ok ||
@@ -321,6 +347,32 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     hc->ch_chunks = kas_choose_chunks(hc->choose, in.cells16 ? 2 : 4);
     if (k * hc->ch_chunks > INT32_MAX) return fail(KAS_E_UNSUPPORTED, "kas_choice: k scenarios of this size are more than one gather launch takes");
     hc->ch_head.lay_out(S, k);
+  }
+  // moves, in the order include/kas_abi.h documents: the mask, the capacities, the arrays, their alignment, the list, the shape
+  if (in.moves) {
+    const char* bad = kas_moves_args_error(in.moves, in.cells16 ? 2 : 4);
+    if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
+    hc->mv_list.clear();
+    if (in.choose) {
+      hc->mv_n = in.choose->k;
+    } else if (in.mv_n_select < 0) {
+      hc->mv_n = S;
+      for (int64_t s = 0; s < S; ++s) hc->mv_list.push_back((int32_t)s);
+    } else {
+      if (in.mv_n_select > 0 && !in.mv_select) return fail(KAS_E_INVALID_ARG, "kas_moves: select == NULL");
+      hc->mv_n = in.mv_n_select;
+      for (int32_t j = 0; j < in.mv_n_select; ++j) {
+        if (in.mv_select[j] < -1 || in.mv_select[j] >= S) return fail(KAS_E_INVALID_ARG, "kas_moves: select: scenario index out of range");
+        hc->mv_list.push_back(in.mv_select[j]);
+      }
+    }
+    kas_moves_plan_build(b, &hc->moves);
+    bad = kas_moves_shape_error(hc->moves, hc->mv_n);
+    if (bad[0]) return fail(KAS_E_UNSUPPORTED, bad);
+    if (in.choose) kas_moves_k_largest(hc->moves, in.choose->k, &hc->mv_room_moves, &hc->mv_room_cells);
+    else kas_moves_room(hc->moves, hc->mv_list.data(), hc->mv_n, &hc->mv_room_moves, &hc->mv_room_cells);
+    hc->mv_moves_cap = in.moves->moves_cap < hc->mv_room_moves ? in.moves->moves_cap : hc->mv_room_moves;
+    hc->mv_cells_cap = in.moves->cells_cap < hc->mv_room_cells ? in.moves->cells_cap : hc->mv_room_cells;
   }
   // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
   const int64_t cell = in.cells16 ? 2 : 4;                     // bytes of a cur / out cell as it travels
@@ -351,6 +403,16 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     by[KAS_HB_CH_HEAD] = by[KAS_HB_CH_HEAD_PIN] = hc->ch_head.bytes;
     by[KAS_HB_CH_ROWS] = by[KAS_HB_CH_ROWS_PIN] = (size_t)cell * (size_t)(hc->ch_rows_need + 8);
     by[KAS_HB_CH_NODES] = by[KAS_HB_CH_NODES_PIN] = sizeof(kas_node_impact) * (size_t)(hc->ch_nodes_need + 1);
+  }
+  if (in.moves) {
+    by[KAS_HB_MV_SCEN] = sizeof(KasMovesScen) * (hc->moves.scen.size() + 1);
+    by[KAS_HB_MV_SEGS] = sizeof(KasMovesSeg) * (hc->moves.segs.size() + 1);
+    by[KAS_HB_MV_SELECT] = in.choose ? 0 : 4 * (size_t)(hc->mv_n + 1);
+    by[KAS_HB_MV_SCRATCH] = sizeof(KasMovesCount) * ((size_t)hc->mv_n * (size_t)hc->moves.max_items + 1);
+    by[KAS_HB_MV_HEAD] = by[KAS_HB_MV_HEAD_PIN] = 16 * (size_t)(hc->mv_n + 1);
+    by[KAS_HB_MV_MOVES] = sizeof(kas_move) * (size_t)(hc->mv_moves_cap + 1);
+    by[KAS_HB_MV_CELLS] = (size_t)cell * (size_t)(hc->mv_cells_cap + 8);
+    by[KAS_HB_MV_SIZES0] = in.choose && !hc->ch_gather_rows ? sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1) : 0;
   }
   return KAS_E_OK;
 }

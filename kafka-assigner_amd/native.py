@@ -29,6 +29,8 @@ SYMBOLS = [
     "kas_plan_create16", "kas_solve_device16", "kas_resolve_replication_factor", "kas_failure_text",
     "kas_impact_device", "kas_impact_device16", "kas_solve_host_impact", "kas_solve_host16_impact",
     "kas_rank_device", "kas_choose_device", "kas_choose_device16", "kas_solve_host_choose", "kas_solve_host16_choose",
+    "kas_moves_device", "kas_moves_device16", "kas_solve_host_moves", "kas_solve_host16_moves", "kas_solve_host_choose_moves",
+    "kas_solve_host16_choose_moves",
 ]
 
 _LIB = None
@@ -134,6 +136,16 @@ def load():
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec),
                        C.POINTER(abi.Choice), C.POINTER(abi.ImpactTables)]
+    for fn in (L.kas_moves_device, L.kas_moves_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.c_void_p, C.c_int32, C.POINTER(abi.Moves), C.c_void_p]
+    for fn in (L.kas_solve_host_moves, L.kas_solve_host16_moves):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.Moves)]
+    for fn in (L.kas_solve_host_choose_moves, L.kas_solve_host16_choose_moves):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec),
+                       C.POINTER(abi.Choice), C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves)]
     if L.kas_abi_version() != abi.KAS_ABI_VERSION:
         raise ImportError("libkas_hip.so ABI version mismatch")
     _LIB = L
@@ -258,6 +270,17 @@ class Plan:
                         choice_nodes or None, int(nodes_cap))
         fn = self._lib.kas_choose_device16 if self.cells16 else self._lib.kas_choose_device
         _check(fn(self._h, C.byref(t), C.byref(imp), C.byref(spec), C.byref(ch), C.c_void_p(stream) if stream else None))
+
+    def moves_device(self, mask, select: int, n_select: int, cur: int, out: int, topic_results: int, move_off: int, cell_off: int,
+                     moves: int, moves_cap: int, cells: int, cells_cap: int, aux: int = 0, stream: int = 0):
+        """kas_moves_device / 16: the moves (kinds `mask`: names of abi.MOVE_KINDS or a KAS_MOVE_* mask) of this plan's previous
+        solve for the scenarios in the device array `select` (int32 [n_select]; a choice's chosen[] as it is) into the device
+        arrays move_off / cell_off (int64 [n_select + 1]), moves (kas_move [moves_cap]) and cells.  Raw device pointers (int)."""
+        t = abi.Tables()
+        t.cur = cur or None; t.out = out or None; t.aux = aux or None; t.topic_results = topic_results or None
+        mv = abi.Moves(abi.move_mask(mask), 0, move_off or None, cell_off or None, moves or None, int(moves_cap), cells or None, int(cells_cap))
+        fn = self._lib.kas_moves_device16 if self.cells16 else self._lib.kas_moves_device
+        _check(fn(self._h, C.byref(t), select or None, int(n_select), C.byref(mv), C.c_void_p(stream) if stream else None))
 
     def set_flags(self, flags: int):
         _check(self._lib.kas_plan_set_flags(self._h, flags))
@@ -475,6 +498,131 @@ def solve_host_choose(fb: FlatBatch, keys, k: int, cells16: bool = False, ctx: O
     c.rows = c.rows[:int(c.row_off[kk])]
     c.nodes = c.nodes[:int(c.node_off[kk])]
     return ho, c
+
+
+@dataclass
+class MoveList:
+    """What a moves call leaves (include/kas_abi.h, kas_moves): listed scenario j owns moves[move_off[j]:move_off[j + 1]] and
+    cells[cell_off[j]:cell_off[j + 1]]; a record's new list is cells[cell_off[j] + cell_at:][:len].  moves / cells hold what
+    the capacities let through; move_off[-1] / cell_off[-1] are the true totals."""
+    mask: int
+    select: np.ndarray                   # the listed scenarios (a choice: its chosen[])
+    move_off: np.ndarray
+    cell_off: np.ndarray
+    moves: np.ndarray                    # abi.MOVE_DTYPE
+    cells: np.ndarray                    # int32 broker ids, or uint16 node indices
+
+    @property
+    def truncated(self) -> bool:
+        return int(self.move_off[-1]) > self.moves.size or int(self.cell_off[-1]) > self.cells.size
+
+    def of(self, j: int):
+        """(records, cells) of listed scenario j: the block's records and its cells (cell_at indexes the latter)"""
+        return (self.moves[int(self.move_off[j]):int(self.move_off[j + 1])], self.cells[int(self.cell_off[j]):int(self.cell_off[j + 1])])
+
+
+def scenario_rows(fb: FlatBatch) -> np.ndarray:
+    """int64 [S]: rows of each scenario (its topics' P): the most moves it can have"""
+    per_topic = np.clip(fb.topics["n_partitions"], 0, None).astype(np.int64)
+    cum = np.concatenate([[0], np.cumsum(per_topic)])
+    b = fb.scen["topic_begin"].astype(np.int64)
+    c = np.clip(fb.scen["topic_count"], 0, None).astype(np.int64)
+    return np.where(c > 0, cum[np.minimum(b + c, fb.n_topics)] - cum[np.minimum(b, fb.n_topics)], 0).astype(np.int64)
+
+
+def moves_room(fb: FlatBatch, select) -> tuple:
+    """(rows, packed cells) of the scenarios in `select` (entries outside 0..S-1 take none): always enough room for their moves"""
+    sel = np.asarray(list(select) if not isinstance(select, np.ndarray) else select, dtype=np.int64).reshape(-1)
+    sel = sel[(sel >= 0) & (sel < fb.n_scenarios)]
+    return int(scenario_rows(fb)[sel].sum()), int(packed_cells(fb)[sel].sum())
+
+
+def _move_arrays(mask, n, moves_cap, cells_cap, cells16):
+    ml = MoveList(mask=abi.move_mask(mask), select=None, move_off=np.full(n + 1, -9, np.int64), cell_off=np.full(n + 1, -9, np.int64),
+                  moves=np.zeros(max(moves_cap, 1), abi.MOVE_DTYPE)[:moves_cap],
+                  cells=np.zeros(max(cells_cap, 1), np.uint16 if cells16 else np.int32)[:cells_cap])
+    mv = abi.Moves(ml.mask, 0, ml.move_off.ctypes.data, ml.cell_off.ctypes.data, ml.moves.ctypes.data if moves_cap else None, moves_cap,
+                   ml.cells.ctypes.data if cells_cap else None, cells_cap)
+    return ml, mv
+
+
+def _trim(ml: MoveList):
+    n_moves = min(int(ml.move_off[-1]), ml.moves.size)
+    ml.moves = ml.moves[:n_moves]
+    ml.cells = ml.cells[:min(int(ml.cell_off[-1]), ml.cells.size)]
+    return ml
+
+
+def solve_host_moves(fb: FlatBatch, mask=("replicas",), select=None, cells16: bool = False, moves_cap: Optional[int] = None,
+                     cells_cap: Optional[int] = None, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_moves / kas_solve_host16_moves: every scenario is solved and reports its records; no rows come back, but
+    the moves of the scenarios in `select` (None: every scenario) under `mask` (kind names of abi.MOVE_KINDS, or a KAS_MOVE_*
+    mask).  Capacities default to what is always enough (moves_room).  Returns (HostOutputs without rows, MoveList)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)                 # (held until the call returns: the table only borrows it)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    listed = np.arange(fb.n_scenarios, dtype=np.int32) if sel is None else sel
+    room = moves_room(fb, listed)
+    ml, mv = _move_arrays(mask, int(listed.size), room[0] if moves_cap is None else int(moves_cap),
+                          room[1] if cells_cap is None else int(cells_cap), cells16)
+    ml.select = listed
+    fn = L.kas_solve_host16_moves if cells16 else L.kas_solve_host_moves
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
+              -1 if sel is None else int(sel.size), C.byref(mv)))
+    return ho, _trim(ml)
+
+
+def solve_host_choose_moves(fb: FlatBatch, keys, k: int, mask=("replicas",), rows: bool = True, cells16: bool = False,
+                            moves_cap: Optional[int] = None, cells_cap: Optional[int] = None, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_choose_moves / 16: solve_host_choose plus the moves of the chosen, in rank order; rows=False hands the
+    library no rows array (rows == NULL, rows_cap == 0): nothing but records, node blocks and moves comes back.
+    Returns (HostOutputs without rows, Choice, MoveList)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    spec = abi.choose_spec(keys, k)
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)                 # (held until the call returns: the table only borrows it)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    S, kk = fb.n_scenarios, max(int(k), 0)
+    rows_cap = int(np.sort(packed_cells(fb))[::-1][:kk].sum()) if rows else 0
+    nodes_cap = int(np.sort(np.clip(fb.scen["n_nodes"], 0, None).astype(np.int64))[::-1][:kk].sum())
+    c = Choice(rank=np.full(max(S, 1), -9, np.int32)[:S], chosen=np.full(max(kk, 1), -9, np.int32)[:kk],
+               row_off=np.full(kk + 1, -9, np.int64), node_off=np.full(kk + 1, -9, np.int64), n_ok=-9,
+               rows=np.zeros(max(rows_cap, 1), np.uint16 if cells16 else np.int32)[:rows_cap],
+               nodes=np.zeros(max(nodes_cap, 1), abi.NODE_IMPACT_DTYPE)[:nodes_cap],
+               scenarios=np.zeros(max(S, 1), abi.SCENARIO_IMPACT_DTYPE)[:S])
+    n_ok = np.full(1, -9, np.int32)
+
+    def p(a):
+        return a.ctypes.data if a.size else None
+    ch = abi.Choice(p(c.rank), p(c.chosen), p(c.row_off), p(c.node_off), p(n_ok), p(c.rows), rows_cap, p(c.nodes), nodes_cap)
+    imp = abi.ImpactTables(None, p(c.scenarios))
+    room_rows = int(np.sort(scenario_rows(fb))[::-1][:kk].sum())
+    room_cells = int(np.sort(packed_cells(fb))[::-1][:kk].sum())
+    ml, mv = _move_arrays(mask, kk, room_rows if moves_cap is None else int(moves_cap), room_cells if cells_cap is None else int(cells_cap),
+                          cells16)
+    fn = L.kas_solve_host16_choose_moves if cells16 else L.kas_solve_host_choose_moves
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), C.byref(imp), C.byref(mv)))
+    c.n_ok = int(n_ok[0])
+    c.rows = c.rows[:int(c.row_off[kk])] if rows else c.rows[:0]
+    c.nodes = c.nodes[:int(c.node_off[kk])]
+    ml.select = c.chosen
+    return ho, c, _trim(ml)
 
 
 def solve_host_sharded(fb: FlatBatch, ctxs) -> HostOutputs:

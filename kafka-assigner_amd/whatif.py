@@ -18,6 +18,11 @@ variants' rows on the device (kas_solve_host_impact with n_select = 0): only rec
 best() lets the GPU also compare the variants (kas_solve_host_choose): plan.best(variants, k=3, by=("max_inbound",
 "moved_replicas")) returns the three best variants that solve, best first, each with its rows and its per-broker impact;
 nothing comes back for the others but their records.
+
+moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for the rows that change instead of every row, compacted
+on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
+results[0].reassignment() -> the Kafka reassignment JSON object of those partitions.  solve(..., moves=...) returns the moves of
+every variant and no rows (kas_solve_host_moves); best(..., moves=..., rows=False) those of the winners and no rows at all.
 """
 from __future__ import annotations
 
@@ -65,6 +70,8 @@ class VariantResult:
     _nodes: np.ndarray = field(repr=False, default=None)      # this variant's block of kas_node_impact records
     _node_ids: np.ndarray = field(repr=False, default=None)
     _packed_at: Optional[int] = field(repr=False, default=None)   # best(): _out holds this variant's rows packed from here
+    _moves: Optional[tuple] = field(repr=False, default=None)     # moves=...: (this variant's kas_move records, its list cells)
+    _moves_mask: int = field(repr=False, default=0)               # ... and the kinds that were asked for
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -78,6 +85,30 @@ class VariantResult:
         if self._out is None:
             raise ValueError("solve(..., rows=False) downloaded no rows: solve with rows=True to read an assignment")
         return self._plan._rows(self._index, topic, self._out, self._packed_at)
+
+    def moves(self, topic: Optional[str] = None, kinds=None) -> list:
+        """[(topic, partition, [new replicas], {kinds})]: the partitions that change under this variant, in (topic, partition)
+        order, of the kinds asked for with moves=... ({kinds}: every kind that applies to the row).  topic: that topic's only;
+        kinds: a subset of the kinds that were asked for."""
+        if self._moves is None:
+            raise ValueError("no moves: solve(..., moves=(...)) or best(..., moves=(...))")
+        mask = self._moves_mask if kinds is None else abi.move_mask(kinds)
+        if mask & ~self._moves_mask:
+            raise ValueError("kinds that were not asked for with moves=...")
+        recs, cells = self._moves
+        names = self._plan.topic_names
+        out = []
+        for r in recs:
+            if not int(r["flags"]) & mask or (topic is not None and names[int(r["topic"])] != topic):
+                continue
+            at = int(r["cell_at"])
+            out.append((names[int(r["topic"])], int(r["partition"]), [int(b) for b in cells[at:at + int(r["len"])]],
+                        {k for k, bit in abi.MOVE_KINDS.items() if int(r["flags"]) & bit}))
+        return out
+
+    def reassignment(self, kinds=None) -> dict:
+        """The Kafka reassignment JSON object (version, partitions) holding the partitions of moves(kinds=kinds) only."""
+        return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": reps} for t, p, reps, _ in self.moves(kinds=kinds)]}
 
     def broker_impact(self) -> Dict[int, Dict[str, int]]:
         """broker id -> {replicas_before, replicas_after, leaders_before, leaders_after, inbound, outbound} under this
@@ -150,15 +181,22 @@ class WhatIf:
                          ctx=np.zeros(0, np.int32), out_len=out_off)
 
     # ---- solve ---------------------------------------------------------------------------------
-    def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True) -> List[VariantResult]:
+    def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True, moves=None) -> List[VariantResult]:
         """Solve every variant in one batch (default: the HIP path through the C ABI).
         impact=True: also the per-broker impact of every variant, computed on the GPU (kas_solve_host_impact).
         rows=False: no variant's rows come back (kas_solve_host_select / kas_solve_host_impact with n_select = 0) — the
-        records and the impact only; assignment() then raises."""
+        records and the impact only; assignment() then raises.
+        moves=(kinds): the moves of every variant instead of its rows (kas_solve_host_moves: no rows come back whatever `rows`
+        says, and the call takes neither impact nor solve_fn); moves() and reassignment() then answer."""
         from . import native
         fb = self.flat_batch(variants)
-        nodes = scen_imp = None
-        if impact:
+        nodes = scen_imp = ml = None
+        if moves is not None:
+            if solve_fn is not None or impact:
+                raise ValueError("moves=... takes the library's own host call, without impact (best() has both)")
+            ho, ml = native.solve_host_moves(fb, abi.move_mask(moves))
+            rows = False
+        elif impact:
             if solve_fn is not None:
                 raise ValueError("impact=True takes the library's own host call (no solve_fn)")
             ho, nodes, scen_imp = native.solve_host_impact(fb, select=None if rows else [])
@@ -179,6 +217,8 @@ class WhatIf:
                 extra = {f: int(scen_imp[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
                 off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
                 extra.update(_nodes=nodes[base[s]:base[s + 1]], _node_ids=fb.node_id[off:off + n])
+            if ml is not None:
+                extra.update(_moves=ml.of(s), _moves_mask=ml.mask)
             res.append(VariantResult(label=v.label, status=int(sr["status"]),
                                      fail_topic=self.topic_names[ft] if ft >= 0 else None,
                                      fail_partition=int(sr["fail_partition"]),
@@ -187,11 +227,14 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ho.out if rows else None, **extra))
         return res
 
-    def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved")) -> List[VariantResult]:
+    def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved"), moves=None,
+             rows: bool = True) -> List[VariantResult]:
         """The k best variants that solve, best first, chosen on the GPU (kas_solve_host_choose): variants are compared by the
         criteria named in `by` (abi.KEY_NAMES; one to four, smaller is better, the earlier variant wins a tie).  Every variant is
         solved and reduced to its records, but rows and per-broker impact come back for the winners only: each result has
-        assignment(), broker_impact() and its rank.  Fewer than k results when fewer variants solve."""
+        assignment(), broker_impact() and its rank.  Fewer than k results when fewer variants solve.
+        moves=(kinds): also each winner's moves (kas_solve_host_choose_moves; moves(), reassignment()); with rows=False no rows
+        are fetched and assignment() raises."""
         from . import native
         by = [by] if isinstance(by, str) else list(by)
         for name in by:
@@ -201,7 +244,13 @@ class WhatIf:
             raise ValueError("by: one to four criteria")
         fb = self.flat_batch(variants)
         k = max(0, min(int(k), len(variants)))
-        ho, ch = native.solve_host_choose(fb, by, k)
+        ml = None
+        if moves is None:
+            if not rows:
+                raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
+            ho, ch = native.solve_host_choose(fb, by, k)
+        else:
+            ho, ch, ml = native.solve_host_choose_moves(fb, by, k, abi.move_mask(moves), rows=rows)
         self._fb = fb
         res = []
         for j in range(min(k, ch.n_ok)):
@@ -209,10 +258,12 @@ class WhatIf:
             sr = ho.scenario_results[s]
             off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
             extra = {f: int(ch.scenarios[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
+            if ml is not None:
+                extra.update(_moves=ml.of(j), _moves_mask=ml.mask)
             res.append(VariantResult(label=variants[s].label, status=int(sr["status"]), fail_topic=None,
                                      fail_partition=int(sr["fail_partition"]), moved_replicas=int(sr["moved_replicas"]),
                                      moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]), rank=j,
-                                     _plan=self, _index=s, _out=ch.rows, _packed_at=int(ch.row_off[j]),
+                                     _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
                                      _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
                                      **extra))
         return res
