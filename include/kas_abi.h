@@ -59,6 +59,8 @@
 extern "C" {
 #endif
 
+/* (the front entries below — kas_front_rank_device, kas_front_device / 16, kas_solve_host_front / 16 — were added under
+ * version 6 as well: purely additive) */
 /* (the moves entries below — kas_moves_device / 16, kas_solve_host_moves / 16, kas_solve_host_choose_moves / 16 — were added
  * under version 6 as well: purely additive) */
 /* (the choose entries below — kas_rank_device, kas_choose_device / 16, kas_solve_host_choose / 16 — were added under
@@ -533,6 +535,60 @@ int kas_solve_host_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, const
 int kas_solve_host16_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
                                   const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
                                   const kas_moves* host_moves);
+
+/* ---- the Pareto front of the scenarios, marked and ranked on the device (added under ABI v6: purely additive) ----------
+ * A lexicographic key decides in advance that the first criterion outweighs every other.  The *front* is every scenario that
+ * no other scenario beats on all criteria at once, optionally among those that respect hard bounds.
+ *   eligible   scenario s is eligible iff its status is KAS_OK and limit_key[i](s) <= limit[i] for every i < n_limits.
+ *   dominates  t dominates s iff both are eligible, key[i](t) <= key[i](s) for every i < n_keys, and either some
+ *              key[i](t) < key[i](s) or all are equal and t < s: of scenarios with identical criteria only the earliest
+ *              survives.  A strict partial order: every dominated scenario is dominated by a member.
+ *   member     s is a member iff it is eligible and nothing dominates it.  A bound on a criterion among key[] only filters
+ *              the front; a bound on another criterion can create members (bounds are applied before domination).
+ * Members are ordered exactly as kas_choose_spec orders scenarios: (key[0], ..., key[n_keys - 1], s), lexicographic. */
+#define KAS_FRONT_NOT_OK     (-1)  /* rank[s] of a scenario whose status is not KAS_OK             */
+#define KAS_FRONT_OVER_LIMIT (-2)  /* ... that is OK and violates a bound                          */
+#define KAS_FRONT_DOMINATED  (-3)  /* ... that is eligible and dominated                           */
+typedef struct kas_front_spec {
+  int32_t n_keys;                          /* 1..KAS_CHOOSE_MAX_KEYS: the criteria that are traded off   */
+  int32_t key[KAS_CHOOSE_MAX_KEYS];        /* KAS_KEY_*; their order only orders the members              */
+  int32_t n_limits;                        /* 0..KAS_CHOOSE_MAX_KEYS hard bounds                          */
+  int32_t limit_key[KAS_CHOOSE_MAX_KEYS];  /* KAS_KEY_*, any criterion, in the spec or not                */
+  int32_t limit[KAS_CHOOSE_MAX_KEYS];      /* >= 0: the criterion must be <= limit                        */
+  int32_t k;                               /* members to return, 0 <= k <= S; 0 classifies only           */
+} kas_front_spec;
+
+/* A front goes into a kas_choice (above) plus int32_t counts[4] = {n_ok, n_eligible, n_front, 0}:
+ *   rank[s]        for a member the number of members with a smaller key, else its class code KAS_FRONT_*
+ *   chosen[j]      the member of rank j for j < min(k, n_front), -1 behind
+ *   row_off[k+1], node_off[k+1]  the prefix sums over the members in that order, repeating the last offset behind
+ *                  min(k, n_front), exactly as kas_choice documents them
+ *   n_ok[1]        as ever; n_front > k tells the caller that the list was cut
+ * Every entry of rank, chosen, the offsets, n_ok and counts is written and nothing behind them.  The same inputs give the
+ * same bytes (no atomics, nothing between workgroups).
+ * Refused with KAS_E_INVALID_ARG before any GPU work, in this order: n_keys outside 1..4; an unknown criterion; n_limits
+ * outside 0..4; an unknown limit criterion; a negative limit; k outside 0..S; then everything the matching choose entry
+ * refuses, in its order (capacities against the k largest scenarios, NULL arrays with counts among them, alignment).
+ *
+ * kas_front_rank_device: n_scenarios records alone (device pointers; no plan), as kas_rank_device: rank[S], chosen[k] and
+ * counts[4]; scratch is n_scenarios int32 of the caller's device memory.
+ * kas_front_device / 16: as kas_choose_device / 16, the front in place of the ranking; the class scratch is the plan's,
+ * allocated at its first front call.
+ * kas_solve_host_front / 16: kas_solve_host_choose_moves / 16 with the front in place of the ranking.  host_choice->rows ==
+ * NULL with rows_cap == 0 gathers no rows; host_moves == NULL asks for no moves (kas_solve_host_choose's shape). */
+int kas_front_rank_device(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                          int32_t n_scenarios, const kas_front_spec* spec, int32_t* rank, int32_t* chosen, int32_t* counts,
+                          int32_t* scratch, void* hip_stream);
+int kas_front_device(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                     const kas_front_spec* spec, const kas_choice* device_choice, int32_t* counts, void* hip_stream);
+int kas_front_device16(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                       const kas_front_spec* spec, const kas_choice* device_choice, int32_t* counts, void* hip_stream);
+int kas_solve_host_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                         const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
+                         const kas_impact_tables* host_impact, const kas_moves* host_moves);
+int kas_solve_host16_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                           const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
+                           const kas_impact_tables* host_impact, const kas_moves* host_moves);
 
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */

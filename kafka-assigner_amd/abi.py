@@ -213,6 +213,42 @@ def choose_spec(keys, k: int) -> "ChooseSpec":
     return spec
 
 
+# the Pareto front of the scenarios (kas_front_spec): the criteria traded off, hard bounds, the class codes a non-member's rank holds
+KAS_FRONT_NOT_OK, KAS_FRONT_OVER_LIMIT, KAS_FRONT_DOMINATED = -1, -2, -3
+FRONT_CLASSES = {0: "member", KAS_FRONT_NOT_OK: "failed", KAS_FRONT_OVER_LIMIT: "over_limit", KAS_FRONT_DOMINATED: "dominated"}
+FRONT_ENTRIES = ("kas_front_rank_device", "kas_front_device", "kas_front_device16", "kas_solve_host_front", "kas_solve_host16_front")
+
+
+class FrontSpec(C.Structure):
+    _fields_ = [("n_keys", C.c_int32), ("key", C.c_int32 * KAS_CHOOSE_MAX_KEYS), ("n_limits", C.c_int32),
+                ("limit_key", C.c_int32 * KAS_CHOOSE_MAX_KEYS), ("limit", C.c_int32 * KAS_CHOOSE_MAX_KEYS), ("k", C.c_int32)]
+
+
+def _key_id(name) -> int:
+    if isinstance(name, str):
+        if name not in KEYS:
+            raise ValueError("unknown criterion %r (one of %s)" % (name, ", ".join(KEY_NAMES)))
+        return KEYS[name]
+    return int(name)
+
+
+def front_spec(by, within=None, k: int = 0) -> "FrontSpec":
+    """kas_front_spec: `by` the criteria traded off (names of KEY_NAMES or KAS_KEY_* numbers), `within` hard bounds as
+    {criterion: limit} (or a list of pairs), k members to return; unknown names raise ValueError."""
+    ids = [_key_id(n) for n in ([by] if isinstance(by, (str, int)) else list(by))]
+    pairs = list(within.items()) if isinstance(within, dict) else list(within or ())
+    spec = FrontSpec()
+    spec.n_keys = len(ids)
+    for i, v in enumerate(ids[:KAS_CHOOSE_MAX_KEYS]):
+        spec.key[i] = v
+    spec.n_limits = len(pairs)
+    for i, (name, limit) in enumerate(pairs[:KAS_CHOOSE_MAX_KEYS]):
+        spec.limit_key[i] = _key_id(name)
+        spec.limit[i] = int(limit)
+    spec.k = int(k)
+    return spec
+
+
 # the move list (kas_move / kas_moves): a row's flags, the 16-byte record, where a list goes
 KAS_MOVE_REPLICAS, KAS_MOVE_LEADER, KAS_MOVE_ORDER = 1, 2, 4
 MOVE_KINDS = {"replicas": KAS_MOVE_REPLICAS, "leader": KAS_MOVE_LEADER, "order": KAS_MOVE_ORDER}
@@ -246,7 +282,7 @@ def move_mask(kinds) -> int:
 
 assert MOVE_DTYPE.itemsize == C.sizeof(Move) == 16 and C.sizeof(Moves) == 56
 assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32
-assert C.sizeof(ChooseSpec) == 24 and C.sizeof(Choice) == 72
+assert C.sizeof(ChooseSpec) == 24 and C.sizeof(Choice) == 72 and C.sizeof(FrontSpec) == 60
 assert TOPIC_RESULT_DTYPE.itemsize == C.sizeof(TopicResult) == 16
 assert SCENARIO_RESULT_DTYPE.itemsize == C.sizeof(ScenarioResult) == 32
 assert TOPIC_DESC_DTYPE.itemsize == C.sizeof(TopicDesc) == 64

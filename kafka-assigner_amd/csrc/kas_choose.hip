@@ -1,9 +1,12 @@
 // kas_choose.hip — gfx950 kernels that choose the best scenarios of a solve (kas_rank_device / kas_choose_device /
-// kas_solve_host_choose in kas_hip.hip).  Tables and launch arguments: kas_choose.h; device code: kas_choose_body.h.  A
-// translation unit of its own, so that nothing here changes how the kernels of kas_hip.hip and kas_impact.hip are compiled.
+// kas_solve_host_choose in kas_hip.hip) or mark and rank their Pareto front (kas_front_rank_device / kas_front_device /
+// kas_solve_host_front).  Tables and launch arguments: kas_choose.h, kas_front.h; device code: kas_choose_body.h,
+// kas_front_body.h.  A translation unit of its own, so that nothing here changes how the kernels of kas_hip.hip and
+// kas_impact.hip are compiled.
 #include <hip/hip_runtime.h>
 
 #include "kas_choose_body.h"
+#include "kas_front_body.h"
 
 // one lane per scenario (and one more): every workgroup streams all S keys through its LDS tile
 __global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_rank_kernel(KasChooseLaunch a) {
@@ -14,6 +17,18 @@ __global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_rank_kernel(KasChooseLau
 // one workgroup per (chosen scenario, chunk of its packed rows and node block)
 __global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_gather_kernel(KasChooseLaunch a) {
   kasc::gather_item(a, (int64_t)blockIdx.x);
+}
+
+// one lane per scenario: every workgroup streams all S scenarios through its LDS tile and tests each against its lanes' own
+__global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_front_mark_kernel(KasFrontLaunch a) {
+  __shared__ kasf::Entry tile[KAS_CHOOSE_TILE];
+  kasf::mark_block(a, (int32_t)blockIdx.x, tile);
+}
+
+// the rank kernel's loop over the members of the front (the classes kas_front_mark_kernel left)
+__global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_front_rank_kernel(KasFrontLaunch a) {
+  __shared__ kasc::Entry tile[KAS_CHOOSE_TILE];
+  kasf::rank_block(a, (int32_t)blockIdx.x, tile);
 }
 
 int kas_rank_launch(const KasChooseLaunch* a, void* hip_stream) {
@@ -27,5 +42,16 @@ int kas_gather_launch(const KasChooseLaunch* a, void* hip_stream) {
   if (grid <= 0) return (int)hipSuccess;
   if (grid > INT32_MAX) return (int)hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(kas_gather_kernel, dim3((unsigned)grid), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
+  return (int)hipGetLastError();
+}
+
+int kas_front_mark_launch(const KasFrontLaunch* a, void* hip_stream) {
+  hipLaunchKernelGGL(kas_front_mark_kernel, dim3((unsigned)kas_front_mark_grid(a->c.S)), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
+  return (int)hipGetLastError();
+}
+
+int kas_front_rank_launch(const KasFrontLaunch* a, void* hip_stream) {
+  const unsigned grid = (unsigned)(((int64_t)a->c.S + 1 + KAS_CHOOSE_BLOCK - 1) / KAS_CHOOSE_BLOCK);
+  hipLaunchKernelGGL(kas_front_rank_kernel, dim3(grid), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
   return (int)hipGetLastError();
 }

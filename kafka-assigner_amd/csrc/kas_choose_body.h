@@ -37,11 +37,19 @@ KAS_DEV int32_t criterion(const kas_scenario_result& r, const kas_scenario_impac
   }
 }
 
-KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s) {
+// Who takes part in a ranking, and what the ranking leaves for those who do not.  ByStatus: the scenarios that solved
+// (kas_choose_spec); kas_front_body.h has the other one, the members of a front.
+struct ByStatus {};
+KAS_DEV int32_t takes_part(const ByStatus&, const KasChooseLaunch&, int32_t, const kas_scenario_result& r) { return r.status == KAS_OK ? 1 : 0; }
+KAS_DEV int32_t outside(const ByStatus&, const KasChooseLaunch&, int32_t) { return -1; }
+KAS_DEV void count(const ByStatus&, const KasChooseLaunch& a, int32_t n) { a.n_ok[0] = n; }
+
+template <class Part>
+KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s, const Part& part) {
   const kas_scenario_result r = a.sr[s];
   const kas_scenario_impact m = a.si[s];
   Entry e;
-  e.ok = r.status == KAS_OK ? 1 : 0;
+  e.ok = takes_part(part, a, s, r);
   uint32_t c[KAS_CHOOSE_MAX_KEYS];
 #pragma unroll
   for (int i = 0; i < KAS_CHOOSE_MAX_KEYS; ++i)
@@ -55,19 +63,20 @@ KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s) {
 
 // Workgroup `block` of the rank kernel.  tile: KAS_CHOOSE_TILE entries of LDS.  The grid covers S + 1 lanes: lane g < S is
 // scenario g, and lane g <= k is also slot g of chosen / row_off / node_off, which it writes when no scenario has that rank.
-KAS_DEV void rank_block(const KasChooseLaunch& a, int32_t block, Entry* tile) {
+template <class Part = ByStatus>
+KAS_DEV void rank_block(const KasChooseLaunch& a, int32_t block, Entry* tile, const Part& part = Part()) {
   const int32_t tid = kasw::tid();
   const int32_t g = block * KAS_CHOOSE_BLOCK + tid;
   const bool live = g < a.S;
   Entry mine;
   mine.hi = 0; mine.lo = 0; mine.cells = 0; mine.nodes = 0; mine.ok = 0;
-  if (live) mine = entry_of(a, g);
+  if (live) mine = entry_of(a, g, part);
   int32_t smaller = 0, n_ok = 0;
   int64_t cells = 0, nodes = 0, all_cells = 0, all_nodes = 0;
   for (int32_t base = 0; base < a.S; base += KAS_CHOOSE_TILE) {
     const int32_t n = a.S - base < KAS_CHOOSE_TILE ? a.S - base : KAS_CHOOSE_TILE;
     kasw::sync();                                               // (every lane has left the tile before)
-    for (int32_t i = tid; i < n; i += KAS_CHOOSE_BLOCK) tile[i] = entry_of(a, base + i);
+    for (int32_t i = tid; i < n; i += KAS_CHOOSE_BLOCK) tile[i] = entry_of(a, base + i, part);
     kasw::sync();
     for (int32_t i = 0; i < n; ++i) {                           // (every lane reads the same entry: an LDS broadcast)
       const Entry e = tile[i];
@@ -82,17 +91,17 @@ KAS_DEV void rank_block(const KasChooseLaunch& a, int32_t block, Entry* tile) {
     }
   }
   if (live) {
-    a.rank[g] = mine.ok ? smaller : -1;
+    a.rank[g] = mine.ok ? smaller : outside(part, a, g);
     if (mine.ok && smaller <= a.k) {
       if (smaller < a.k) a.chosen[smaller] = g;
       if (a.sizes) { a.row_off[smaller] = cells; a.node_off[smaller] = nodes; }
     }
   }
-  if (g >= n_ok && g <= a.k) {                                  // a slot behind the last OK scenario
+  if (g >= n_ok && g <= a.k) {                                  // a slot behind the last scenario that takes part
     if (g < a.k) a.chosen[g] = -1;
     if (a.sizes) { a.row_off[g] = all_cells; a.node_off[g] = all_nodes; }
   }
-  if (g == 0) a.n_ok[0] = n_ok;
+  if (g == 0) count(part, a, n_ok);
 }
 
 // ---- gather -------------------------------------------------------------------------------------------------------------

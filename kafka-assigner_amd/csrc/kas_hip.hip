@@ -30,6 +30,7 @@
 #include "kas_host_call.h"     // what a host call does: ranges, cell width, buffer sizes, the plan cache's choice
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
 #include "kas_choose.h"   // ranking and gathering the best scenarios: its kernels are kas_choose.hip's
+#include "kas_front.h"    // marking and ranking the Pareto front: kas_choose.hip's as well
 #include "kas_moves.h"    // the move list of a solve: its kernels are kas_moves.hip's
 
 // ---------------------------------------------------------------------------------------------
@@ -396,7 +397,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_ALL];              // device pools, record staging, impact records, a choice and its staging, a move list (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_END];              // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -450,6 +451,7 @@ struct kas_plan {
   int choose_ready = 0;
   KasChoosePlan choose;
   KasBuf b_ch_sizes, b_ch_segs;
+  KasBuf b_fr_cls;                      // the classes of a front (kas_front_device / 16), allocated at the plan's first such call
   // the move list on the device (kas_moves_device / 16): the scenario and segment tables are built on the host with the plan and
   // uploaded at the plan's first such call, with the (listed scenario, item) scratch
   int moves_ready = 0;
@@ -623,7 +625,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_ALL; ++i) {
+  for (int i = 0; i < KAS_HB_END; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -660,7 +662,7 @@ void kas_plan_destroy(kas_plan* p) {
   if (p->moves_pending) (void)hipEventSynchronize(p->ev_moves);
   for (KasBuf* b : {&p->b_mv_scen, &p->b_mv_segs, &p->b_mv_scratch}) kas_buf_free(b);
   if (p->ev_moves) (void)hipEventDestroy(p->ev_moves);
-  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs}) kas_buf_free(b);
+  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs, &p->b_fr_cls}) kas_buf_free(b);
   if (p->ev_impact) (void)hipEventDestroy(p->ev_impact);
   for (KasBuf* b : {&p->b_scen, &p->b_topics, &p->b_node_id, &p->b_node_rack, &p->b_accmask_off, &p->b_accmask,
                     &p->b_orph_off, &p->b_orph, &p->b_perm, &p->b_stats, &p->b_ord_flag, &p->b_sp_hist, &p->b_sp_quota,
@@ -1085,6 +1087,29 @@ int kas_rank_device(kas_ctx* ctx, const kas_scenario_result* scenario_results, c
   return KAS_E_OK;
 }
 
+int kas_front_rank_device(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                          int32_t n_scenarios, const kas_front_spec* spec, int32_t* rank, int32_t* chosen, int32_t* counts, int32_t* scratch,
+                          void* hip_stream) {
+  if (!ctx) return set_error(KAS_E_INVALID_ARG, "ctx == NULL");
+  if (n_scenarios < 0) return set_error(KAS_E_INVALID_ARG, "n_scenarios < 0");
+  const char* bad = kas_front_spec_error(spec, n_scenarios);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (!counts || (n_scenarios > 0 && (!scenario_results || !scenario_impact || !rank || !scratch)) || (spec->k > 0 && !chosen))
+    return set_error(KAS_E_INVALID_ARG, "kas_front_rank_device: an array the call reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(ctx->device));
+  KasFrontLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.c.sr = scenario_results; a.c.si = scenario_impact;
+  kas_front_fill_spec(&a, spec, n_scenarios);
+  a.c.rank = rank; a.c.chosen = chosen; a.c.n_ok = counts;       // (n_ok is counts[0])
+  a.cls = scratch; a.counts = counts;
+  void* st = hip_stream ? hip_stream : (void*)ctx->stream;
+  int e = kas_front_mark_launch(&a, st);
+  if (e == 0) e = kas_front_rank_launch(&a, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("front kernels: ") + hipGetErrorString((hipError_t)e));
+  return KAS_E_OK;
+}
+
 // The plan's size and segment tables (built on the host with the plan) on the device: allocated and uploaded at the plan's first
 // choice — blocking copies, once — and kept until the plan is rebuilt.
 static int kas_choose_prepare(kas_plan* p) {
@@ -1099,9 +1124,17 @@ static int kas_choose_prepare(kas_plan* p) {
   return KAS_E_OK;
 }
 
+// front: the Pareto front in place of the ranking (kas_front_device / 16; `spec` is then not read, `counts` is the call's)
 static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_choose_spec* spec,
-                           const kas_choice* ch, hipStream_t st) {
+                           const kas_choice* ch, hipStream_t st, const kas_front_spec* front = nullptr, int32_t* counts = nullptr) {
   const int32_t S = p->n_scenarios;
+  kas_choose_spec front_cs;
+  if (front) {
+    const char* bad = kas_front_spec_error(front, S);
+    if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+    front_cs = kas_front_choose_spec(front);
+    spec = &front_cs;
+  }
   const char* bad = kas_choose_spec_error(spec, S);
   if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
   const KasChoosePlan& cp = p->choose;
@@ -1110,7 +1143,7 @@ static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_ta
   if (ch->rows_cap < rows_need) return set_error(KAS_E_INVALID_ARG, "kas_choice: rows_cap below the packed rows of the k largest scenarios");
   if (ch->nodes_cap < nodes_need) return set_error(KAS_E_INVALID_ARG, "kas_choice: nodes_cap below the node records of the k largest scenarios");
   if ((S > 0 && !ch->rank) || (spec->k > 0 && !ch->chosen) || !ch->row_off || !ch->node_off || !ch->n_ok || (rows_need > 0 && !ch->rows) ||
-      (nodes_need > 0 && !ch->nodes))
+      (nodes_need > 0 && !ch->nodes) || (front && !counts))
     return set_error(KAS_E_INVALID_ARG, "kas_choice: an array the call writes is NULL");
   if (S > 0 && (!t->scenario_results || !imp->scenarios || (rows_need > 0 && !t->out) || (nodes_need > 0 && !imp->nodes)))
     return set_error(KAS_E_INVALID_ARG, "a table the choice reads is NULL");
@@ -1118,13 +1151,17 @@ static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_ta
     return set_error(KAS_E_INVALID_ARG, "kas_choose_device: the plan has no solve and impact pass to choose from");
   const int32_t cell = p->cells16 ? 2 : 4;
   if (((uintptr_t)ch->rows | (uintptr_t)t->out) % (uintptr_t)cell != 0 || ((uintptr_t)ch->nodes | (uintptr_t)imp->nodes) % 4 != 0 ||
-      ((uintptr_t)ch->row_off | (uintptr_t)ch->node_off) % 8 != 0)
+      ((uintptr_t)ch->row_off | (uintptr_t)ch->node_off) % 8 != 0 || (uintptr_t)counts % 4 != 0)
     return set_error(KAS_E_INVALID_ARG, "kas_choice: rows / out must be cell-aligned, node records 4-byte aligned, the offset arrays 8-byte aligned");
   const int64_t chunks = kas_choose_chunks(cp, cell);
   if ((int64_t)spec->k * chunks > INT32_MAX) return set_error(KAS_E_UNSUPPORTED, "kas_choice: k scenarios of this size are more than one gather launch takes");
   KAS_HIP_TRY(hipSetDevice(p->ctx->device));
-  const int rc = kas_choose_prepare(p);
+  int rc = kas_choose_prepare(p);
   if (rc != KAS_E_OK) return rc;
+  if (front && 4 * ((size_t)S + 1) > p->b_fr_cls.cap) {         // the class scratch, behind the pass that may still be using it
+    if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));
+    if ((rc = kas_buf_reserve(&p->b_fr_cls, 4 * ((size_t)S + 1), p->allocs, "front classes")) != KAS_E_OK) return rc;
+  }
   // ordered behind the plan's previous solve and its impact pass; a later solve waits for the gather as it waits for that pass
   if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
   if (p->impact_pending && p->impact_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
@@ -1136,7 +1173,18 @@ static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_ta
   a.rank = ch->rank; a.chosen = ch->chosen; a.row_off = ch->row_off; a.node_off = ch->node_off; a.n_ok = ch->n_ok;
   a.out = t->out; a.src_nodes = imp->nodes; a.rows = ch->rows; a.nodes = ch->nodes;
   a.src_cell = a.dst_cell = cell; a.chunks = (int32_t)chunks;
-  int e = kas_rank_launch(&a, st);
+  int e;
+  if (front) {
+    KasFrontLaunch f;
+    memset(&f, 0, sizeof(f));
+    kas_front_fill_spec(&f, front, S);
+    f.c = a;
+    f.cls = (int32_t*)p->b_fr_cls.p; f.counts = counts;
+    e = kas_front_mark_launch(&f, st);
+    if (e == 0) e = kas_front_rank_launch(&f, st);
+  } else {
+    e = kas_rank_launch(&a, st);
+  }
   if (e == 0) e = kas_gather_launch(&a, st);
   if (e != 0) return set_error(KAS_E_HIP, std::string("choose kernels: ") + hipGetErrorString((hipError_t)e));
   if (p->impact_pending) {
@@ -1159,6 +1207,23 @@ int kas_choose_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_t
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_choose_device16 needs a plan of kas_plan_create16");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_choose_impl(p, &t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+int kas_front_device(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_front_spec* spec, const kas_choice* ch,
+                     int32_t* counts, void* hip_stream) {
+  if (!p || !t || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_front_device16");
+  if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
+  return kas_choose_impl(p, t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts);
+}
+
+int kas_front_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const kas_front_spec* spec, const kas_choice* ch,
+                       int32_t* counts, void* hip_stream) {
+  if (!p || !t16 || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_front_device16 needs a plan of kas_plan_create16");
+  if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_choose_impl(p, &t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts);
 }
 
 // ---- the move list (kernels: kas_moves.hip) ----------------------------------------------------------------------------
@@ -1493,7 +1558,7 @@ struct KasCellPool {
 static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select,
                                  int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr,
                                  const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
-                                 bool rows_optional = false) {
+                                 bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1512,6 +1577,9 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.have_ch_node_off = hch->node_off != nullptr; in.have_ch_n_ok = hch->n_ok != nullptr;
     in.have_ch_rows = hch->rows != nullptr; in.have_ch_nodes = hch->nodes != nullptr;
   }
+  if (front) {                                                 // kas_solve_host_front / 16: `spec` is the planner's (hc.ch_spec)
+    in.choose = nullptr; in.front = front; in.have_fr_counts = counts != nullptr; in.ch_rows_optional = rows_optional;
+  }
   if (hmv) {                                                   // kas_solve_host_moves / kas_solve_host_choose_moves / 16
     in.moves = hmv; in.ch_rows_optional = rows_optional;
     if (!hch) { in.mv_select = select; in.mv_n_select = n_select; in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0; }
@@ -1525,6 +1593,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     std::string err;
     if ((rc = kas_plan_host_call(in, &hc, &err)) != KAS_E_OK) return set_error(rc, err);
   }
+  if (front) spec = &hc.ch_spec;
   batch = &hc.batch;                                           // (a 16-bit call: node i of every scenario has the id i)
   const KasShape& full = hc.full;
   const int K = hc.K;
@@ -1534,7 +1603,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_ALL; ++i)
+  for (int i = 0; i < KAS_HB_END; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -1670,12 +1739,24 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     a.src_cell = native16 ? 2 : 4; a.dst_cell = (int32_t)out.cell;            // (a widened call: narrowed on the way)
     a.chunks = (int32_t)hc.ch_chunks;
     if (he == hipSuccess) {
-      int e = kas_rank_launch(&a, s0);
+      int e;
+      if (front) {                                              // mark and front rank where the rank kernel runs
+        KasFrontLaunch f;
+        memset(&f, 0, sizeof(f));
+        kas_front_fill_spec(&f, front, (int32_t)S);
+        f.c = a;
+        f.cls = (int32_t*)ctx->hbuf[KAS_HB_FR_CLS].p; f.counts = (int32_t*)ctx->hbuf[KAS_HB_FR_COUNTS].p;
+        e = kas_front_mark_launch(&f, s0);
+        if (e == 0) e = kas_front_rank_launch(&f, s0);
+      } else {
+        e = kas_rank_launch(&a, s0);
+      }
       if (!hc.ch_gather_rows) a.sizes = (const KasChooseSize*)ctx->hbuf[KAS_HB_MV_SIZES0].p;
       if (e == 0) e = kas_gather_launch(&a, s0);
       hip_ok((hipError_t)e, "choose kernels");
     }
     copy(p_head, d_head, hc.ch_head.bytes, hipMemcpyDeviceToHost, s0, "download the choice");
+    if (front) copy(ctx->hbuf[KAS_HB_FR_COUNTS_PIN].p, ctx->hbuf[KAS_HB_FR_COUNTS].p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s0, "download the counts");
   }
   // a move list: the three kernels on s0 behind every range (and behind the rank kernel, whose chosen[] is a choice's list)
   char* const d_mvh = (char*)ctx->hbuf[KAS_HB_MV_HEAD].p;
@@ -1719,6 +1800,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     memcpy(hch->row_off, p_head + hc.ch_head.row_off, 8 * (size_t)(ch_k + 1));
     memcpy(hch->node_off, p_head + hc.ch_head.node_off, 8 * (size_t)(ch_k + 1));
     memcpy(hch->n_ok, p_head + hc.ch_head.n_ok, 4);
+    if (front) memcpy(counts, ctx->hbuf[KAS_HB_FR_COUNTS_PIN].p, 4 * sizeof(int32_t));
   }
   for (const KasHostRange& r : hc.ranges) {                    // (only what the ranges own: as the direct copies did)
     const KasExtent& t = r.own[KAS_POOL_TOPICS];
@@ -1866,6 +1948,22 @@ int kas_solve_host16_choose_moves(kas_ctx* ctx, const kas_batch_desc* batch, con
   const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, spec, hch, hmv, true);
+}
+
+int kas_solve_host_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_front_spec* spec, const kas_choice* hch,
+                         int32_t* counts, const kas_impact_tables* himp, const kas_moves* hmv) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, nullptr, hch, hmv, true, spec, counts);
+}
+
+int kas_solve_host16_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_front_spec* spec, const kas_choice* hch,
+                           int32_t* counts, const kas_impact_tables* himp, const kas_moves* hmv) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, nullptr, hch, hmv, true, spec, counts);
 }
 
 int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_desc* batch, const kas_tables* h) {

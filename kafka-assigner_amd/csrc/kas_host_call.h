@@ -16,6 +16,7 @@
 #include "kas_launch_plan.h"   // kas_cells16_ok, KAS_BUILT_*
 #include "kas_choose.h"        // the size and segment tables of kas_solve_host_choose
 #include "kas_moves.h"         // the scenario and segment tables of kas_solve_host_moves / kas_solve_host_choose_moves
+#include "kas_front.h"         // the spec of kas_solve_host_front
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -198,11 +199,15 @@ enum KasHostBuf {
   KAS_HB_MV_HEAD, KAS_HB_MV_MOVES, KAS_HB_MV_CELLS, // move_off and cell_off; the records and their list cells
   KAS_HB_MV_SIZES0,                                 // a choice without rows: the choose size table with no cells, for the gather
   KAS_HB_MV_HEAD_PIN,                               // pinned HOST staging of the offsets (records and cells go straight to the caller: exactly what was written)
-  KAS_HB_ALL
+  KAS_HB_ALL,                                       // the buffers of the calls above end here
+  // kas_solve_host_front / 16 alone (behind KAS_HB_ALL, for the same reason)
+  KAS_HB_FR_CLS = KAS_HB_ALL,                       // the classes the mark kernel leaves for the front rank kernel
+  KAS_HB_FR_COUNTS, KAS_HB_FR_COUNTS_PIN,           // n_ok, n_eligible, n_front, 0 and their pinned HOST staging
+  KAS_HB_END
 };
 static inline bool kas_host_buf_pinned(int32_t id) {
   return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN ||
-         id == KAS_HB_MV_HEAD_PIN;
+         id == KAS_HB_MV_HEAD_PIN || id == KAS_HB_FR_COUNTS_PIN;
 }
 
 // everything the decisions read
@@ -229,6 +234,10 @@ struct KasHostCallIn {
   const int32_t* mv_select = nullptr;
   int32_t mv_n_select = -1;
   bool ch_rows_optional = false;
+  // kas_solve_host_front / 16: the front in place of the ranking (`choose` is then not read: the front's criteria and k take its
+  // place in every decision above; ch_rows_optional as in a choice with moves, and `moves` may be left out)
+  const kas_front_spec* front = nullptr;
+  bool have_fr_counts = false;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -258,13 +267,14 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_ALL] = {};                // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_END] = {};                // what to reserve of each buffer; 0: this call must not touch it
   // kas_solve_host_choose / 16
   KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
   int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
   int64_t ch_chunks = 0;                        // gather workgroups per chosen scenario
   KasChooseHead ch_head;                        // where the arrays of the header lie in KAS_HB_CH_HEAD
   bool ch_gather_rows = true;                   // false: kas_solve_host_choose_moves without rows
+  kas_choose_spec ch_spec{};                    // the spec every choose decision was made from: the caller's, or a front's criteria and k
   // kas_solve_host_moves / kas_solve_host_choose_moves / 16
   KasMovesPlan moves;                           // the scenario and segment tables of the whole call, offsets as the device sees the pools
   std::vector<int32_t> mv_list;                 // the list as it is uploaded (empty for a choice: its chosen[] is on the device)
@@ -287,6 +297,14 @@ static inline int32_t kas_host_range_count(int64_t bytes, int64_t S, int32_t ran
 static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, std::string* err) {
   auto fail = [&](int code, const char* m) { if (err) *err = m; return code; };
   int rc;
+  if (in.front) {                                               // a front's own refusals come first
+    const char* bad = kas_front_spec_error(in.front, in.batch->n_scenarios);
+    if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
+    hc->ch_spec = kas_front_choose_spec(in.front);
+  } else if (in.choose) {
+    hc->ch_spec = *in.choose;
+  }
+  const kas_choose_spec* const choose = in.front ? &hc->ch_spec : in.choose;
   hc->all_rows = in.n_select < 0;
   if (!hc->all_rows && in.n_select > 0 && !in.select) return fail(KAS_E_INVALID_ARG, "select == NULL");
   hc->batch = *in.batch;
@@ -327,14 +345,14 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.impact) {
     hc->imp_base.assign((size_t)S + 1, 0);
     for (int64_t s = 0; s < S; ++s) hc->imp_base[(size_t)s + 1] = hc->imp_base[(size_t)s] + (b->scenarios[s].n_nodes > 0 ? b->scenarios[s].n_nodes : 0);
-    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !in.choose))
+    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !choose))
       return fail(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
   }
   // a choice: the spec, then the room for any k scenarios (which ones win is not known before the solve), then the arrays
-  if (in.choose) {
-    const char* bad = kas_choose_spec_error(in.choose, S);
+  if (choose) {
+    const char* bad = kas_choose_spec_error(choose, S);
     if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
-    const int64_t k = in.choose->k;
+    const int64_t k = choose->k;
     kas_choose_plan_build(b, &hc->choose);
     kas_choose_k_largest(hc->choose, (int32_t)k, &hc->ch_rows_need, &hc->ch_nodes_need);
     hc->ch_gather_rows = !(in.ch_rows_optional && in.rows_cap == 0 && !in.have_ch_rows);
@@ -342,7 +360,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     if (in.rows_cap < hc->ch_rows_need) return fail(KAS_E_INVALID_ARG, "kas_choice: rows_cap below the packed rows of the k largest scenarios");
     if (in.nodes_cap < hc->ch_nodes_need) return fail(KAS_E_INVALID_ARG, "kas_choice: nodes_cap below the node records of the k largest scenarios");
     if ((S > 0 && !in.have_ch_rank) || (k > 0 && !in.have_ch_chosen) || !in.have_ch_row_off || !in.have_ch_node_off || !in.have_ch_n_ok ||
-        (hc->ch_rows_need > 0 && !in.have_ch_rows) || (hc->ch_nodes_need > 0 && !in.have_ch_nodes))
+        (hc->ch_rows_need > 0 && !in.have_ch_rows) || (hc->ch_nodes_need > 0 && !in.have_ch_nodes) || (in.front && !in.have_fr_counts))
       return fail(KAS_E_INVALID_ARG, "kas_choice: an array the call writes is NULL");
     hc->ch_chunks = kas_choose_chunks(hc->choose, in.cells16 ? 2 : 4);
     if (k * hc->ch_chunks > INT32_MAX) return fail(KAS_E_UNSUPPORTED, "kas_choice: k scenarios of this size are more than one gather launch takes");
@@ -353,8 +371,8 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     const char* bad = kas_moves_args_error(in.moves, in.cells16 ? 2 : 4);
     if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
     hc->mv_list.clear();
-    if (in.choose) {
-      hc->mv_n = in.choose->k;
+    if (choose) {
+      hc->mv_n = choose->k;
     } else if (in.mv_n_select < 0) {
       hc->mv_n = S;
       for (int64_t s = 0; s < S; ++s) hc->mv_list.push_back((int32_t)s);
@@ -369,7 +387,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     kas_moves_plan_build(b, &hc->moves);
     bad = kas_moves_shape_error(hc->moves, hc->mv_n);
     if (bad[0]) return fail(KAS_E_UNSUPPORTED, bad);
-    if (in.choose) kas_moves_k_largest(hc->moves, in.choose->k, &hc->mv_room_moves, &hc->mv_room_cells);
+    if (choose) kas_moves_k_largest(hc->moves, choose->k, &hc->mv_room_moves, &hc->mv_room_cells);
     else kas_moves_room(hc->moves, hc->mv_list.data(), hc->mv_n, &hc->mv_room_moves, &hc->mv_room_cells);
     hc->mv_moves_cap = in.moves->moves_cap < hc->mv_room_moves ? in.moves->moves_cap : hc->mv_room_moves;
     hc->mv_cells_cap = in.moves->cells_cap < hc->mv_room_cells ? in.moves->cells_cap : hc->mv_room_cells;
@@ -397,7 +415,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   by[KAS_HB_SR] = by[KAS_HB_SR_PIN] = sizeof(kas_scenario_result) * (size_t)(S + 1);
   by[KAS_HB_IMP_NODES] = in.impact ? sizeof(kas_node_impact) * (size_t)(hc->imp_base[(size_t)S] + 1) : 0;
   by[KAS_HB_IMP_SCEN] = in.impact ? sizeof(kas_scenario_impact) * (size_t)(S + 1) : 0;
-  if (in.choose) {
+  if (choose) {
     by[KAS_HB_CH_SIZES] = sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1);
     by[KAS_HB_CH_SEGS] = sizeof(KasChooseSeg) * (hc->choose.segs.size() + 1);
     by[KAS_HB_CH_HEAD] = by[KAS_HB_CH_HEAD_PIN] = hc->ch_head.bytes;
@@ -407,12 +425,17 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.moves) {
     by[KAS_HB_MV_SCEN] = sizeof(KasMovesScen) * (hc->moves.scen.size() + 1);
     by[KAS_HB_MV_SEGS] = sizeof(KasMovesSeg) * (hc->moves.segs.size() + 1);
-    by[KAS_HB_MV_SELECT] = in.choose ? 0 : 4 * (size_t)(hc->mv_n + 1);
+    by[KAS_HB_MV_SELECT] = choose ? 0 : 4 * (size_t)(hc->mv_n + 1);
     by[KAS_HB_MV_SCRATCH] = sizeof(KasMovesCount) * ((size_t)hc->mv_n * (size_t)hc->moves.max_items + 1);
     by[KAS_HB_MV_HEAD] = by[KAS_HB_MV_HEAD_PIN] = 16 * (size_t)(hc->mv_n + 1);
     by[KAS_HB_MV_MOVES] = sizeof(kas_move) * (size_t)(hc->mv_moves_cap + 1);
     by[KAS_HB_MV_CELLS] = (size_t)cell * (size_t)(hc->mv_cells_cap + 8);
-    by[KAS_HB_MV_SIZES0] = in.choose && !hc->ch_gather_rows ? sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1) : 0;
+    by[KAS_HB_MV_SIZES0] = choose && !hc->ch_gather_rows ? sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1) : 0;
+  }
+  if (in.front) {
+    if (!hc->ch_gather_rows) by[KAS_HB_MV_SIZES0] = sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1);   // (with or without moves)
+    by[KAS_HB_FR_CLS] = 4 * (size_t)(S + 1);
+    by[KAS_HB_FR_COUNTS] = by[KAS_HB_FR_COUNTS_PIN] = 4 * sizeof(int32_t);
   }
   return KAS_E_OK;
 }

@@ -31,6 +31,7 @@ SYMBOLS = [
     "kas_rank_device", "kas_choose_device", "kas_choose_device16", "kas_solve_host_choose", "kas_solve_host16_choose",
     "kas_moves_device", "kas_moves_device16", "kas_solve_host_moves", "kas_solve_host16_moves", "kas_solve_host_choose_moves",
     "kas_solve_host16_choose_moves",
+    "kas_front_rank_device", "kas_front_device", "kas_front_device16", "kas_solve_host_front", "kas_solve_host16_front",
 ]
 
 _LIB = None
@@ -146,6 +147,17 @@ def load():
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec),
                        C.POINTER(abi.Choice), C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves)]
+    L.kas_front_rank_device.restype = C.c_int
+    L.kas_front_rank_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.FrontSpec), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    for fn in (L.kas_front_device, L.kas_front_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.POINTER(abi.FrontSpec),
+                       C.POINTER(abi.Choice), C.c_void_p, C.c_void_p]
+    for fn in (L.kas_solve_host_front, L.kas_solve_host16_front):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.FrontSpec),
+                       C.POINTER(abi.Choice), C.c_void_p, C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves)]
     if L.kas_abi_version() != abi.KAS_ABI_VERSION:
         raise ImportError("libkas_hip.so ABI version mismatch")
     _LIB = L
@@ -270,6 +282,19 @@ class Plan:
                         choice_nodes or None, int(nodes_cap))
         fn = self._lib.kas_choose_device16 if self.cells16 else self._lib.kas_choose_device
         _check(fn(self._h, C.byref(t), C.byref(imp), C.byref(spec), C.byref(ch), C.c_void_p(stream) if stream else None))
+
+    def front_device(self, spec, out: int, scenario_results: int, nodes: int, scenarios: int, rank: int, chosen: int,
+                     row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int, choice_nodes: int, nodes_cap: int, counts: int,
+                     stream: int = 0):
+        """kas_front_device / 16: choose_device with the Pareto front under `spec` (abi.front_spec) in place of the ranking;
+        counts: int32 [4] on the device (n_ok, n_eligible, n_front, 0).  Raw device pointers (int)."""
+        t = abi.Tables()
+        t.out = out or None; t.scenario_results = scenario_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        ch = abi.Choice(rank or None, chosen or None, row_off or None, node_off or None, n_ok or None, rows or None, int(rows_cap),
+                        choice_nodes or None, int(nodes_cap))
+        fn = self._lib.kas_front_device16 if self.cells16 else self._lib.kas_front_device
+        _check(fn(self._h, C.byref(t), C.byref(imp), C.byref(spec), C.byref(ch), counts or None, C.c_void_p(stream) if stream else None))
 
     def moves_device(self, mask, select: int, n_select: int, cur: int, out: int, topic_results: int, move_off: int, cell_off: int,
                      moves: int, moves_cap: int, cells: int, cells_cap: int, aux: int = 0, stream: int = 0):
@@ -623,6 +648,75 @@ def solve_host_choose_moves(fb: FlatBatch, keys, k: int, mask=("replicas",), row
     c.nodes = c.nodes[:int(c.node_off[kk])]
     ml.select = c.chosen
     return ho, c, _trim(ml)
+
+
+def front_rank_device(scenario_results: int, scenario_impact: int, n_scenarios: int, spec, rank: int, chosen: int, counts: int,
+                      scratch: int, stream: int = 0, ctx: Optional[DeviceContext] = None):
+    """kas_front_rank_device: mark and rank the Pareto front of n_scenarios records on the device under `spec` (abi.front_spec).
+    Raw device pointers (int): the two record arrays in, rank int32 [S], chosen int32 [k] and counts int32 [4] out, scratch
+    int32 [S].  Asynchronous on `stream`."""
+    ctx = ctx or default_context()
+    _check(load().kas_front_rank_device(ctx._h, scenario_results or None, scenario_impact or None, int(n_scenarios), C.byref(spec),
+                                        rank or None, chosen or None, counts or None, scratch or None,
+                                        C.c_void_p(stream) if stream else None))
+
+
+@dataclass
+class Front(Choice):
+    """What kas_solve_host_front leaves: a Choice whose rank holds a member's rank or a class code (abi.KAS_FRONT_*), plus the
+    counts; n_front > len(chosen) when k cut the list."""
+    n_eligible: int = 0
+    n_front: int = 0
+
+
+def solve_host_front(fb: FlatBatch, spec, mask=None, rows: bool = True, cells16: bool = False, moves_cap: Optional[int] = None,
+                     cells_cap: Optional[int] = None, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_front / 16: solve_host_choose_moves with the Pareto front under `spec` (abi.front_spec) in place of the
+    ranking.  mask=None asks for no moves; rows=False hands the library no rows array.
+    Returns (HostOutputs without rows, Front, MoveList or None)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)                 # (held until the call returns: the table only borrows it)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    S, kk = fb.n_scenarios, max(int(spec.k), 0)
+    rows_cap = int(np.sort(packed_cells(fb))[::-1][:kk].sum()) if rows else 0
+    nodes_cap = int(np.sort(np.clip(fb.scen["n_nodes"], 0, None).astype(np.int64))[::-1][:kk].sum())
+    c = Front(rank=np.full(max(S, 1), -9, np.int32)[:S], chosen=np.full(max(kk, 1), -9, np.int32)[:kk],
+              row_off=np.full(kk + 1, -9, np.int64), node_off=np.full(kk + 1, -9, np.int64), n_ok=-9,
+              rows=np.zeros(max(rows_cap, 1), np.uint16 if cells16 else np.int32)[:rows_cap],
+              nodes=np.zeros(max(nodes_cap, 1), abi.NODE_IMPACT_DTYPE)[:nodes_cap],
+              scenarios=np.zeros(max(S, 1), abi.SCENARIO_IMPACT_DTYPE)[:S])
+    n_ok = np.full(1, -9, np.int32)
+    counts = np.full(4, -9, np.int32)
+
+    def p(a):
+        return a.ctypes.data if a.size else None
+    ch = abi.Choice(p(c.rank), p(c.chosen), p(c.row_off), p(c.node_off), p(n_ok), p(c.rows), rows_cap, p(c.nodes), nodes_cap)
+    imp = abi.ImpactTables(None, p(c.scenarios))
+    ml = mv = None
+    if mask is not None:
+        room_rows = int(np.sort(scenario_rows(fb))[::-1][:kk].sum())
+        room_cells = int(np.sort(packed_cells(fb))[::-1][:kk].sum())
+        ml, mv = _move_arrays(mask, kk, room_rows if moves_cap is None else int(moves_cap),
+                              room_cells if cells_cap is None else int(cells_cap), cells16)
+    fn = L.kas_solve_host16_front if cells16 else L.kas_solve_host_front
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), counts.ctypes.data, C.byref(imp),
+              C.byref(mv) if mv is not None else None))
+    c.n_ok, c.n_eligible, c.n_front = int(n_ok[0]), int(counts[1]), int(counts[2])
+    assert int(counts[0]) == c.n_ok and int(counts[3]) == 0
+    c.rows = c.rows[:int(c.row_off[kk])] if rows else c.rows[:0]
+    c.nodes = c.nodes[:int(c.node_off[kk])]
+    if ml is not None:
+        ml.select = c.chosen
+        ml = _trim(ml)
+    return ho, c, ml
 
 
 def solve_host_sharded(fb: FlatBatch, ctxs) -> HostOutputs:

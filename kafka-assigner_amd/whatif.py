@@ -19,6 +19,9 @@ best() lets the GPU also compare the variants (kas_solve_host_choose): plan.best
 "moved_replicas")) returns the three best variants that solve, best first, each with its rows and its per-broker impact;
 nothing comes back for the others but their records.
 
+front() returns the variants that no other variant beats on all the named criteria at once (kas_solve_host_front), optionally
+among those within hard bounds: plan.front(variants, by=("moved_replicas", "replica_spread"), within={"max_inbound": 200}).
+
 moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for the rows that change instead of every row, compacted
 on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
 results[0].reassignment() -> the Kafka reassignment JSON object of those partitions.  solve(..., moves=...) returns the moves of
@@ -116,6 +119,12 @@ class VariantResult:
         if self._nodes is None:
             raise ValueError("no impact records: solve with impact=True")
         return {int(b): {f: int(r[f]) for f in abi.NODE_IMPACT_FIELDS} for b, r in zip(self._node_ids, self._nodes)}
+
+
+class Front(list):
+    """What WhatIf.front returns: the members (VariantResult) in member order, and what became of every variant."""
+    n_ok = n_eligible = n_front = 0
+    classes: List[str] = []
 
 
 class WhatIf:
@@ -254,6 +263,47 @@ class WhatIf:
         self._fb = fb
         res = []
         for j in range(min(k, ch.n_ok)):
+            s = int(ch.chosen[j])
+            sr = ho.scenario_results[s]
+            off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
+            extra = {f: int(ch.scenarios[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
+            if ml is not None:
+                extra.update(_moves=ml.of(j), _moves_mask=ml.mask)
+            res.append(VariantResult(label=variants[s].label, status=int(sr["status"]), fail_topic=None,
+                                     fail_partition=int(sr["fail_partition"]), moved_replicas=int(sr["moved_replicas"]),
+                                     moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]), rank=j,
+                                     _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
+                                     _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
+                                     **extra))
+        return res
+
+    def front(self, variants: Sequence[Variant], by: Sequence[str] = ("moved_replicas", "replica_spread"), within=None, k: int = 16,
+              moves=None, rows: bool = True) -> "Front":
+        """The Pareto front of the variants, marked and ranked on the GPU (kas_solve_host_front): every variant that solves,
+        respects the hard bounds in `within` ({criterion: limit}, e.g. {"max_inbound": 200}) and is beaten by no other such
+        variant on all the criteria in `by` at once (abi.KEY_NAMES; one to four, smaller is better; of variants with identical
+        criteria the earliest survives).  Up to k members come back in the order best() would give them, each with
+        assignment(), broker_impact(), its rank and — with moves=(kinds) — moves(); rows=False fetches no rows.  The list also
+        carries n_ok, n_eligible, n_front (> len when k cut it) and classes: per variant "member", "dominated", "over_limit"
+        or "failed"."""
+        from . import native
+        by = [by] if isinstance(by, str) else list(by)
+        within = dict(within or {})
+        for name in by + list(within):
+            if name not in abi.KEYS:
+                raise ValueError("unknown criterion %r (one of %s)" % (name, ", ".join(abi.KEY_NAMES)))
+        if not 1 <= len(by) <= abi.KAS_CHOOSE_MAX_KEYS:
+            raise ValueError("by: one to four criteria")
+        if len(within) > abi.KAS_CHOOSE_MAX_KEYS or any(int(v) < 0 for v in within.values()):
+            raise ValueError("within: at most four bounds, none negative")
+        fb = self.flat_batch(variants)
+        k = max(0, min(int(k), len(variants)))
+        ho, ch, ml = native.solve_host_front(fb, abi.front_spec(by, within, k), None if moves is None else abi.move_mask(moves), rows=rows)
+        self._fb = fb
+        res = Front()
+        res.n_ok, res.n_eligible, res.n_front = ch.n_ok, ch.n_eligible, ch.n_front
+        res.classes = [abi.FRONT_CLASSES[min(int(r), 0)] for r in ch.rank]
+        for j in range(min(k, ch.n_front)):
             s = int(ch.chosen[j])
             sr = ho.scenario_results[s]
             off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
