@@ -590,6 +590,91 @@ int kas_solve_host16_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_
                            const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
                            const kas_impact_tables* host_impact, const kas_moves* host_moves);
 
+/* ---- rack impact: what a scenario does to racks, reduced on the device (added under ABI v6) --------------------------
+ * A rack pass behind the impact pass.  Rows, C, O, clen, olen and "names a node" are exactly those of kas_node_impact above;
+ * only topics whose kas_topic_result.status == KAS_OK contribute.
+ *   report rack table   every scenario has an int32 table rr[i], the rack index of node i, 0 <= rr[i] < R_s with
+ *                       R_s = 1 + max rr (R_s = 0 when the scenario has no nodes).  The caller may pass it as report_rack,
+ *                       an array parallel to batch->node_rack (indexed by node_off + i) — so that a variant solved with
+ *                       --disable_rack_awareness, whose solver table is id-as-rack, is still reported against the real
+ *                       racks; NULL means the batch's own node_rack.
+ *   a cell's rack       a cell that names node i has rack rr[i]; a cell of C that names no node has no rack and is not
+ *                       "known".
+ *   per row             kB = known cells of C, dB = distinct racks among them; kA = cells of O that name a node, dA =
+ *                       distinct racks among them.
+ * Ranking or fronting by these figures is not part of this pass: kas_choose_spec and the rank kernels read
+ * kas_scenario_result and kas_scenario_impact only.  The scenario record is laid out (sixteen non-negative int32) so that
+ * its fields can become criteria. */
+#define KAS_RACK_LIMIT 4096   /* racks per scenario (the reduce kernel's R_s x 7 int32 histogram lives in the LDS) */
+
+/* One per rack r < R_s; every field a sum over the scenario's nodes with rr == r */
+typedef struct kas_rack_impact {
+  int32_t nodes;              /* nodes with rr == r                                            */
+  int32_t replicas_before;    /* sums of the kas_node_impact fields of the same names          */
+  int32_t replicas_after;
+  int32_t leaders_before;
+  int32_t leaders_after;
+  int32_t inbound;
+  int32_t outbound;
+  int32_t reserved;           /* 0 */
+} kas_rack_impact;
+
+/* Per scenario (every field 0 when the scenario has no nodes) */
+typedef struct kas_scenario_rack_impact {
+  /* summed over rows */
+  int32_t colocated_before;         /* sum of kB - dB: replicas that share a rack with an earlier one of their row  */
+  int32_t colocated_after;          /* sum of kA - dA                                                               */
+  int32_t rows_colocated_before;    /* rows with kB > dB                                                            */
+  int32_t rows_colocated_after;     /* rows with kA > dA                                                            */
+  int32_t single_rack_rows_before;  /* rows with kB >= 2 and dB == 1                                                */
+  int32_t single_rack_rows_after;   /* rows with kA >= 2 and dA == 1                                                */
+  int32_t new_rack_replicas;        /* cells o of O that name a node, are not in C, and whose rack is the rack of no
+                                       known cell of C                                                              */
+  int32_t rows_losing_racks;        /* rows with dA < dB                                                            */
+  /* taken over the scenario's racks */
+  int32_t n_racks;                  /* R_s                                                                          */
+  int32_t max_rack_inbound, max_rack_outbound;
+  int32_t min_rack_replicas_after, max_rack_replicas_after;
+  int32_t min_rack_leaders_after, max_rack_leaders_after;
+  int32_t reserved;                 /* 0 */
+} kas_scenario_rack_impact;
+
+/* Where the records go.  Scenario s owns R_s rack records at racks[rack_off[s]]; rack_off[0 .. S] is the prefix sum of R_s,
+ * computed on the host and returned to the caller.  racks_cap: the kas_rack_impact records `racks` has room for. */
+typedef struct kas_rack_tables {
+  kas_rack_impact*          racks;
+  kas_scenario_rack_impact* scenarios;   /* [S] */
+  int64_t*                  rack_off;    /* [S + 1], HOST memory in every entry point (may be NULL in the device form) */
+  int64_t                   racks_cap;
+} kas_rack_tables;
+
+/* The rack impact of the plan's previous solve and impact pass: device_tables are the tables that solve used,
+ * device_impact the records that impact pass wrote (device pointers; device_out->racks and ->scenarios too).
+ * host_report_rack: HOST memory, node_pool_len entries, or NULL.  Asynchronous, ordered behind the plan's previous solve and
+ * impact pass; it writes every record of its outputs itself.  A plan's first call, or a call whose table differs from the
+ * previous call's (the contents are compared, not the pointer), uploads the plan's copy of the table and rack_off with
+ * blocking copies; later calls only enqueue.
+ * Refused before any GPU work, in this order: KAS_E_INVALID_ARG for a NULL argument or array, a non-NULL table for a batch
+ * without nodes, or a negative entry of a scenario's table; KAS_E_UNSUPPORTED for a scenario with R_s > KAS_RACK_LIMIT;
+ * KAS_E_INVALID_ARG for racks_cap below the sum of R_s; KAS_E_INVALID_ARG for a plan without a solve and an impact pass.
+ * No scenario is refused for its node count: where the id lookup and the scenario's racks (uint16 per node) do not fit
+ * the LDS together, the row kernel reads the racks from global memory. */
+int kas_rack_impact_device(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                           const int32_t* host_report_rack, const kas_rack_tables* device_out, void* hip_stream);
+int kas_rack_impact_device16(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                             const int32_t* host_report_rack, const kas_rack_tables* device_out, void* hip_stream);
+
+/* kas_solve_host_impact / 16 plus the rack pass on each scenario range's stream, right behind its impact pass; the rack
+ * records, the scenario rack records and rack_off come back in host_racks (host memory).  host_impact->nodes may be NULL:
+ * the node records then stay on the device — the call a rack report wants.  report_rack: as above (host memory).  The
+ * refusals above apply, behind those of kas_solve_host_impact. */
+int kas_solve_host_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                               const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact,
+                               const int32_t* report_rack, const kas_rack_tables* host_racks);
+int kas_solve_host16_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                 const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact,
+                                 const int32_t* report_rack, const kas_rack_tables* host_racks);
+
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */
 int  kas_host_alloc(int64_t bytes, void** out_ptr);

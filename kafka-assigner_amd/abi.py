@@ -249,6 +249,22 @@ def front_spec(by, within=None, k: int = 0) -> "FrontSpec":
     return spec
 
 
+# the rack pass behind the impact pass (kas_rack_impact / kas_scenario_rack_impact) and where its records go (kas_rack_tables)
+KAS_RACK_LIMIT = 4096
+RACK_IMPACT_FIELDS = ("nodes", "replicas_before", "replicas_after", "leaders_before", "leaders_after", "inbound", "outbound")
+SCENARIO_RACK_ROW_FIELDS = ("colocated_before", "colocated_after", "rows_colocated_before", "rows_colocated_after",
+                            "single_rack_rows_before", "single_rack_rows_after", "new_rack_replicas", "rows_losing_racks")
+SCENARIO_RACK_FIELDS = SCENARIO_RACK_ROW_FIELDS + ("n_racks", "max_rack_inbound", "max_rack_outbound", "min_rack_replicas_after",
+                                                   "max_rack_replicas_after", "min_rack_leaders_after", "max_rack_leaders_after")
+RACK_IMPACT_DTYPE = _np.dtype([(f, "<i4") for f in RACK_IMPACT_FIELDS] + [("reserved", "<i4")])
+SCENARIO_RACK_IMPACT_DTYPE = _np.dtype([(f, "<i4") for f in SCENARIO_RACK_FIELDS] + [("reserved", "<i4")])
+RACK_ENTRIES = ("kas_rack_impact_device", "kas_rack_impact_device16", "kas_solve_host_rack_impact", "kas_solve_host16_rack_impact")
+
+
+class RackTables(C.Structure):
+    _fields_ = [("racks", C.c_void_p), ("scenarios", C.c_void_p), ("rack_off", C.c_void_p), ("racks_cap", C.c_int64)]
+
+
 # the move list (kas_move / kas_moves): a row's flags, the 16-byte record, where a list goes
 KAS_MOVE_REPLICAS, KAS_MOVE_LEADER, KAS_MOVE_ORDER = 1, 2, 4
 MOVE_KINDS = {"replicas": KAS_MOVE_REPLICAS, "leader": KAS_MOVE_LEADER, "order": KAS_MOVE_ORDER}
@@ -282,6 +298,7 @@ def move_mask(kinds) -> int:
 
 assert MOVE_DTYPE.itemsize == C.sizeof(Move) == 16 and C.sizeof(Moves) == 56
 assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32
+assert RACK_IMPACT_DTYPE.itemsize == 32 and SCENARIO_RACK_IMPACT_DTYPE.itemsize == 64 and C.sizeof(RackTables) == 32
 assert C.sizeof(ChooseSpec) == 24 and C.sizeof(Choice) == 72 and C.sizeof(FrontSpec) == 60
 assert TOPIC_RESULT_DTYPE.itemsize == C.sizeof(TopicResult) == 16
 assert SCENARIO_RESULT_DTYPE.itemsize == C.sizeof(ScenarioResult) == 32

@@ -29,6 +29,7 @@
 #include "kas_launch_plan.h"   // which kernels a solve launches: the resolver the emulator shares
 #include "kas_host_call.h"     // what a host call does: ranges, cell width, buffer sizes, the plan cache's choice
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
+#include "kas_racks.h"    // the rack pass behind it: its kernels are kas_racks.hip's
 #include "kas_choose.h"   // ranking and gathering the best scenarios: its kernels are kas_choose.hip's
 #include "kas_front.h"    // marking and ranking the Pareto front: kas_choose.hip's as well
 #include "kas_moves.h"    // the move list of a solve: its kernels are kas_moves.hip's
@@ -397,7 +398,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_END];              // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_LAST];             // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -447,6 +448,15 @@ struct kas_plan {
   hipEvent_t ev_impact = nullptr;       // recorded behind the plan's last impact pass
   hipStream_t impact_stream = nullptr;
   int impact_pending = 0;               // ev_impact has been recorded
+  // rack pass (kas_rack_impact_device / 16): the report table and rack_off are built and uploaded at the plan's first rack call
+  // and again when a call brings another table; ev_impact is recorded again behind every rack pass
+  int rack_ready = 0;
+  KasRackPlan rack;
+  KasBuf b_rk_rr, b_rk_off, b_rk_sums;
+  int64_t node_pool_len = 0;
+  int rack_host_ready = 0;              // the two below have been read back (a rack call without the batch in host memory)
+  std::vector<kas_scenario_desc> rk_scen;
+  std::vector<int32_t> rk_node_rack;
   // choosing on the device (kas_choose_device / 16): the size and segment tables, built at the plan's first such call
   int choose_ready = 0;
   KasChoosePlan choose;
@@ -625,7 +635,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_END; ++i) {
+  for (int i = 0; i < KAS_HB_LAST; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -662,7 +672,8 @@ void kas_plan_destroy(kas_plan* p) {
   if (p->moves_pending) (void)hipEventSynchronize(p->ev_moves);
   for (KasBuf* b : {&p->b_mv_scen, &p->b_mv_segs, &p->b_mv_scratch}) kas_buf_free(b);
   if (p->ev_moves) (void)hipEventDestroy(p->ev_moves);
-  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs, &p->b_fr_cls}) kas_buf_free(b);
+  for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs, &p->b_fr_cls,
+                    &p->b_rk_rr, &p->b_rk_off, &p->b_rk_sums}) kas_buf_free(b);
   if (p->ev_impact) (void)hipEventDestroy(p->ev_impact);
   for (KasBuf* b : {&p->b_scen, &p->b_topics, &p->b_node_id, &p->b_node_rack, &p->b_accmask_off, &p->b_accmask,
                     &p->b_orph_off, &p->b_orph, &p->b_perm, &p->b_stats, &p->b_ord_flag, &p->b_sp_hist, &p->b_sp_quota,
@@ -741,6 +752,7 @@ static int kas_plan_build(kas_plan* p, const kas_batch_desc* batch) {
   if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));   // (its work list is about to go)
   if (p->moves_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_moves));
   p->impact_ready = 0; p->impact_pending = 0; p->choose_ready = 0; p->moves_ready = 0; p->moves_pending = 0;
+  p->rack_ready = 0; p->rack_host_ready = 0; p->node_pool_len = batch->node_pool_len;
   kas_moves_plan_build(batch, &p->moves);
   kas_choose_plan_build(batch, &p->choose);                    // (host arithmetic over the descriptors: kas_choose_device refuses from it before any GPU work)
   p->shape = sh;
@@ -1065,6 +1077,107 @@ int kas_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_t
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_impact_device16 needs a plan of kas_plan_create16");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_impact_impl(p, &t, imp, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
+}
+
+// ---- the rack pass (kernels: kas_racks.hip) -----------------------------------------------------------------------------
+// The rack impact of the plan's previous solve and impact pass, from the tables `t` and the records `imp` (device pointers),
+// into rk->racks / rk->scenarios (device pointers), on `st`.  report: the caller's table in host memory or NULL; hb: the
+// plan's batch in host memory (the host path's slice) or NULL (the descriptors and node_rack are then read back once).
+// rk->rack_off (host memory, may be NULL) gets the plan's prefix sums.
+static int kas_rack_impl(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const int32_t* report, const kas_rack_tables* rk,
+                         hipStream_t st, const kas_batch_desc* hb) {
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  kas_batch_desc b;
+  memset(&b, 0, sizeof(b));
+  if (hb) {
+    b = *hb;
+  } else {
+    if (!p->rack_host_ready) {
+      p->rk_scen.resize((size_t)p->n_scenarios); p->rk_node_rack.resize((size_t)p->node_pool_len);
+      if (!p->rk_scen.empty()) KAS_HIP_TRY(hipMemcpy(p->rk_scen.data(), p->b_scen.p, sizeof(kas_scenario_desc) * p->rk_scen.size(), hipMemcpyDeviceToHost));
+      if (!p->rk_node_rack.empty()) KAS_HIP_TRY(hipMemcpy(p->rk_node_rack.data(), p->b_node_rack.p, sizeof(int32_t) * p->rk_node_rack.size(), hipMemcpyDeviceToHost));
+      p->rack_host_ready = 1;
+    }
+    b.n_scenarios = p->n_scenarios; b.scenarios = p->rk_scen.data();
+    b.node_rack = p->rk_node_rack.data(); b.node_pool_len = p->node_pool_len;
+  }
+  if (report && b.node_pool_len <= 0) return set_error(KAS_E_INVALID_ARG, "report_rack: a table for a batch without nodes");
+  const int32_t* table = report ? report : b.node_rack;
+  const size_t NP = (size_t)(b.node_pool_len > 0 ? b.node_pool_len : 0);
+  const int64_t S = p->n_scenarios;
+  // the same table as the previous call's (its contents): nothing to build, nothing to upload
+  const bool same = p->rack_ready && kas_rack_plan_serves(p->rack, table, b.node_pool_len);
+  KasRackPlan fresh;
+  if (!same) {
+    std::string err;
+    const int rc = kas_rack_plan_build(&b, table, p->shape.n_max, p->shape.idmap_entries, p->shape.need_bsearch, p->cells16, -1, &fresh, &err);
+    if (rc != KAS_E_OK) return set_error(rc, err);
+  }
+  const KasRackPlan& want = same ? p->rack : fresh;
+  if (rk->racks_cap < want.rack_off[(size_t)S]) return set_error(KAS_E_INVALID_ARG, "kas_rack_tables: racks_cap below the sum of the scenarios' rack counts");
+  if ((S > 0 && !rk->scenarios) || (want.rack_off[(size_t)S] > 0 && !rk->racks))
+    return set_error(KAS_E_INVALID_ARG, "kas_rack_tables: racks / scenarios == NULL");
+  if (S > 0 && (p->last_slot < 0 || !p->impact_pending || !p->impact_ready))
+    return set_error(KAS_E_INVALID_ARG, "kas_rack_impact_device: the plan has no solve and impact pass to report on");
+  if (S > 0 && (!imp->scenarios || !t->out || !t->topic_results || (p->shape.cur_need > 0 && !t->cur) || (p->shape.aux_need > 0 && !t->aux) ||
+                (p->impact.nodes_total > 0 && !imp->nodes)))
+    return set_error(KAS_E_INVALID_ARG, "a table the rack pass reads is NULL");
+  if (!same) {
+    if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));   // (an earlier rack pass may still read the tables)
+    p->rack_ready = 0;
+    p->rack = std::move(fresh);
+    int rc;
+    if ((rc = kas_buf_reserve(&p->b_rk_rr, sizeof(int32_t) * (NP + 1), p->allocs, "report rack table")) != KAS_E_OK ||
+        (rc = kas_buf_reserve(&p->b_rk_off, sizeof(int64_t) * ((size_t)S + 1), p->allocs, "rack record offsets")) != KAS_E_OK ||
+        (rc = kas_buf_reserve(&p->b_rk_sums, sizeof(int32_t) * KAS_RACK_SUMS * ((size_t)S + 1), p->allocs, "rack row sums")) != KAS_E_OK)
+      return rc;
+    if (NP > 0) KAS_HIP_TRY(hipMemcpy(p->b_rk_rr.p, p->rack.rr.data(), sizeof(int32_t) * NP, hipMemcpyHostToDevice));
+    KAS_HIP_TRY(hipMemcpy(p->b_rk_off.p, p->rack.rack_off.data(), sizeof(int64_t) * ((size_t)S + 1), hipMemcpyHostToDevice));
+    p->rack_ready = 1;
+  }
+  if (rk->rack_off) memcpy(rk->rack_off, p->rack.rack_off.data(), sizeof(int64_t) * ((size_t)S + 1));
+  if (S == 0) return KAS_E_OK;
+  // ordered behind the plan's previous solve and impact pass (and its previous rack pass: the sums are the plan's)
+  if (p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->impact_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
+  KAS_HIP_TRY(hipMemsetAsync(p->b_rk_sums.p, 0, sizeof(int32_t) * KAS_RACK_SUMS * (size_t)S, st));
+  const KasImpactPlan& ip = p->impact;
+  KasRackLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.scen = (const kas_scenario_desc*)p->b_scen.p; a.topics = (const kas_topic_desc*)p->b_topics.p;
+  a.node_id = (const int32_t*)p->b_node_id.p;
+  a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.topic_results = t->topic_results;
+  a.items = (const KasImpactItem*)p->b_imp_items.p;
+  a.rr = (const int32_t*)p->b_rk_rr.p;
+  a.node_base = (const int64_t*)p->b_imp_base.p; a.rack_off = (const int64_t*)p->b_rk_off.p;
+  a.sums = (int32_t*)p->b_rk_sums.p;
+  a.nodes = imp->nodes; a.racks = rk->racks; a.scenarios = rk->scenarios;
+  a.n_items = (int32_t)ip.items.size(); a.n_scenarios = (int32_t)S;
+  a.idmap_entries = p->shape.idmap_entries;
+  a.off_rack = p->rack.off_rack; a.racks_in_lds = p->rack.racks_in_lds;
+  a.lds_bytes = p->rack.lds_bytes; a.reduce_lds_bytes = p->rack.reduce_lds_bytes;
+  a.cells16 = p->cells16;
+  const int e = kas_rack_launch(&a, p->Wc, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("rack pass: ") + hipGetErrorString((hipError_t)e));
+  // a later solve, impact pass or choice waits for this pass as it waits for the impact pass
+  KAS_HIP_TRY(hipEventRecord(p->ev_impact, st));
+  p->impact_stream = st;
+  return KAS_E_OK;
+}
+
+int kas_rack_impact_device(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const int32_t* host_report_rack,
+                           const kas_rack_tables* out, void* hip_stream) {
+  if (!p || !t || !imp || !out) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_rack_impact_device16");
+  return kas_rack_impl(p, t, imp, host_report_rack, out, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
+}
+
+int kas_rack_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const int32_t* host_report_rack,
+                             const kas_rack_tables* out, void* hip_stream) {
+  if (!p || !t16 || !imp || !out) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_rack_impact_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_rack_impl(p, &t, imp, host_report_rack, out, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
 }
 
 // ---- choosing the best scenarios (kernels: kas_choose.hip) --------------------------------------------------------------
@@ -1558,7 +1671,8 @@ struct KasCellPool {
 static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select,
                                  int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr,
                                  const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
-                                 bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr) {
+                                 bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
+                                 const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1584,6 +1698,10 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.moves = hmv; in.ch_rows_optional = rows_optional;
     if (!hch) { in.mv_select = select; in.mv_n_select = n_select; in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0; }
   }
+  if (hrk) {                                                   // kas_solve_host_rack_impact / 16
+    in.racks = true; in.report_rack = report_rack; in.racks_cap = hrk->racks_cap;
+    in.have_rk_racks = hrk->racks != nullptr; in.have_rk_scenarios = hrk->scenarios != nullptr; in.have_rk_off = hrk->rack_off != nullptr;
+  }
   in.lane_order_ok = ctx->lds_lane_order_ok;
   for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
   if (const char* e = getenv("KAS_HOST_RANGES")) in.ranges_override = atoi(e);
@@ -1603,7 +1721,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_END; ++i)
+  for (int i = 0; i < KAS_HB_LAST; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -1704,6 +1822,15 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
       di.scenarios = (kas_scenario_impact*)ctx->hbuf[KAS_HB_IMP_SCEN].p + r.lo;
       const int irc = kas_impact_impl(plans[i], &d, &di, st, &r.bd);
       if (irc != KAS_E_OK) { fail_rc = irc; break; }
+      if (hrk) {                                               // ... and the rack pass right behind it
+        kas_rack_tables dr;
+        dr.racks = (kas_rack_impact*)ctx->hbuf[KAS_HB_RK_RACKS].p + hc.rack.rack_off[(size_t)r.lo];
+        dr.scenarios = (kas_scenario_rack_impact*)ctx->hbuf[KAS_HB_RK_SCEN].p + r.lo;
+        dr.rack_off = nullptr; dr.racks_cap = INT64_MAX;
+        const int32_t* rep = report_rack && r.bd.node_rack ? report_rack + (r.bd.node_rack - batch->node_rack) : nullptr;
+        const int rrc = kas_rack_impl(plans[i], &d, &di, rep, &dr, st, &r.bd);
+        if (rrc != KAS_E_OK) { fail_rc = rrc; break; }
+      }
     }
     if (widened && all_rows && o.hi > o.lo && !narrow(st, o.lo, o.hi - o.lo)) break;
     if (K > 1) hip_ok(hipEventRecord(ctx->hev_done[i], st), "record");
@@ -1824,8 +1951,14 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   }
   if (himp) {
     const int64_t nodes = hch ? 0 : hc.imp_base[(size_t)S];      // (a choice leaves the node table on the device)
-    if (nodes > 0) copy(himp->nodes, ctx->hbuf[KAS_HB_IMP_NODES].p, sizeof(kas_node_impact) * (size_t)nodes, hipMemcpyDeviceToHost, s0, "download node impact");
+    if (nodes > 0 && himp->nodes) copy(himp->nodes, ctx->hbuf[KAS_HB_IMP_NODES].p, sizeof(kas_node_impact) * (size_t)nodes, hipMemcpyDeviceToHost, s0, "download node impact");
     if (S > 0) copy(himp->scenarios, ctx->hbuf[KAS_HB_IMP_SCEN].p, sizeof(kas_scenario_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario impact");
+  }
+  if (hrk) {
+    const int64_t recs = hc.rack.rack_off[(size_t)S];
+    if (recs > 0) copy(hrk->racks, ctx->hbuf[KAS_HB_RK_RACKS].p, sizeof(kas_rack_impact) * (size_t)recs, hipMemcpyDeviceToHost, s0, "download rack impact");
+    if (S > 0) copy(hrk->scenarios, ctx->hbuf[KAS_HB_RK_SCEN].p, sizeof(kas_scenario_rack_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario rack impact");
+    memcpy(hrk->rack_off, hc.rack.rack_off.data(), sizeof(int64_t) * ((size_t)S + 1));
   }
   // the move list: the offsets (they are here already), then exactly the records that were written and the cells they use
   if (hmv && he == hipSuccess) {
@@ -1900,6 +2033,23 @@ int kas_solve_host16_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas
   const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp);
+}
+
+int kas_solve_host_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select, int32_t n_select,
+                               const kas_impact_tables* himp, const int32_t* report_rack, const kas_rack_tables* hrk) {
+  if (!ctx || !batch || !h || !himp || !hrk) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, select, n_select, nullptr, himp, nullptr, nullptr, nullptr, false, nullptr, nullptr, hrk, report_rack);
+}
+
+int kas_solve_host16_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
+                                 const kas_impact_tables* himp, const int32_t* report_rack, const kas_rack_tables* hrk) {
+  if (!ctx || !batch || !h16 || !himp || !hrk) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp, nullptr, nullptr, nullptr, false, nullptr, nullptr,
+                               hrk, report_rack);
 }
 
 int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,

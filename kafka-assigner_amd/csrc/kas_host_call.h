@@ -17,6 +17,7 @@
 #include "kas_choose.h"        // the size and segment tables of kas_solve_host_choose
 #include "kas_moves.h"         // the scenario and segment tables of kas_solve_host_moves / kas_solve_host_choose_moves
 #include "kas_front.h"         // the spec of kas_solve_host_front
+#include "kas_racks.h"         // the rack tables of kas_solve_host_rack_impact
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -203,7 +204,10 @@ enum KasHostBuf {
   // kas_solve_host_front / 16 alone (behind KAS_HB_ALL, for the same reason)
   KAS_HB_FR_CLS = KAS_HB_ALL,                       // the classes the mark kernel leaves for the front rank kernel
   KAS_HB_FR_COUNTS, KAS_HB_FR_COUNTS_PIN,           // n_ok, n_eligible, n_front, 0 and their pinned HOST staging
-  KAS_HB_END
+  KAS_HB_END,                                       // the buffers of the calls above end here
+  // kas_solve_host_rack_impact / 16 alone (behind KAS_HB_END, for the same reason)
+  KAS_HB_RK_RACKS = KAS_HB_END, KAS_HB_RK_SCEN,     // the rack records and the scenario rack records on the device
+  KAS_HB_LAST
 };
 static inline bool kas_host_buf_pinned(int32_t id) {
   return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN ||
@@ -238,6 +242,13 @@ struct KasHostCallIn {
   // place in every decision above; ch_rows_optional as in a choice with moves, and `moves` may be left out)
   const kas_front_spec* front = nullptr;
   bool have_fr_counts = false;
+  // kas_solve_host_rack_impact / 16: the rack pass behind the impact pass (defaults: no rack pass, and every decision above as
+  // it was).  report_rack: the caller's table or NULL (the batch's node_rack); with `racks` the node records may stay on the
+  // device (have_imp_nodes false)
+  bool racks = false;
+  const int32_t* report_rack = nullptr;
+  int64_t racks_cap = 0;                        // kas_rack_tables
+  bool have_rk_racks = false, have_rk_scenarios = false, have_rk_off = false;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -267,7 +278,7 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_END] = {};                // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_LAST] = {};               // what to reserve of each buffer; 0: this call must not touch it
   // kas_solve_host_choose / 16
   KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
   int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
@@ -281,6 +292,8 @@ struct KasHostCall {
   int64_t mv_n = 0;                             // listed scenarios
   int64_t mv_room_moves = 0, mv_room_cells = 0; // what the list can need at most (a choice: the k largest scenarios)
   int64_t mv_moves_cap = 0, mv_cells_cap = 0;   // the capacities on the device: the caller's, no more than the room
+  // kas_solve_host_rack_impact / 16
+  KasRackPlan rack;                             // the report table and rack_off of the whole call
 };
 
 // Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
@@ -345,8 +358,19 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.impact) {
     hc->imp_base.assign((size_t)S + 1, 0);
     for (int64_t s = 0; s < S; ++s) hc->imp_base[(size_t)s + 1] = hc->imp_base[(size_t)s] + (b->scenarios[s].n_nodes > 0 ? b->scenarios[s].n_nodes : 0);
-    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !choose))
+    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !choose && !in.racks))
       return fail(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
+  }
+  // the rack pass: the table (a negative entry, then too many racks), then the capacity, then the arrays
+  if (in.racks) {
+    if (!in.impact) return fail(KAS_E_INVALID_ARG, "kas_rack_tables: the rack pass needs the impact pass");
+    if (in.report_rack && b->node_pool_len <= 0) return fail(KAS_E_INVALID_ARG, "report_rack: a table for a batch without nodes");
+    if ((rc = kas_rack_plan_build(b, in.report_rack ? in.report_rack : b->node_rack, full.n_max, full.idmap_entries, full.need_bsearch,
+                                  in.cells16 ? 1 : 0, -1, &hc->rack, err)) != KAS_E_OK)
+      return rc;
+    if (in.racks_cap < hc->rack.rack_off[(size_t)S]) return fail(KAS_E_INVALID_ARG, "kas_rack_tables: racks_cap below the sum of the scenarios' rack counts");
+    if (!in.have_rk_off || (S > 0 && !in.have_rk_scenarios) || (hc->rack.rack_off[(size_t)S] > 0 && !in.have_rk_racks))
+      return fail(KAS_E_INVALID_ARG, "kas_rack_tables: racks / scenarios / rack_off == NULL");
   }
   // a choice: the spec, then the room for any k scenarios (which ones win is not known before the solve), then the arrays
   if (choose) {
@@ -431,6 +455,10 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     by[KAS_HB_MV_MOVES] = sizeof(kas_move) * (size_t)(hc->mv_moves_cap + 1);
     by[KAS_HB_MV_CELLS] = (size_t)cell * (size_t)(hc->mv_cells_cap + 8);
     by[KAS_HB_MV_SIZES0] = choose && !hc->ch_gather_rows ? sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1) : 0;
+  }
+  if (in.racks) {
+    by[KAS_HB_RK_RACKS] = sizeof(kas_rack_impact) * (size_t)(hc->rack.rack_off[(size_t)S] + 1);
+    by[KAS_HB_RK_SCEN] = sizeof(kas_scenario_rack_impact) * (size_t)(S + 1);
   }
   if (in.front) {
     if (!hc->ch_gather_rows) by[KAS_HB_MV_SIZES0] = sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1);   // (with or without moves)

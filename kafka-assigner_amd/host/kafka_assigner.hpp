@@ -73,6 +73,19 @@ struct RunImpact {
   int64_t departed_replicas = 0, leaders_moved = 0, moved_replicas = 0;
 };
 
+// What a run's reassignment does to each rack (the CLI's --print_rack_impact; kas_rack_impact / kas_scenario_rack_impact of
+// include/kas_abi.h), summed over the run's topics: per-rack counters and per-row sums of separate solves add up (`nodes` is
+// the rack's brokers, not a sum).  The racks are the snapshot's whatever --disable_rack_awareness says.
+struct RackImpact {
+  int64_t nodes = 0, replicas_before = 0, replicas_after = 0, leaders_before = 0, leaders_after = 0, inbound = 0, outbound = 0;
+};
+struct RunRackImpact {
+  std::map<int, std::string> racks;            // in: broker -> its real rack (a broker without one is a rack named by its id)
+  std::vector<std::pair<std::string, RackImpact>> byRack;   // in order of first appearance over the ascending broker ids
+  int64_t colocated_before = 0, colocated_after = 0, rows_colocated_before = 0, rows_colocated_after = 0,
+          single_rack_rows_before = 0, single_rack_rows_after = 0, new_rack_replicas = 0, rows_losing_racks = 0;
+};
+
 // One process-wide device context (a HIP stream on device 0), created on first use.
 inline kas_ctx* deviceContext() {
   static kas_ctx* ctx = nullptr;
@@ -89,7 +102,8 @@ class KafkaAssignmentStrategy {
   static std::map<int, std::vector<int>> getRackAwareAssignment(
       const std::string& topicName, const std::map<int, std::vector<int>>& currentAssignment,
       const std::map<int, std::string>& nodeRackAssignment, const std::set<int>& nodes,
-      const std::set<int>& partitions, int replicationFactor, Context* context, RunImpact* impact = nullptr) {
+      const std::set<int>& partitions, int replicationFactor, Context* context, RunImpact* impact = nullptr,
+      RunRackImpact* rackImpact = nullptr) {
     const int32_t N = (int32_t)nodes.size();
     std::vector<int32_t> node_id(nodes.begin(), nodes.end());           // ascending (KAS:78)
     std::vector<int32_t> node_rack(N);
@@ -167,16 +181,39 @@ class KafkaAssignmentStrategy {
     std::vector<kas_node_impact> node_impact(impact ? (size_t)N + 1 : 0);
     kas_scenario_impact scen_impact{};
     kas_impact_tables it{};
-    it.nodes = node_impact.data(); it.scenarios = &scen_impact;
+    it.nodes = impact ? node_impact.data() : nullptr; it.scenarios = &scen_impact;
+    // with `rackImpact`: ... plus the rack pass against the real racks (kas_solve_host_rack_impact / 16; the node records
+    // stay on the device unless `impact` wants them)
+    std::vector<int32_t> report_rack(rackImpact ? (size_t)N : 0);
+    std::vector<std::string> rack_names;
+    if (rackImpact) {
+      std::map<std::string, int32_t> index;
+      for (int32_t i = 0; i < N; ++i) {
+        auto at = rackImpact->racks.find(node_id[i]);
+        const std::string r = at != rackImpact->racks.end() ? at->second : std::to_string(node_id[i]);
+        auto ins = index.emplace(r, (int32_t)index.size());
+        if (ins.second) rack_names.push_back(r);
+        report_rack[(size_t)i] = ins.first->second;
+      }
+    }
+    std::vector<kas_rack_impact> rack_recs(rack_names.size() + 1);
+    kas_scenario_rack_impact rack_scen{};
+    int64_t rack_off[2] = {0, 0};
+    kas_rack_tables rt{};
+    rt.racks = rack_recs.data(); rt.scenarios = &rack_scen; rt.rack_off = rack_off; rt.racks_cap = (int64_t)rack_names.size();
+    const int32_t* rep = N > 0 ? report_rack.data() : nullptr;
     if (cells16) {
       kas_tables16 t16{};
       t16.cur = cur16.data(); t16.out = out16.data(); t16.aux = t.aux; t16.ctx = t.ctx;
       t16.topic_results = &tr; t16.scenario_results = &sr;
       t16.cur_len = t.cur_len; t16.out_len = t.out_len; t16.aux_len = t.aux_len; t16.ctx_len = t.ctx_len;
-      rc = impact ? kas_solve_host16_impact(deviceContext(), &bd, &t16, nullptr, -1, &it)
-                  : kas_solve_host16(deviceContext(), &bd, &t16, nullptr, -1);
+      rc = rackImpact ? kas_solve_host16_rack_impact(deviceContext(), &bd, &t16, nullptr, -1, &it, rep, &rt)
+           : impact   ? kas_solve_host16_impact(deviceContext(), &bd, &t16, nullptr, -1, &it)
+                      : kas_solve_host16(deviceContext(), &bd, &t16, nullptr, -1);
     } else {
-      rc = impact ? kas_solve_host_impact(deviceContext(), &bd, &t, nullptr, -1, &it) : kas_solve_host(deviceContext(), &bd, &t);
+      rc = rackImpact ? kas_solve_host_rack_impact(deviceContext(), &bd, &t, nullptr, -1, &it, rep, &rt)
+           : impact   ? kas_solve_host_impact(deviceContext(), &bd, &t, nullptr, -1, &it)
+                      : kas_solve_host(deviceContext(), &bd, &t);
     }
     if (rc != KAS_E_OK) throw SolverError(std::string(kas_strerror(rc)) + ": " + kas_last_error());
 
@@ -206,6 +243,24 @@ class KafkaAssignmentStrategy {
       impact->departed_replicas += scen_impact.departed_replicas;
       impact->leaders_moved += scen_impact.leaders_moved;
       impact->moved_replicas += tr.moved_replicas;
+    }
+    if (rackImpact) {
+      for (size_t r = 0; r < rack_names.size(); ++r) {
+        size_t k = 0;
+        while (k < rackImpact->byRack.size() && rackImpact->byRack[k].first != rack_names[r]) ++k;
+        if (k == rackImpact->byRack.size()) rackImpact->byRack.emplace_back(rack_names[r], RackImpact());
+        RackImpact& d = rackImpact->byRack[k].second;
+        const kas_rack_impact& q = rack_recs[r];
+        d.nodes = q.nodes;
+        d.replicas_before += q.replicas_before; d.replicas_after += q.replicas_after;
+        d.leaders_before += q.leaders_before; d.leaders_after += q.leaders_after;
+        d.inbound += q.inbound; d.outbound += q.outbound;
+      }
+      rackImpact->colocated_before += rack_scen.colocated_before; rackImpact->colocated_after += rack_scen.colocated_after;
+      rackImpact->rows_colocated_before += rack_scen.rows_colocated_before; rackImpact->rows_colocated_after += rack_scen.rows_colocated_after;
+      rackImpact->single_rack_rows_before += rack_scen.single_rack_rows_before;
+      rackImpact->single_rack_rows_after += rack_scen.single_rack_rows_after;
+      rackImpact->new_rack_replicas += rack_scen.new_rack_replicas; rackImpact->rows_losing_racks += rack_scen.rows_losing_racks;
     }
     std::map<int, std::vector<int>> result;
     {
@@ -243,7 +298,7 @@ class KafkaTopicAssigner {
   std::map<int, std::vector<int>> generateAssignment(
       const std::string& topic, const std::map<int, std::vector<int>>& currentAssignment,
       const std::set<int>& brokers, const std::map<int, std::string>& rackAssignment,
-      int desiredReplicationFactor, RunImpact* impact = nullptr) {
+      int desiredReplicationFactor, RunImpact* impact = nullptr, RunRackImpact* rackImpact = nullptr) {
     int replicationFactor = desiredReplicationFactor;                   // KTA:49
     std::set<int> partitions;
     for (auto& e : currentAssignment) {                                 // KTA:50-62
@@ -262,7 +317,7 @@ class KafkaTopicAssigner {
       throw IllegalStateException("Topic " + topic + " has a higher replication factor (" +
                                   std::to_string(replicationFactor) + ") than available brokers!");
     return KafkaAssignmentStrategy::getRackAwareAssignment(topic, currentAssignment, rackAssignment, brokers,
-                                                           partitions, replicationFactor, &assignmentContext, impact);
+                                                           partitions, replicationFactor, &assignmentContext, impact, rackImpact);
   }
 
   Context assignmentContext;

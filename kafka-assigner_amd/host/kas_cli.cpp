@@ -155,10 +155,40 @@ static std::string impactJson(const kas::RunImpact& imp) {
   return mjson::dump(doc);
 }
 
+// --print_rack_impact: one JSON document, per real rack its counters (kas_rack_impact) summed over the run's topics, and the run's
+// rack-diversity sums (kas_scenario_rack_impact)
+static std::string rackImpactJson(const kas::RunRackImpact& imp) {
+  auto arr = mjson::make(mjson::Value::Array);
+  for (auto& e : imp.byRack) {
+    auto o = mjson::make(mjson::Value::Object);
+    o->o.emplace_back("rack", mjson::string(e.first));
+    o->o.emplace_back("nodes", mjson::integer(e.second.nodes));
+    o->o.emplace_back("replicas_before", mjson::integer(e.second.replicas_before));
+    o->o.emplace_back("replicas_after", mjson::integer(e.second.replicas_after));
+    o->o.emplace_back("leaders_before", mjson::integer(e.second.leaders_before));
+    o->o.emplace_back("leaders_after", mjson::integer(e.second.leaders_after));
+    o->o.emplace_back("inbound", mjson::integer(e.second.inbound));
+    o->o.emplace_back("outbound", mjson::integer(e.second.outbound));
+    arr->a.push_back(o);
+  }
+  auto doc = mjson::make(mjson::Value::Object);
+  doc->o.emplace_back("racks", arr);
+  doc->o.emplace_back("colocated_before", mjson::integer(imp.colocated_before));
+  doc->o.emplace_back("colocated_after", mjson::integer(imp.colocated_after));
+  doc->o.emplace_back("rows_colocated_before", mjson::integer(imp.rows_colocated_before));
+  doc->o.emplace_back("rows_colocated_after", mjson::integer(imp.rows_colocated_after));
+  doc->o.emplace_back("single_rack_rows_before", mjson::integer(imp.single_rack_rows_before));
+  doc->o.emplace_back("single_rack_rows_after", mjson::integer(imp.single_rack_rows_after));
+  doc->o.emplace_back("new_rack_replicas", mjson::integer(imp.new_rack_replicas));
+  doc->o.emplace_back("rows_losing_racks", mjson::integer(imp.rows_losing_racks));
+  return mjson::dump(doc);
+}
+
 int main(int argc, char** argv) {
   std::string snapshot, mode, brokerIds, brokerHosts, hostsToRemove, topicsArg;
   bool haveIds = false, haveHosts = false, haveTopics = false, disableRack = false, haveZk = false;
   bool printImpact = false;                  // --print_impact (not the reference's): what the reassignment does to each broker
+  bool printRackImpact = false;              // --print_rack_impact (not the reference's): ... and to each rack of the snapshot
   int desiredRf = -1;
   bool bad = false;
   for (int i = 1; i < argc; ++i) {
@@ -175,6 +205,7 @@ int main(int argc, char** argv) {
     else if (a == "--desired_replication_factor") { val(tmp); try { desiredRf = std::stoi(tmp); } catch (...) { bad = true; } }
     else if (a == "--disable_rack_awareness") disableRack = true;
     else if (a == "--print_impact") printImpact = true;
+    else if (a == "--print_rack_impact") printRackImpact = true;
     else bad = true;
   }
   (void)haveZk;
@@ -238,14 +269,18 @@ int main(int argc, char** argv) {
     kas::KafkaTopicAssigner assigner;                                    // ONE Context for the run (KAG:172)
     kas::RunImpact impact;
     for (int b : brokers) impact.brokers[b];                             // (every broker of the run, also without topics)
+    kas::RunRackImpact rackImpact;                                       // (the snapshot's racks, with or without --disable_rack_awareness)
+    for (auto& b : snap.brokers) if (b.has_rack && brokers.count(b.id)) rackImpact.racks[b.id] = b.rack;
     for (auto& topic : topics) {                                         // KAG:173-184
       auto it = snap.assignment.find(topic);
       static const std::map<int, std::vector<int>> none;
       finalAssignment[topic] = assigner.generateAssignment(topic, it != snap.assignment.end() ? it->second : none,
-                                                           brokers, rackAssignment, desiredRf, printImpact ? &impact : nullptr);
+                                                           brokers, rackAssignment, desiredRf, printImpact ? &impact : nullptr,
+                                                           printRackImpact ? &rackImpact : nullptr);
     }
     std::cout << "NEW ASSIGNMENT:\n" << reassignmentJson(topics, finalAssignment) << std::endl;       // KAG:185-186
     if (printImpact) std::cout << "REASSIGNMENT IMPACT:\n" << impactJson(impact) << std::endl;
+    if (printRackImpact) std::cout << "REASSIGNMENT RACK IMPACT:\n" << rackImpactJson(rackImpact) << std::endl;
     return 0;
   } catch (const kas::IllegalStateException& e) {
     fprintf(stderr, "Exception in thread \"main\" java.lang.IllegalStateException: %s\n", e.what());

@@ -32,6 +32,7 @@ SYMBOLS = [
     "kas_moves_device", "kas_moves_device16", "kas_solve_host_moves", "kas_solve_host16_moves", "kas_solve_host_choose_moves",
     "kas_solve_host16_choose_moves",
     "kas_front_rank_device", "kas_front_device", "kas_front_device16", "kas_solve_host_front", "kas_solve_host16_front",
+    "kas_rack_impact_device", "kas_rack_impact_device16", "kas_solve_host_rack_impact", "kas_solve_host16_rack_impact",
 ]
 
 _LIB = None
@@ -126,6 +127,13 @@ def load():
     L.kas_solve_host16_impact.restype = C.c_int
     L.kas_solve_host16_impact.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables),
                                           C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.ImpactTables)]
+    for fn in (L.kas_rack_impact_device, L.kas_rack_impact_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p, C.POINTER(abi.RackTables), C.c_void_p]
+    for fn in (L.kas_solve_host_rack_impact, L.kas_solve_host16_rack_impact):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32,
+                       C.POINTER(abi.ImpactTables), C.c_void_p, C.POINTER(abi.RackTables)]
     L.kas_rank_device.restype = C.c_int
     L.kas_rank_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.ChooseSpec), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]
@@ -267,6 +275,23 @@ class Plan:
         imp = abi.ImpactTables(nodes or None, scenarios or None)
         fn = self._lib.kas_impact_device16 if self.cells16 else self._lib.kas_impact_device
         _check(fn(self._h, C.byref(t), C.byref(imp), C.c_void_p(stream) if stream else None))
+
+    def rack_impact_device(self, cur: int, out: int, topic_results: int, nodes: int, scenarios: int, racks: int, racks_cap: int,
+                           rack_scenarios: int, report_rack=None, aux: int = 0, stream: int = 0) -> np.ndarray:
+        """kas_rack_impact_device / 16: the rack impact of this plan's previous solve and impact pass (whose records are the
+        device arrays `nodes` / `scenarios`) into the device arrays `racks` (kas_rack_impact [racks_cap]) and `rack_scenarios`
+        (kas_scenario_rack_impact [S]).  report_rack: host int32 [node_pool_len] or None (the batch's node_rack).  Raw device
+        pointers (int).  Returns rack_off, int64 [S + 1]."""
+        t = abi.Tables()
+        t.cur = cur or None; t.out = out or None; t.aux = aux or None; t.topic_results = topic_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        rack_off = np.zeros(self._fb.n_scenarios + 1, dtype=np.int64)
+        rep = None if report_rack is None else np.ascontiguousarray(report_rack, dtype=np.int32)
+        rk = abi.RackTables(racks or None, rack_scenarios or None, rack_off.ctypes.data, int(racks_cap))
+        fn = self._lib.kas_rack_impact_device16 if self.cells16 else self._lib.kas_rack_impact_device
+        _check(fn(self._h, C.byref(t), C.byref(imp), None if rep is None else C.c_void_p(rep.ctypes.data), C.byref(rk),
+                  C.c_void_p(stream) if stream else None))
+        return rack_off
 
     def choose_device(self, keys, k: int, out: int, scenario_results: int, nodes: int, scenarios: int, rank: int, chosen: int,
                       row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int, choice_nodes: int, nodes_cap: int,
@@ -453,6 +478,62 @@ def solve_host_impact(fb: FlatBatch, select=None, cells16: bool = False, ctx: Op
     _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
               -1 if sel is None else int(sel.size), C.byref(imp)))
     return ho, nodes, scen
+
+
+def rack_counts(fb: FlatBatch, report_rack=None) -> np.ndarray:
+    """int64 [S]: R_s = 1 + the largest rack index of each scenario's nodes in `report_rack` (None: fb.node_rack)."""
+    table = fb.node_rack if report_rack is None else np.asarray(report_rack)
+    out = np.zeros(fb.n_scenarios, dtype=np.int64)
+    for s in range(fb.n_scenarios):
+        off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
+        out[s] = int(table[off:off + n].max()) + 1 if n > 0 else 0
+    return out
+
+
+@dataclass
+class RackReport:
+    """What kas_solve_host_rack_impact returns beside the solve: scenario s's rack records are racks[rack_off[s]:rack_off[s + 1]]."""
+    racks: np.ndarray                    # RACK_IMPACT_DTYPE
+    scenarios: np.ndarray                # SCENARIO_RACK_IMPACT_DTYPE [S]
+    rack_off: np.ndarray                 # int64 [S + 1]
+    nodes: Optional[np.ndarray] = None   # the node impact records, when they were asked for
+    impact: Optional[np.ndarray] = None  # every scenario's kas_scenario_impact
+
+    def of(self, s: int) -> np.ndarray:
+        return self.racks[int(self.rack_off[s]):int(self.rack_off[s + 1])]
+
+
+def solve_host_rack_impact(fb: FlatBatch, report_rack=None, select=None, cells16: bool = False, nodes: bool = True,
+                           racks_cap: Optional[int] = None, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_rack_impact / 16: solve_host_impact plus the rack pass.  report_rack: int32 [node_pool_len] parallel to
+    fb.node_rack, or None (the batch's own racks).  nodes=False: the node records stay on the device (host_impact->nodes ==
+    NULL).  racks_cap: the capacity handed to the library (default: exactly what the table needs).
+    Returns (HostOutputs, RackReport)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    out_len = None if sel is None else selected_out_len(fb, sel)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)
+        t, ho = host_tables16(fb, cur16, out_len=out_len)
+    else:
+        t, ho = host_tables(fb, out_len=out_len)
+    n_rec, scen = impact_arrays(fb)
+    imp = abi.ImpactTables(n_rec.ctypes.data if (n_rec.size and nodes) else None, scen.ctypes.data if scen.size else None)
+    rep = None if report_rack is None else np.ascontiguousarray(report_rack, dtype=np.int32)
+    S = fb.n_scenarios
+    cap = max(int(rack_counts(fb, rep).sum()), 0) if racks_cap is None else int(racks_cap)
+    racks = np.zeros(max(cap, 1), dtype=abi.RACK_IMPACT_DTYPE)
+    rscen = np.zeros(max(S, 1), dtype=abi.SCENARIO_RACK_IMPACT_DTYPE)
+    rack_off = np.zeros(S + 1, dtype=np.int64)
+    rk = abi.RackTables(racks.ctypes.data, rscen.ctypes.data, rack_off.ctypes.data, cap)
+    fn = L.kas_solve_host16_rack_impact if cells16 else L.kas_solve_host_rack_impact
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
+              -1 if sel is None else int(sel.size), C.byref(imp), None if rep is None else C.c_void_p(rep.ctypes.data), C.byref(rk)))
+    return ho, RackReport(racks=racks[:int(rack_off[S])], scenarios=rscen[:S], rack_off=rack_off, nodes=n_rec if nodes else None, impact=scen)
 
 
 def rank_device(scenario_results: int, scenario_impact: int, n_scenarios: int, keys, k: int, rank: int, chosen: int, n_ok: int,

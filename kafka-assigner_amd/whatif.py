@@ -22,6 +22,12 @@ nothing comes back for the others but their records.
 front() returns the variants that no other variant beats on all the named criteria at once (kas_solve_host_front), optionally
 among those within hard bounds: plan.front(variants, by=("moved_replicas", "replica_spread"), within={"max_inbound": 200}).
 
+racks=True (with impact=True) adds the rack pass (kas_solve_host_rack_impact): results[0].colocated_after — replicas that share a
+rack with another replica of their partition —, .single_rack_rows_after, .new_rack_replicas, ... and results[0].rack_impact() ->
+{rack name: {"nodes": ..., "replicas_after": ..., "inbound": ...}}.  The report is against the REAL racks (brokers / Variant.add; a
+broker without a rack is a rack of its own, named by its id) whatever rack_aware says, so a rack-unaware variant shows what it
+costs.  best() and front() do not rank by these figures yet.
+
 moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for the rows that change instead of every row, compacted
 on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
 results[0].reassignment() -> the Kafka reassignment JSON object of those partitions.  solve(..., moves=...) returns the moves of
@@ -66,6 +72,22 @@ class VariantResult:
     max_replicas_after: Optional[int] = None
     min_leaders_after: Optional[int] = None
     max_leaders_after: Optional[int] = None
+    # racks=True (kas_scenario_rack_impact); None without it
+    colocated_before: Optional[int] = None
+    colocated_after: Optional[int] = None
+    rows_colocated_before: Optional[int] = None
+    rows_colocated_after: Optional[int] = None
+    single_rack_rows_before: Optional[int] = None
+    single_rack_rows_after: Optional[int] = None
+    new_rack_replicas: Optional[int] = None
+    rows_losing_racks: Optional[int] = None
+    n_racks: Optional[int] = None
+    max_rack_inbound: Optional[int] = None
+    max_rack_outbound: Optional[int] = None
+    min_rack_replicas_after: Optional[int] = None
+    max_rack_replicas_after: Optional[int] = None
+    min_rack_leaders_after: Optional[int] = None
+    max_rack_leaders_after: Optional[int] = None
     rank: Optional[int] = None                   # best(): place among the variants that solve (0 = best); None from solve()
     _plan: "WhatIf" = field(repr=False, default=None)
     _index: int = field(repr=False, default=0)
@@ -75,6 +97,8 @@ class VariantResult:
     _packed_at: Optional[int] = field(repr=False, default=None)   # best(): _out holds this variant's rows packed from here
     _moves: Optional[tuple] = field(repr=False, default=None)     # moves=...: (this variant's kas_move records, its list cells)
     _moves_mask: int = field(repr=False, default=0)               # ... and the kinds that were asked for
+    _racks: np.ndarray = field(repr=False, default=None)          # racks=True: this variant's block of kas_rack_impact records
+    _rack_names: Optional[list] = field(repr=False, default=None)  # ... and the name of each rack index
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -119,6 +143,14 @@ class VariantResult:
         if self._nodes is None:
             raise ValueError("no impact records: solve with impact=True")
         return {int(b): {f: int(r[f]) for f in abi.NODE_IMPACT_FIELDS} for b, r in zip(self._node_ids, self._nodes)}
+
+
+    def rack_impact(self) -> Dict[str, Dict[str, int]]:
+        """rack name -> {nodes, replicas_before, replicas_after, leaders_before, leaders_after, inbound, outbound} under this
+        variant (solve(..., impact=True, racks=True)); a broker without a rack is a rack named by its id."""
+        if self._racks is None:
+            raise ValueError("no rack records: solve with impact=True, racks=True")
+        return {name: {f: int(r[f]) for f in abi.RACK_IMPACT_FIELDS} for name, r in zip(self._rack_names, self._racks)}
 
 
 class Front(list):
@@ -189,17 +221,37 @@ class WhatIf:
                          cur=self.cur, aux=np.concatenate(aux) if aux else np.zeros(0, np.int32),
                          ctx=np.zeros(0, np.int32), out_len=out_off)
 
+    def report_racks(self, variants: Sequence[Variant]):
+        """(table, names): the report rack table of flat_batch(variants) — int32, parallel to its node_rack — built from the REAL
+        racks (self.brokers / Variant.add; a None rack -> the broker's id, KAS:82-86) whatever rack_aware says, and per variant
+        the rack name of each rack index (indices in order of first appearance over the variant's ascending broker ids)."""
+        table, names = [], []
+        for v in variants:
+            live = {b: r for b, r in self.brokers.items() if b not in set(v.remove)}
+            live.update(v.add)
+            index: Dict[str, int] = {}
+            for b in sorted(live):
+                r = live[b] if live[b] is not None else str(b)
+                table.append(index.setdefault(r, len(index)))
+            names.append(list(index))
+        return np.asarray(table, dtype=np.int32), names
+
     # ---- solve ---------------------------------------------------------------------------------
-    def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True, moves=None) -> List[VariantResult]:
+    def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True, moves=None,
+              racks: bool = False) -> List[VariantResult]:
         """Solve every variant in one batch (default: the HIP path through the C ABI).
         impact=True: also the per-broker impact of every variant, computed on the GPU (kas_solve_host_impact).
         rows=False: no variant's rows come back (kas_solve_host_select / kas_solve_host_impact with n_select = 0) — the
         records and the impact only; assignment() then raises.
         moves=(kinds): the moves of every variant instead of its rows (kas_solve_host_moves: no rows come back whatever `rows`
-        says, and the call takes neither impact nor solve_fn); moves() and reassignment() then answer."""
+        says, and the call takes neither impact nor solve_fn); moves() and reassignment() then answer.
+        racks=True (needs impact=True): also the rack pass (kas_solve_host_rack_impact) against the real racks (report_racks):
+        colocated_after, single_rack_rows_after, ... and rack_impact() then answer."""
         from . import native
         fb = self.flat_batch(variants)
-        nodes = scen_imp = ml = None
+        nodes = scen_imp = ml = rk = rack_names = None
+        if racks and (not impact or moves is not None):
+            raise ValueError("racks=True is a pass behind the impact pass: solve(..., impact=True, racks=True), without moves")
         if moves is not None:
             if solve_fn is not None or impact:
                 raise ValueError("moves=... takes the library's own host call, without impact (best() has both)")
@@ -208,7 +260,12 @@ class WhatIf:
         elif impact:
             if solve_fn is not None:
                 raise ValueError("impact=True takes the library's own host call (no solve_fn)")
-            ho, nodes, scen_imp = native.solve_host_impact(fb, select=None if rows else [])
+            if racks:
+                table, rack_names = self.report_racks(variants)
+                ho, rk = native.solve_host_rack_impact(fb, report_rack=table, select=None if rows else [])
+                nodes, scen_imp = rk.nodes, rk.impact
+            else:
+                ho, nodes, scen_imp = native.solve_host_impact(fb, select=None if rows else [])
         elif not rows:
             if solve_fn is not None:
                 raise ValueError("rows=False takes the library's own host call (no solve_fn)")
@@ -226,6 +283,9 @@ class WhatIf:
                 extra = {f: int(scen_imp[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
                 off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
                 extra.update(_nodes=nodes[base[s]:base[s + 1]], _node_ids=fb.node_id[off:off + n])
+            if rk is not None:
+                extra.update({f: int(rk.scenarios[f][s]) for f in abi.SCENARIO_RACK_FIELDS})
+                extra.update(_racks=rk.of(s), _rack_names=rack_names[s])
             if ml is not None:
                 extra.update(_moves=ml.of(s), _moves_mask=ml.mask)
             res.append(VariantResult(label=v.label, status=int(sr["status"]),
