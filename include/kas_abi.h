@@ -602,9 +602,8 @@ int kas_solve_host16_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_
  *                       "known".
  *   per row             kB = known cells of C, dB = distinct racks among them; kA = cells of O that name a node, dA =
  *                       distinct racks among them.
- * Ranking or fronting by these figures is not part of this pass: kas_choose_spec and the rank kernels read
- * kas_scenario_result and kas_scenario_impact only.  The scenario record is laid out (sixteen non-negative int32) so that
- * its fields can become criteria. */
+ * Ranking or fronting by these figures is not part of this pass: the scenario record is laid out (sixteen non-negative
+ * int32) so that its fields are criteria of the *_racks entries below (KAS_KEY_RACK_BASE). */
 #define KAS_RACK_LIMIT 4096   /* racks per scenario (the reduce kernel's R_s x 7 int32 histogram lives in the LDS) */
 
 /* One per rack r < R_s; every field a sum over the scenario's nodes with rr == r */
@@ -674,6 +673,85 @@ int kas_solve_host_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, const 
 int kas_solve_host16_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
                                  const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact,
                                  const int32_t* report_rack, const kas_rack_tables* host_racks);
+
+/* ---- ranking and fronting by rack criteria (added under ABI v6: purely additive) --------------------------------------
+ * A *rack criterion* is a non-negative int32 taken from a scenario's kas_scenario_rack_impact.  Key KAS_KEY_RACK_BASE + i,
+ * i = 0..14, is int32 word i of the record; two more are differences of its words.  kas_choose_spec and kas_front_spec take
+ * these keys as they take the others (key[], limit_key[]), in any mix, but only in the *_racks entries below: every other
+ * entry keeps refusing a key >= KAS_KEY_COUNT as an unknown criterion, and keys 10..15 are unknown everywhere. */
+#define KAS_KEY_RACK_BASE                16
+#define KAS_KEY_COLOCATED_BEFORE         16  /* kas_scenario_rack_impact.colocated_before                   */
+#define KAS_KEY_COLOCATED_AFTER          17  /* .colocated_after                                            */
+#define KAS_KEY_ROWS_COLOCATED_BEFORE    18  /* .rows_colocated_before                                      */
+#define KAS_KEY_ROWS_COLOCATED_AFTER     19  /* .rows_colocated_after                                       */
+#define KAS_KEY_SINGLE_RACK_ROWS_BEFORE  20  /* .single_rack_rows_before                                    */
+#define KAS_KEY_SINGLE_RACK_ROWS_AFTER   21  /* .single_rack_rows_after                                     */
+#define KAS_KEY_NEW_RACK_REPLICAS        22  /* .new_rack_replicas                                          */
+#define KAS_KEY_ROWS_LOSING_RACKS        23  /* .rows_losing_racks                                          */
+#define KAS_KEY_N_RACKS                  24  /* .n_racks                                                    */
+#define KAS_KEY_MAX_RACK_INBOUND         25  /* .max_rack_inbound                                           */
+#define KAS_KEY_MAX_RACK_OUTBOUND        26  /* .max_rack_outbound                                          */
+#define KAS_KEY_MIN_RACK_REPLICAS_AFTER  27  /* .min_rack_replicas_after                                    */
+#define KAS_KEY_MAX_RACK_REPLICAS_AFTER  28  /* .max_rack_replicas_after                                    */
+#define KAS_KEY_MIN_RACK_LEADERS_AFTER   29  /* .min_rack_leaders_after                                     */
+#define KAS_KEY_MAX_RACK_LEADERS_AFTER   30  /* .max_rack_leaders_after                                     */
+#define KAS_KEY_RACK_REPLICA_SPREAD      31  /* max_rack_replicas_after - min_rack_replicas_after           */
+#define KAS_KEY_RACK_LEADER_SPREAD       32  /* max_rack_leaders_after - min_rack_leaders_after             */
+#define KAS_KEY_RACK_END                 33
+
+/* Every entry below is its parent entry (the same name without _racks) with one more source of criteria, and orders, ties,
+ * classes, offsets and determinism are the parent's.  A spec that names no rack criterion gives, with or without rack
+ * records, the bytes the parent entry gives.  Refused with KAS_E_INVALID_ARG before any GPU work, in this order: the spec
+ * refusals of the parent entry, with the same texts (a key is known when it is below KAS_KEY_COUNT or in KAS_KEY_RACK_BASE ..
+ * KAS_KEY_RACK_END - 1); "rack criterion without rack records" when a key or a limit key is a rack criterion and the rack
+ * records are NULL; then everything the parent entry refuses, in its order; then, in the host entries, the rack refusals of
+ * kas_solve_host_rack_impact, in its order.  (ctx == NULL and n_scenarios < 0 are refused first, as in the parents.)
+ *
+ * kas_rank_device_racks / kas_front_rank_device_racks: kas_rank_device / kas_front_rank_device plus rack_scenarios[S], a
+ * device array complete on the stream (NULL: no rack criterion may be named).  No plan. */
+int kas_rank_device_racks(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                          const kas_scenario_rack_impact* rack_scenarios, int32_t n_scenarios, const kas_choose_spec* spec,
+                          int32_t* rank, int32_t* chosen, int32_t* n_ok, void* hip_stream);
+int kas_front_rank_device_racks(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                                const kas_scenario_rack_impact* rack_scenarios, int32_t n_scenarios, const kas_front_spec* spec,
+                                int32_t* rank, int32_t* chosen, int32_t* counts, int32_t* scratch, void* hip_stream);
+
+/* kas_choose_device / 16 and kas_front_device / 16 plus rack_scenarios: the DEVICE array of scenario rack records that the
+ * plan's rack pass (kas_rack_impact_device / 16: device_out->scenarios) wrote for the plan's previous solve.  Ordered behind
+ * that pass as behind the impact pass (the rack pass re-records the event a choice waits for); the gather is the parent's. */
+int kas_choose_device_racks(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                            const kas_scenario_rack_impact* rack_scenarios, const kas_choose_spec* spec,
+                            const kas_choice* device_choice, void* hip_stream);
+int kas_choose_device16_racks(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                              const kas_scenario_rack_impact* rack_scenarios, const kas_choose_spec* spec,
+                              const kas_choice* device_choice, void* hip_stream);
+int kas_front_device_racks(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                           const kas_scenario_rack_impact* rack_scenarios, const kas_front_spec* spec,
+                           const kas_choice* device_choice, int32_t* counts, void* hip_stream);
+int kas_front_device16_racks(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                             const kas_scenario_rack_impact* rack_scenarios, const kas_front_spec* spec,
+                             const kas_choice* device_choice, int32_t* counts, void* hip_stream);
+
+/* kas_solve_host_choose_moves / 16 and kas_solve_host_front / 16 plus the rack pass of kas_solve_host_rack_impact on each
+ * scenario range's stream, against report_rack (host memory, or NULL: the batch's node_rack); the ranking or the front waits
+ * for every range's rack pass.  Rows, node blocks and moves come back for the chosen only; ALL rack records, scenario rack
+ * records and rack_off come back in host_racks as from kas_solve_host_rack_impact (no rack blocks are gathered).
+ * host_moves == NULL asks for no moves; host_choice->rows == NULL with rows_cap == 0 gathers no rows.  host_racks == NULL: no
+ * rack pass and no rack records — the parent call, and no rack criterion may be named. */
+int kas_solve_host_choose_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                                const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
+                                const kas_moves* host_moves, const int32_t* report_rack, const kas_rack_tables* host_racks);
+int kas_solve_host16_choose_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                  const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
+                                  const kas_moves* host_moves, const int32_t* report_rack, const kas_rack_tables* host_racks);
+int kas_solve_host_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                               const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
+                               const kas_impact_tables* host_impact, const kas_moves* host_moves, const int32_t* report_rack,
+                               const kas_rack_tables* host_racks);
+int kas_solve_host16_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                 const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
+                                 const kas_impact_tables* host_impact, const kas_moves* host_moves, const int32_t* report_rack,
+                                 const kas_rack_tables* host_racks);
 
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */

@@ -265,6 +265,62 @@ class RackTables(C.Structure):
     _fields_ = [("racks", C.c_void_p), ("scenarios", C.c_void_p), ("rack_off", C.c_void_p), ("racks_cap", C.c_int64)]
 
 
+# rack criteria of the *_racks entries: key KAS_KEY_RACK_BASE + i is int32 word i of kas_scenario_rack_impact, two spreads behind
+KAS_KEY_RACK_BASE = 16
+RACK_KEY_NAMES = SCENARIO_RACK_FIELDS + ("rack_replica_spread", "rack_leader_spread")
+RACK_KEYS = {name: KAS_KEY_RACK_BASE + i for i, name in enumerate(RACK_KEY_NAMES)}
+KAS_KEY_RACK_REPLICA_SPREAD, KAS_KEY_RACK_LEADER_SPREAD = RACK_KEYS["rack_replica_spread"], RACK_KEYS["rack_leader_spread"]
+KAS_KEY_RACK_END = KAS_KEY_RACK_BASE + len(RACK_KEY_NAMES)
+RACK_CHOOSE_ENTRIES = ("kas_rank_device_racks", "kas_front_rank_device_racks", "kas_choose_device_racks", "kas_choose_device16_racks",
+                       "kas_front_device_racks", "kas_front_device16_racks", "kas_solve_host_choose_racks",
+                       "kas_solve_host16_choose_racks", "kas_solve_host_front_racks", "kas_solve_host16_front_racks")
+assert KAS_KEY_RACK_END == 33 and not set(KEYS) & set(RACK_KEYS)
+
+
+def is_rack_key(name) -> bool:
+    """is `name` (a criterion name or a KAS_KEY_* number) a rack criterion"""
+    return name in RACK_KEYS if isinstance(name, str) else KAS_KEY_RACK_BASE <= int(name) < KAS_KEY_RACK_END
+
+
+def rack_key_id(name) -> int:
+    """KAS_KEY_* of a criterion name of either set (KEY_NAMES, RACK_KEY_NAMES), or the number itself; unknown names raise
+    ValueError listing both sets."""
+    if isinstance(name, str):
+        if name in KEYS:
+            return KEYS[name]
+        if name in RACK_KEYS:
+            return RACK_KEYS[name]
+        raise ValueError("unknown criterion %r (one of %s; rack criteria: %s)" % (name, ", ".join(KEY_NAMES), ", ".join(RACK_KEY_NAMES)))
+    return int(name)
+
+
+def rack_choose_spec(keys, k: int) -> "ChooseSpec":
+    """kas_choose_spec for the *_racks entries: names of KEY_NAMES and RACK_KEY_NAMES (or KAS_KEY_* numbers), in any mix."""
+    ids = [rack_key_id(n) for n in ([keys] if isinstance(keys, (str, int)) else list(keys))]
+    spec = ChooseSpec()
+    spec.n_keys = len(ids)
+    for i, v in enumerate(ids[:KAS_CHOOSE_MAX_KEYS]):
+        spec.key[i] = v
+    spec.k = int(k)
+    return spec
+
+
+def rack_front_spec(by, within=None, k: int = 0) -> "FrontSpec":
+    """kas_front_spec for the *_racks entries: front_spec with both name sets, among the criteria and among the bounds."""
+    ids = [rack_key_id(n) for n in ([by] if isinstance(by, (str, int)) else list(by))]
+    pairs = list(within.items()) if isinstance(within, dict) else list(within or ())
+    spec = FrontSpec()
+    spec.n_keys = len(ids)
+    for i, v in enumerate(ids[:KAS_CHOOSE_MAX_KEYS]):
+        spec.key[i] = v
+    spec.n_limits = len(pairs)
+    for i, (name, limit) in enumerate(pairs[:KAS_CHOOSE_MAX_KEYS]):
+        spec.limit_key[i] = rack_key_id(name)
+        spec.limit[i] = int(limit)
+    spec.k = int(k)
+    return spec
+
+
 # the move list (kas_move / kas_moves): a row's flags, the 16-byte record, where a list goes
 KAS_MOVE_REPLICAS, KAS_MOVE_LEADER, KAS_MOVE_ORDER = 1, 2, 4
 MOVE_KINDS = {"replicas": KAS_MOVE_REPLICAS, "leader": KAS_MOVE_LEADER, "order": KAS_MOVE_ORDER}

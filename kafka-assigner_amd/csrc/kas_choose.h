@@ -3,7 +3,8 @@
 //
 // Pure C++ (no HIP calls), so that the same tables are built in the library and in the CPU emulation under tests/emu/.
 //
-// Two kernels behind a solve and its impact pass:
+// Two kernels behind a solve and its impact pass (the rank kernel in two instances: the second also reads the scenario rack
+// records of a rack pass, for the rack criteria of KAS_KEY_RACK_BASE):
 //   rank    one lane per scenario, KAS_CHOOSE_BLOCK lanes a workgroup.  Every workgroup streams all S keys through the LDS in
 //           tiles of KAS_CHOOSE_TILE entries, built from the 64 bytes of records per scenario; a lane counts the entries whose
 //           key is smaller than its own — its rank — and in the same loop sums their packed cells and node counts: the offsets
@@ -119,15 +120,28 @@ static inline int64_t kas_choose_chunks(const KasChoosePlan& cp, int32_t dst_cel
   return kas_choose_chunks_of(cp.max_cells * dst_cell) + kas_choose_chunks_of((int64_t)cp.max_nodes * (int64_t)sizeof(kas_node_impact));
 }
 
+// Rack criteria (KAS_KEY_RACK_BASE .. KAS_KEY_RACK_END - 1) are known to the *_racks entries only: `racks` widens the key set.
+static inline bool kas_key_is_rack(int32_t key) { return key >= KAS_KEY_RACK_BASE && key < KAS_KEY_RACK_END; }
+static inline bool kas_key_known(int32_t key, bool racks) { return (key >= 0 && key < KAS_KEY_COUNT) || (racks && kas_key_is_rack(key)); }
+
 // "" or what is wrong with a spec for S scenarios (the text of the KAS_E_INVALID_ARG)
-static inline const char* kas_choose_spec_error(const kas_choose_spec* spec, int64_t S) {
+static inline const char* kas_choose_spec_error_keys(const kas_choose_spec* spec, int64_t S, bool racks) {
   if (!spec) return "kas_choose_spec == NULL";
   if (spec->n_keys < 1 || spec->n_keys > KAS_CHOOSE_MAX_KEYS) return "kas_choose_spec: n_keys outside 1..4";
   for (int32_t i = 0; i < spec->n_keys; ++i)
-    if (spec->key[i] < 0 || spec->key[i] >= KAS_KEY_COUNT) return "kas_choose_spec: unknown criterion";
+    if (!kas_key_known(spec->key[i], racks)) return "kas_choose_spec: unknown criterion";
   if (spec->k < 0 || spec->k > S) return "kas_choose_spec: k outside 0..n_scenarios";
   return "";
 }
+static inline const char* kas_choose_spec_error(const kas_choose_spec* spec, int64_t S) { return kas_choose_spec_error_keys(spec, S, false); }
+
+// does a (valid) spec name a rack criterion: what the *_racks entries need rack records for
+static inline bool kas_choose_spec_uses_racks(const kas_choose_spec* spec) {
+  for (int32_t i = 0; i < spec->n_keys; ++i)
+    if (kas_key_is_rack(spec->key[i])) return true;
+  return false;
+}
+#define KAS_NO_RACK_RECORDS "rack criterion without rack records"   // the refusal of a rack criterion with NULL records
 
 // the spec's words of the launch arguments
 static inline void kas_choose_fill_spec(KasChooseLaunch* a, const kas_choose_spec* spec, int32_t S) {
@@ -135,6 +149,14 @@ static inline void kas_choose_fill_spec(KasChooseLaunch* a, const kas_choose_spe
   for (int i = 0; i < KAS_CHOOSE_MAX_KEYS; ++i) a->key[i] = i < spec->n_keys ? spec->key[i] : 0;
 }
 
-// kas_choose.hip.  Both return a hipError_t (0 = hipSuccess).  kas_gather_launch needs a.chunks * a.k below 2^31.
+// Kernel arguments of the rank kernel's instance that also reads scenario rack records (a struct of its own: the arguments of
+// the instances above stay as they are).  srk: [S], never NULL here.
+struct KasRackChooseLaunch {
+  KasChooseLaunch c;
+  const kas_scenario_rack_impact* srk;
+};
+
+// kas_choose.hip.  All return a hipError_t (0 = hipSuccess).  kas_gather_launch needs a.chunks * a.k below 2^31.
 int kas_rank_launch(const KasChooseLaunch* a, void* hip_stream);
 int kas_gather_launch(const KasChooseLaunch* a, void* hip_stream);
+int kas_rank_racks_launch(const KasRackChooseLaunch* a, void* hip_stream);

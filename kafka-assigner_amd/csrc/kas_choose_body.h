@@ -37,6 +37,23 @@ KAS_DEV int32_t criterion(const kas_scenario_result& r, const kas_scenario_impac
   }
 }
 
+// Where a scenario's criteria come from, chosen at compile time.  Records: the scenario record and the impact record alone (the
+// instances that were always there).  RackRecords: also the scenario rack records — a rack criterion is int32 word key -
+// KAS_KEY_RACK_BASE of the 64-byte record, loaded alone (two words for a spread); the key is uniform, so is the branch.
+struct Records {};
+struct RackRecords { const kas_scenario_rack_impact* srk; };
+static_assert(sizeof(kas_scenario_rack_impact) == 64 && KAS_KEY_RACK_END - KAS_KEY_RACK_BASE == 17, "fifteen words and two spreads");
+KAS_DEV int32_t criterion_of(const Records&, const kas_scenario_result& r, const kas_scenario_impact& m, int32_t, int32_t key) {
+  return criterion(r, m, key);
+}
+KAS_DEV int32_t criterion_of(const RackRecords& x, const kas_scenario_result& r, const kas_scenario_impact& m, int32_t s, int32_t key) {
+  if (key < KAS_KEY_RACK_BASE) return criterion(r, m, key);
+  const int32_t* w = reinterpret_cast<const int32_t*>(x.srk + s);
+  if (key == KAS_KEY_RACK_REPLICA_SPREAD) return w[KAS_KEY_MAX_RACK_REPLICAS_AFTER - KAS_KEY_RACK_BASE] - w[KAS_KEY_MIN_RACK_REPLICAS_AFTER - KAS_KEY_RACK_BASE];
+  if (key == KAS_KEY_RACK_LEADER_SPREAD) return w[KAS_KEY_MAX_RACK_LEADERS_AFTER - KAS_KEY_RACK_BASE] - w[KAS_KEY_MIN_RACK_LEADERS_AFTER - KAS_KEY_RACK_BASE];
+  return w[key - KAS_KEY_RACK_BASE];
+}
+
 // Who takes part in a ranking, and what the ranking leaves for those who do not.  ByStatus: the scenarios that solved
 // (kas_choose_spec); kas_front_body.h has the other one, the members of a front.
 struct ByStatus {};
@@ -44,8 +61,8 @@ KAS_DEV int32_t takes_part(const ByStatus&, const KasChooseLaunch&, int32_t, con
 KAS_DEV int32_t outside(const ByStatus&, const KasChooseLaunch&, int32_t) { return -1; }
 KAS_DEV void count(const ByStatus&, const KasChooseLaunch& a, int32_t n) { a.n_ok[0] = n; }
 
-template <class Part>
-KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s, const Part& part) {
+template <class Part, class Src>
+KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s, const Part& part, const Src& src) {
   const kas_scenario_result r = a.sr[s];
   const kas_scenario_impact m = a.si[s];
   Entry e;
@@ -53,7 +70,7 @@ KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s, const Part& part) {
   uint32_t c[KAS_CHOOSE_MAX_KEYS];
 #pragma unroll
   for (int i = 0; i < KAS_CHOOSE_MAX_KEYS; ++i)
-    c[i] = i < a.n_keys ? (uint32_t)criterion(r, m, a.key[i]) ^ 0x80000000u : 0u;
+    c[i] = i < a.n_keys ? (uint32_t)criterion_of(src, r, m, s, a.key[i]) ^ 0x80000000u : 0u;
   e.hi = ((uint64_t)c[0] << 32) | c[1];
   e.lo = ((uint64_t)c[2] << 32) | c[3];
   e.cells = e.ok && a.sizes ? a.sizes[s].cells : 0;
@@ -63,20 +80,20 @@ KAS_DEV Entry entry_of(const KasChooseLaunch& a, int32_t s, const Part& part) {
 
 // Workgroup `block` of the rank kernel.  tile: KAS_CHOOSE_TILE entries of LDS.  The grid covers S + 1 lanes: lane g < S is
 // scenario g, and lane g <= k is also slot g of chosen / row_off / node_off, which it writes when no scenario has that rank.
-template <class Part = ByStatus>
-KAS_DEV void rank_block(const KasChooseLaunch& a, int32_t block, Entry* tile, const Part& part = Part()) {
+template <class Part = ByStatus, class Src = Records>
+KAS_DEV void rank_block(const KasChooseLaunch& a, int32_t block, Entry* tile, const Part& part = Part(), const Src& src = Src()) {
   const int32_t tid = kasw::tid();
   const int32_t g = block * KAS_CHOOSE_BLOCK + tid;
   const bool live = g < a.S;
   Entry mine;
   mine.hi = 0; mine.lo = 0; mine.cells = 0; mine.nodes = 0; mine.ok = 0;
-  if (live) mine = entry_of(a, g, part);
+  if (live) mine = entry_of(a, g, part, src);
   int32_t smaller = 0, n_ok = 0;
   int64_t cells = 0, nodes = 0, all_cells = 0, all_nodes = 0;
   for (int32_t base = 0; base < a.S; base += KAS_CHOOSE_TILE) {
     const int32_t n = a.S - base < KAS_CHOOSE_TILE ? a.S - base : KAS_CHOOSE_TILE;
     kasw::sync();                                               // (every lane has left the tile before)
-    for (int32_t i = tid; i < n; i += KAS_CHOOSE_BLOCK) tile[i] = entry_of(a, base + i, part);
+    for (int32_t i = tid; i < n; i += KAS_CHOOSE_BLOCK) tile[i] = entry_of(a, base + i, part, src);
     kasw::sync();
     for (int32_t i = 0; i < n; ++i) {                           // (every lane reads the same entry: an LDS broadcast)
       const Entry e = tile[i];

@@ -25,19 +25,30 @@ struct KasFrontLaunch {
   int32_t* counts;                      // [4] n_ok, n_eligible (mark), n_front, 0 (front rank)
 };
 
-// "" or what is wrong with a spec for S scenarios (the text of the KAS_E_INVALID_ARG)
-static inline const char* kas_front_spec_error(const kas_front_spec* spec, int64_t S) {
+// "" or what is wrong with a spec for S scenarios (the text of the KAS_E_INVALID_ARG); racks: rack criteria are known (the
+// *_racks entries)
+static inline const char* kas_front_spec_error_keys(const kas_front_spec* spec, int64_t S, bool racks) {
   if (!spec) return "kas_front_spec == NULL";
   if (spec->n_keys < 1 || spec->n_keys > KAS_CHOOSE_MAX_KEYS) return "kas_front_spec: n_keys outside 1..4";
   for (int32_t i = 0; i < spec->n_keys; ++i)
-    if (spec->key[i] < 0 || spec->key[i] >= KAS_KEY_COUNT) return "kas_front_spec: unknown criterion";
+    if (!kas_key_known(spec->key[i], racks)) return "kas_front_spec: unknown criterion";
   if (spec->n_limits < 0 || spec->n_limits > KAS_CHOOSE_MAX_KEYS) return "kas_front_spec: n_limits outside 0..4";
   for (int32_t i = 0; i < spec->n_limits; ++i)
-    if (spec->limit_key[i] < 0 || spec->limit_key[i] >= KAS_KEY_COUNT) return "kas_front_spec: unknown limit criterion";
+    if (!kas_key_known(spec->limit_key[i], racks)) return "kas_front_spec: unknown limit criterion";
   for (int32_t i = 0; i < spec->n_limits; ++i)
     if (spec->limit[i] < 0) return "kas_front_spec: negative limit";
   if (spec->k < 0 || spec->k > S) return "kas_front_spec: k outside 0..n_scenarios";
   return "";
+}
+static inline const char* kas_front_spec_error(const kas_front_spec* spec, int64_t S) { return kas_front_spec_error_keys(spec, S, false); }
+
+// does a (valid) spec name a rack criterion, among its keys or its bounds
+static inline bool kas_front_spec_uses_racks(const kas_front_spec* spec) {
+  for (int32_t i = 0; i < spec->n_keys; ++i)
+    if (kas_key_is_rack(spec->key[i])) return true;
+  for (int32_t i = 0; i < spec->n_limits; ++i)
+    if (kas_key_is_rack(spec->limit_key[i])) return true;
+  return false;
 }
 
 // the part of a (valid) front spec that orders the members and sizes the outputs: what every choose decision reads
@@ -65,6 +76,14 @@ static inline int64_t kas_front_mark_grid(int32_t S) {
   return g < 1 ? 1 : g;
 }
 
-// kas_choose.hip.  Both return a hipError_t (0 = hipSuccess).
+// Kernel arguments of the two kernels' instances that also read scenario rack records (as KasRackChooseLaunch).
+struct KasRackFrontLaunch {
+  KasFrontLaunch f;
+  const kas_scenario_rack_impact* srk;  // [S], never NULL here
+};
+
+// kas_choose.hip.  All return a hipError_t (0 = hipSuccess).
 int kas_front_mark_launch(const KasFrontLaunch* a, void* hip_stream);
 int kas_front_rank_launch(const KasFrontLaunch* a, void* hip_stream);
+int kas_front_mark_racks_launch(const KasRackFrontLaunch* a, void* hip_stream);
+int kas_front_rank_racks_launch(const KasRackFrontLaunch* a, void* hip_stream);

@@ -26,37 +26,40 @@ struct Entry {
 };
 static_assert(sizeof(Entry) == 32, "an LDS tile entry is two 16-byte reads");
 
-KAS_DEV Entry entry_of(const KasFrontLaunch& a, int32_t s) {
+template <class Src>
+KAS_DEV Entry entry_of(const KasFrontLaunch& a, int32_t s, const Src& src) {
   const kas_scenario_result r = a.c.sr[s];
   const kas_scenario_impact m = a.c.si[s];
   Entry e;
 #pragma unroll
   for (int i = 0; i < KAS_CHOOSE_MAX_KEYS; ++i)
-    e.c[i] = i < a.c.n_keys ? (uint32_t)kasc::criterion(r, m, a.c.key[i]) ^ 0x80000000u : 0u;
+    e.c[i] = i < a.c.n_keys ? (uint32_t)kasc::criterion_of(src, r, m, s, a.c.key[i]) ^ 0x80000000u : 0u;
   e.ok = r.status == KAS_OK ? 1 : 0;
   int32_t within = 1;
 #pragma unroll
   for (int i = 0; i < KAS_CHOOSE_MAX_KEYS; ++i)
-    if (i < a.n_limits && kasc::criterion(r, m, a.limit_key[i]) > a.limit[i]) within = 0;
+    if (i < a.n_limits && kasc::criterion_of(src, r, m, s, a.limit_key[i]) > a.limit[i]) within = 0;
   e.eligible = e.ok & within;
   e.reserved[0] = 0; e.reserved[1] = 0;
   return e;
 }
 
-// Workgroup `block` of the mark kernel.  tile: KAS_CHOOSE_TILE entries of LDS.  Lane g < S is scenario g.
-KAS_DEV void mark_block(const KasFrontLaunch& a, int32_t block, Entry* tile) {
+// Workgroup `block` of the mark kernel.  tile: KAS_CHOOSE_TILE entries of LDS.  Lane g < S is scenario g.  Src: where the criteria
+// come from (kas_choose_body.h).
+template <class Src = kasc::Records>
+KAS_DEV void mark_block(const KasFrontLaunch& a, int32_t block, Entry* tile, const Src& src = Src()) {
   const int32_t S = a.c.S;
   const int32_t tid = kasw::tid();
   const int32_t g = block * KAS_CHOOSE_BLOCK + tid;
   const bool live = g < S;
   Entry mine;
   mine.c[0] = 0; mine.c[1] = 0; mine.c[2] = 0; mine.c[3] = 0; mine.ok = 0; mine.eligible = 0;
-  if (live) mine = entry_of(a, g);
+  if (live) mine = entry_of(a, g, src);
   int32_t beaten = 0, n_ok = 0, n_eligible = 0;
   for (int32_t base = 0; base < S; base += KAS_CHOOSE_TILE) {
     const int32_t n = S - base < KAS_CHOOSE_TILE ? S - base : KAS_CHOOSE_TILE;
     kasw::sync();                                               // (every lane has left the tile before)
-    for (int32_t i = tid; i < n; i += KAS_CHOOSE_BLOCK) tile[i] = entry_of(a, base + i);
+    for (int32_t i = tid; i < n; i += KAS_CHOOSE_BLOCK) tile[i] = entry_of(a, base + i, src);
     kasw::sync();
 #pragma unroll KAS_FRONT_MARK_UNROLL
     for (int32_t i = 0; i < n; ++i) {                           // (every lane reads the same entry: an LDS broadcast)
@@ -83,8 +86,9 @@ KAS_DEV int32_t outside(const ByClass& p, const KasChooseLaunch&, int32_t s) { r
 KAS_DEV void count(const ByClass& p, const KasChooseLaunch&, int32_t n) { p.counts[2] = n; p.counts[3] = 0; }
 
 // Workgroup `block` of the front rank kernel: kasc::rank_block's grid and tile.
-KAS_DEV void rank_block(const KasFrontLaunch& a, int32_t block, kasc::Entry* tile) {
-  kasc::rank_block(a.c, block, tile, ByClass{a.cls, a.counts});
+template <class Src = kasc::Records>
+KAS_DEV void rank_block(const KasFrontLaunch& a, int32_t block, kasc::Entry* tile, const Src& src = Src()) {
+  kasc::rank_block(a.c, block, tile, ByClass{a.cls, a.counts}, src);
 }
 
 }  // namespace kasf

@@ -1223,6 +1223,57 @@ int kas_front_rank_device(kas_ctx* ctx, const kas_scenario_result* scenario_resu
   return KAS_E_OK;
 }
 
+// kas_rank_device / kas_front_rank_device with the scenario rack records as a third source of criteria.  A spec without a rack
+// criterion goes to the parent entry (its kernel instances, its bytes).
+int kas_rank_device_racks(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                          const kas_scenario_rack_impact* rack_scenarios, int32_t n_scenarios, const kas_choose_spec* spec, int32_t* rank,
+                          int32_t* chosen, int32_t* n_ok, void* hip_stream) {
+  if (!ctx) return set_error(KAS_E_INVALID_ARG, "ctx == NULL");
+  if (n_scenarios < 0) return set_error(KAS_E_INVALID_ARG, "n_scenarios < 0");
+  const char* bad = kas_choose_spec_error_keys(spec, n_scenarios, true);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (!kas_choose_spec_uses_racks(spec))
+    return kas_rank_device(ctx, scenario_results, scenario_impact, n_scenarios, spec, rank, chosen, n_ok, hip_stream);
+  if (!rack_scenarios) return set_error(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+  if (!n_ok || (n_scenarios > 0 && (!scenario_results || !scenario_impact || !rank)) || (spec->k > 0 && !chosen))
+    return set_error(KAS_E_INVALID_ARG, "kas_rank_device: an array the call reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(ctx->device));
+  KasRackChooseLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.c.sr = scenario_results; a.c.si = scenario_impact; a.srk = rack_scenarios;
+  kas_choose_fill_spec(&a.c, spec, n_scenarios);
+  a.c.rank = rank; a.c.chosen = chosen; a.c.n_ok = n_ok;
+  const int e = kas_rank_racks_launch(&a, hip_stream ? hip_stream : (void*)ctx->stream);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("kas_rank_racks_kernel: ") + hipGetErrorString((hipError_t)e));
+  return KAS_E_OK;
+}
+
+int kas_front_rank_device_racks(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                                const kas_scenario_rack_impact* rack_scenarios, int32_t n_scenarios, const kas_front_spec* spec,
+                                int32_t* rank, int32_t* chosen, int32_t* counts, int32_t* scratch, void* hip_stream) {
+  if (!ctx) return set_error(KAS_E_INVALID_ARG, "ctx == NULL");
+  if (n_scenarios < 0) return set_error(KAS_E_INVALID_ARG, "n_scenarios < 0");
+  const char* bad = kas_front_spec_error_keys(spec, n_scenarios, true);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (!kas_front_spec_uses_racks(spec))
+    return kas_front_rank_device(ctx, scenario_results, scenario_impact, n_scenarios, spec, rank, chosen, counts, scratch, hip_stream);
+  if (!rack_scenarios) return set_error(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+  if (!counts || (n_scenarios > 0 && (!scenario_results || !scenario_impact || !rank || !scratch)) || (spec->k > 0 && !chosen))
+    return set_error(KAS_E_INVALID_ARG, "kas_front_rank_device: an array the call reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(ctx->device));
+  KasRackFrontLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.f.c.sr = scenario_results; a.f.c.si = scenario_impact; a.srk = rack_scenarios;
+  kas_front_fill_spec(&a.f, spec, n_scenarios);
+  a.f.c.rank = rank; a.f.c.chosen = chosen; a.f.c.n_ok = counts;   // (n_ok is counts[0])
+  a.f.cls = scratch; a.f.counts = counts;
+  void* st = hip_stream ? hip_stream : (void*)ctx->stream;
+  int e = kas_front_mark_racks_launch(&a, st);
+  if (e == 0) e = kas_front_rank_racks_launch(&a, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("front kernels: ") + hipGetErrorString((hipError_t)e));
+  return KAS_E_OK;
+}
+
 // The plan's size and segment tables (built on the host with the plan) on the device: allocated and uploaded at the plan's first
 // choice — blocking copies, once — and kept until the plan is rebuilt.
 static int kas_choose_prepare(kas_plan* p) {
@@ -1237,19 +1288,23 @@ static int kas_choose_prepare(kas_plan* p) {
   return KAS_E_OK;
 }
 
-// front: the Pareto front in place of the ranking (kas_front_device / 16; `spec` is then not read, `counts` is the call's)
+// front: the Pareto front in place of the ranking (kas_front_device / 16; `spec` is then not read, `counts` is the call's).
+// rack_keys: the spec may name rack criteria (the *_racks entries), read from srk, the scenario rack records of the plan's rack pass.
 static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_choose_spec* spec,
-                           const kas_choice* ch, hipStream_t st, const kas_front_spec* front = nullptr, int32_t* counts = nullptr) {
+                           const kas_choice* ch, hipStream_t st, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
+                           bool rack_keys = false, const kas_scenario_rack_impact* srk = nullptr) {
   const int32_t S = p->n_scenarios;
   kas_choose_spec front_cs;
   if (front) {
-    const char* bad = kas_front_spec_error(front, S);
+    const char* bad = kas_front_spec_error_keys(front, S, rack_keys);
     if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
     front_cs = kas_front_choose_spec(front);
     spec = &front_cs;
   }
-  const char* bad = kas_choose_spec_error(spec, S);
+  const char* bad = kas_choose_spec_error_keys(spec, S, rack_keys);
   if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  const bool by_racks = rack_keys && (front ? kas_front_spec_uses_racks(front) : kas_choose_spec_uses_racks(spec));
+  if (by_racks && !srk) return set_error(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
   const KasChoosePlan& cp = p->choose;
   int64_t rows_need = 0, nodes_need = 0;
   kas_choose_k_largest(cp, spec->k, &rows_need, &nodes_need);
@@ -1293,10 +1348,12 @@ static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_ta
     kas_front_fill_spec(&f, front, S);
     f.c = a;
     f.cls = (int32_t*)p->b_fr_cls.p; f.counts = counts;
-    e = kas_front_mark_launch(&f, st);
-    if (e == 0) e = kas_front_rank_launch(&f, st);
+    const KasRackFrontLaunch fr{f, srk};
+    e = by_racks ? kas_front_mark_racks_launch(&fr, st) : kas_front_mark_launch(&f, st);
+    if (e == 0) e = by_racks ? kas_front_rank_racks_launch(&fr, st) : kas_front_rank_launch(&f, st);
   } else {
-    e = kas_rank_launch(&a, st);
+    const KasRackChooseLaunch ar{a, srk};
+    e = by_racks ? kas_rank_racks_launch(&ar, st) : kas_rank_launch(&a, st);
   }
   if (e == 0) e = kas_gather_launch(&a, st);
   if (e != 0) return set_error(KAS_E_HIP, std::string("choose kernels: ") + hipGetErrorString((hipError_t)e));
@@ -1337,6 +1394,39 @@ int kas_front_device16(kas_plan* p, const kas_tables16* t16, const kas_impact_ta
   if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_choose_impl(p, &t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts);
+}
+
+// the same four with the scenario rack records of the plan's rack pass (ordered behind it through the plan's impact event)
+int kas_choose_device_racks(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                            const kas_choose_spec* spec, const kas_choice* ch, void* hip_stream) {
+  if (!p || !t || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_choose_device16");
+  return kas_choose_impl(p, t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr, nullptr, true, srk);
+}
+
+int kas_choose_device16_racks(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                              const kas_choose_spec* spec, const kas_choice* ch, void* hip_stream) {
+  if (!p || !t16 || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_choose_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_choose_impl(p, &t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr, nullptr, true, srk);
+}
+
+int kas_front_device_racks(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                           const kas_front_spec* spec, const kas_choice* ch, int32_t* counts, void* hip_stream) {
+  if (!p || !t || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_front_device16");
+  if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
+  return kas_choose_impl(p, t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts, true, srk);
+}
+
+int kas_front_device16_racks(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                             const kas_front_spec* spec, const kas_choice* ch, int32_t* counts, void* hip_stream) {
+  if (!p || !t16 || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_front_device16 needs a plan of kas_plan_create16");
+  if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_choose_impl(p, &t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts, true, srk);
 }
 
 // ---- the move list (kernels: kas_moves.hip) ----------------------------------------------------------------------------
@@ -1672,7 +1762,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
                                  int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr,
                                  const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
                                  bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
-                                 const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr) {
+                                 const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr, bool rack_keys = false) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1698,7 +1788,9 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.moves = hmv; in.ch_rows_optional = rows_optional;
     if (!hch) { in.mv_select = select; in.mv_n_select = n_select; in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0; }
   }
-  if (hrk) {                                                   // kas_solve_host_rack_impact / 16
+  in.rack_keys = rack_keys;                                    // kas_solve_host_choose_racks / kas_solve_host_front_racks / 16
+  if (rack_keys) in.ch_rows_optional = rows_optional;          // (with moves or without)
+  if (hrk) {                                                   // kas_solve_host_rack_impact / 16, and those
     in.racks = true; in.report_rack = report_rack; in.racks_cap = hrk->racks_cap;
     in.have_rk_racks = hrk->racks != nullptr; in.have_rk_scenarios = hrk->scenarios != nullptr; in.have_rk_off = hrk->rack_off != nullptr;
   }
@@ -1837,7 +1929,8 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (i >= lag) download(i - lag);
   }
   for (int i = K - lag < 0 ? 0 : K - lag; i < K && he == hipSuccess && fail_rc == KAS_E_OK; ++i) download(i);
-  // a choice: rank and gather on s0 behind every range (one range: s0 solved it; several: their done events), then its header
+  // a choice: rank and gather on s0 behind every range (one range: s0 solved it; several: their done events, which are recorded
+  // behind a range's rack pass: a ranking by rack criteria sees every range's rack records), then its header
   const int64_t ch_k = hch ? spec->k : 0;
   char* const d_head = (char*)ctx->hbuf[KAS_HB_CH_HEAD].p;
   char* const p_head = (char*)ctx->hbuf[KAS_HB_CH_HEAD_PIN].p;
@@ -1867,16 +1960,21 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     a.chunks = (int32_t)hc.ch_chunks;
     if (he == hipSuccess) {
       int e;
+      // (the planner refused a rack criterion without a rack pass: the records are this call's)
+      const kas_scenario_rack_impact* srk = (const kas_scenario_rack_impact*)ctx->hbuf[KAS_HB_RK_SCEN].p;
+      const bool by_racks = rack_keys && hrk && (front ? kas_front_spec_uses_racks(front) : kas_choose_spec_uses_racks(spec));
       if (front) {                                              // mark and front rank where the rank kernel runs
         KasFrontLaunch f;
         memset(&f, 0, sizeof(f));
         kas_front_fill_spec(&f, front, (int32_t)S);
         f.c = a;
         f.cls = (int32_t*)ctx->hbuf[KAS_HB_FR_CLS].p; f.counts = (int32_t*)ctx->hbuf[KAS_HB_FR_COUNTS].p;
-        e = kas_front_mark_launch(&f, s0);
-        if (e == 0) e = kas_front_rank_launch(&f, s0);
+        const KasRackFrontLaunch fr{f, srk};
+        e = by_racks ? kas_front_mark_racks_launch(&fr, s0) : kas_front_mark_launch(&f, s0);
+        if (e == 0) e = by_racks ? kas_front_rank_racks_launch(&fr, s0) : kas_front_rank_launch(&f, s0);
       } else {
-        e = kas_rank_launch(&a, s0);
+        const KasRackChooseLaunch ar{a, srk};
+        e = by_racks ? kas_rank_racks_launch(&ar, s0) : kas_rank_launch(&a, s0);
       }
       if (!hc.ch_gather_rows) a.sizes = (const KasChooseSize*)ctx->hbuf[KAS_HB_MV_SIZES0].p;
       if (e == 0) e = kas_gather_launch(&a, s0);
@@ -2114,6 +2212,42 @@ int kas_solve_host16_front(kas_ctx* ctx, const kas_batch_desc* batch, const kas_
   const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, nullptr, hch, hmv, true, spec, counts);
+}
+
+// kas_solve_host_choose_moves / kas_solve_host_front / 16 plus the rack pass; the spec may name rack criteria
+int kas_solve_host_choose_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,
+                                const kas_impact_tables* himp, const kas_moves* hmv, const int32_t* report_rack, const kas_rack_tables* hrk) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, spec, hch, hmv, true, nullptr, nullptr, hrk, report_rack, true);
+}
+
+int kas_solve_host16_choose_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_choose_spec* spec,
+                                  const kas_choice* hch, const kas_impact_tables* himp, const kas_moves* hmv, const int32_t* report_rack,
+                                  const kas_rack_tables* hrk) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, spec, hch, hmv, true, nullptr, nullptr, hrk, report_rack, true);
+}
+
+int kas_solve_host_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_front_spec* spec, const kas_choice* hch,
+                               int32_t* counts, const kas_impact_tables* himp, const kas_moves* hmv, const int32_t* report_rack,
+                               const kas_rack_tables* hrk) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, nullptr, hch, hmv, true, spec, counts, hrk, report_rack, true);
+}
+
+int kas_solve_host16_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_front_spec* spec,
+                                 const kas_choice* hch, int32_t* counts, const kas_impact_tables* himp, const kas_moves* hmv,
+                                 const int32_t* report_rack, const kas_rack_tables* hrk) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, nullptr, hch, hmv, true, spec, counts, hrk, report_rack, true);
 }
 
 int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_desc* batch, const kas_tables* h) {

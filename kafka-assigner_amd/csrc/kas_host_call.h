@@ -249,6 +249,10 @@ struct KasHostCallIn {
   const int32_t* report_rack = nullptr;
   int64_t racks_cap = 0;                        // kas_rack_tables
   bool have_rk_racks = false, have_rk_scenarios = false, have_rk_off = false;
+  // kas_solve_host_choose_racks / kas_solve_host_front_racks / 16: `racks` together with `choose` or `front` (the rack refusals then
+  // follow the choice's and the moves'), and rack_keys: the spec may name rack criteria (KAS_KEY_RACK_BASE), which need `racks`;
+  // the spec's refusals then come first, as a front's always do.  Defaults: every decision above as it was.
+  bool rack_keys = false;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -311,10 +315,16 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   auto fail = [&](int code, const char* m) { if (err) *err = m; return code; };
   int rc;
   if (in.front) {                                               // a front's own refusals come first
-    const char* bad = kas_front_spec_error(in.front, in.batch->n_scenarios);
+    const char* bad = kas_front_spec_error_keys(in.front, in.batch->n_scenarios, in.rack_keys);
     if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
+    if (in.rack_keys && !in.racks && kas_front_spec_uses_racks(in.front)) return fail(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
     hc->ch_spec = kas_front_choose_spec(in.front);
   } else if (in.choose) {
+    if (in.rack_keys) {                                         // ... and so do those of a choice that may name rack criteria
+      const char* bad = kas_choose_spec_error_keys(in.choose, in.batch->n_scenarios, true);
+      if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
+      if (!in.racks && kas_choose_spec_uses_racks(in.choose)) return fail(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+    }
     hc->ch_spec = *in.choose;
   }
   const kas_choose_spec* const choose = in.front ? &hc->ch_spec : in.choose;
@@ -362,7 +372,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
       return fail(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
   }
   // the rack pass: the table (a negative entry, then too many racks), then the capacity, then the arrays
-  if (in.racks) {
+  auto rack_pass = [&]() -> int {
     if (!in.impact) return fail(KAS_E_INVALID_ARG, "kas_rack_tables: the rack pass needs the impact pass");
     if (in.report_rack && b->node_pool_len <= 0) return fail(KAS_E_INVALID_ARG, "report_rack: a table for a batch without nodes");
     if ((rc = kas_rack_plan_build(b, in.report_rack ? in.report_rack : b->node_rack, full.n_max, full.idmap_entries, full.need_bsearch,
@@ -371,10 +381,12 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     if (in.racks_cap < hc->rack.rack_off[(size_t)S]) return fail(KAS_E_INVALID_ARG, "kas_rack_tables: racks_cap below the sum of the scenarios' rack counts");
     if (!in.have_rk_off || (S > 0 && !in.have_rk_scenarios) || (hc->rack.rack_off[(size_t)S] > 0 && !in.have_rk_racks))
       return fail(KAS_E_INVALID_ARG, "kas_rack_tables: racks / scenarios / rack_off == NULL");
-  }
+    return KAS_E_OK;
+  };
+  if (in.racks && !choose && (rc = rack_pass()) != KAS_E_OK) return rc;
   // a choice: the spec, then the room for any k scenarios (which ones win is not known before the solve), then the arrays
   if (choose) {
-    const char* bad = kas_choose_spec_error(choose, S);
+    const char* bad = kas_choose_spec_error_keys(choose, S, in.rack_keys);
     if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
     const int64_t k = choose->k;
     kas_choose_plan_build(b, &hc->choose);
@@ -416,6 +428,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     hc->mv_moves_cap = in.moves->moves_cap < hc->mv_room_moves ? in.moves->moves_cap : hc->mv_room_moves;
     hc->mv_cells_cap = in.moves->cells_cap < hc->mv_room_cells ? in.moves->cells_cap : hc->mv_room_cells;
   }
+  if (in.racks && choose && (rc = rack_pass()) != KAS_E_OK) return rc;   // (behind a choice's refusals and its moves')
   // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
   const int64_t cell = in.cells16 ? 2 : 4;                     // bytes of a cur / out cell as it travels
   const int64_t cur_cells = full.cur_need - full.cur_lo, out_cells = full.out_need - full.out_lo;
@@ -456,12 +469,12 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     by[KAS_HB_MV_CELLS] = (size_t)cell * (size_t)(hc->mv_cells_cap + 8);
     by[KAS_HB_MV_SIZES0] = choose && !hc->ch_gather_rows ? sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1) : 0;
   }
+  if (choose && !hc->ch_gather_rows) by[KAS_HB_MV_SIZES0] = sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1);   // (with or without moves)
   if (in.racks) {
     by[KAS_HB_RK_RACKS] = sizeof(kas_rack_impact) * (size_t)(hc->rack.rack_off[(size_t)S] + 1);
     by[KAS_HB_RK_SCEN] = sizeof(kas_scenario_rack_impact) * (size_t)(S + 1);
   }
   if (in.front) {
-    if (!hc->ch_gather_rows) by[KAS_HB_MV_SIZES0] = sizeof(KasChooseSize) * (hc->choose.sizes.size() + 1);   // (with or without moves)
     by[KAS_HB_FR_CLS] = 4 * (size_t)(S + 1);
     by[KAS_HB_FR_COUNTS] = by[KAS_HB_FR_COUNTS_PIN] = 4 * sizeof(int32_t);
   }

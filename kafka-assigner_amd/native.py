@@ -33,6 +33,9 @@ SYMBOLS = [
     "kas_solve_host16_choose_moves",
     "kas_front_rank_device", "kas_front_device", "kas_front_device16", "kas_solve_host_front", "kas_solve_host16_front",
     "kas_rack_impact_device", "kas_rack_impact_device16", "kas_solve_host_rack_impact", "kas_solve_host16_rack_impact",
+    "kas_rank_device_racks", "kas_front_rank_device_racks", "kas_choose_device_racks", "kas_choose_device16_racks",
+    "kas_front_device_racks", "kas_front_device16_racks", "kas_solve_host_choose_racks", "kas_solve_host16_choose_racks",
+    "kas_solve_host_front_racks", "kas_solve_host16_front_racks",
 ]
 
 _LIB = None
@@ -166,6 +169,30 @@ def load():
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.FrontSpec),
                        C.POINTER(abi.Choice), C.c_void_p, C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves)]
+    # the *_racks entries: their parents' prototypes with the scenario rack records (device entries) or report_rack and
+    # kas_rack_tables (host entries) added
+    L.kas_rank_device_racks.restype = C.c_int
+    L.kas_rank_device_racks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.ChooseSpec), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kas_front_rank_device_racks.restype = C.c_int
+    L.kas_front_rank_device_racks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.FrontSpec), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for fn in (L.kas_choose_device_racks, L.kas_choose_device16_racks):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p, C.POINTER(abi.ChooseSpec),
+                       C.POINTER(abi.Choice), C.c_void_p]
+    for fn in (L.kas_front_device_racks, L.kas_front_device16_racks):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p, C.POINTER(abi.FrontSpec),
+                       C.POINTER(abi.Choice), C.c_void_p, C.c_void_p]
+    for fn in (L.kas_solve_host_choose_racks, L.kas_solve_host16_choose_racks):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec), C.POINTER(abi.Choice),
+                       C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves), C.c_void_p, C.POINTER(abi.RackTables)]
+    for fn in (L.kas_solve_host_front_racks, L.kas_solve_host16_front_racks):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.FrontSpec), C.POINTER(abi.Choice),
+                       C.c_void_p, C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves), C.c_void_p, C.POINTER(abi.RackTables)]
     if L.kas_abi_version() != abi.KAS_ABI_VERSION:
         raise ImportError("libkas_hip.so ABI version mismatch")
     _LIB = L
@@ -320,6 +347,33 @@ class Plan:
                         choice_nodes or None, int(nodes_cap))
         fn = self._lib.kas_front_device16 if self.cells16 else self._lib.kas_front_device
         _check(fn(self._h, C.byref(t), C.byref(imp), C.byref(spec), C.byref(ch), counts or None, C.c_void_p(stream) if stream else None))
+
+    def choose_device_racks(self, keys, k: int, out: int, scenario_results: int, nodes: int, scenarios: int, rack_scenarios: int,
+                            rank: int, chosen: int, row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int, choice_nodes: int,
+                            nodes_cap: int, stream: int = 0):
+        """kas_choose_device_racks / 16: choose_device with `rack_scenarios`, the device array of scenario rack records this plan's
+        rack pass wrote (rack_impact_device), as a third source of criteria: `keys` names abi.KEY_NAMES and abi.RACK_KEY_NAMES."""
+        t = abi.Tables()
+        t.out = out or None; t.scenario_results = scenario_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        spec = abi.rack_choose_spec(keys, k)
+        ch = abi.Choice(rank or None, chosen or None, row_off or None, node_off or None, n_ok or None, rows or None, int(rows_cap),
+                        choice_nodes or None, int(nodes_cap))
+        fn = self._lib.kas_choose_device16_racks if self.cells16 else self._lib.kas_choose_device_racks
+        _check(fn(self._h, C.byref(t), C.byref(imp), rack_scenarios or None, C.byref(spec), C.byref(ch), C.c_void_p(stream) if stream else None))
+
+    def front_device_racks(self, spec, out: int, scenario_results: int, nodes: int, scenarios: int, rack_scenarios: int, rank: int,
+                           chosen: int, row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int, choice_nodes: int,
+                           nodes_cap: int, counts: int, stream: int = 0):
+        """kas_front_device_racks / 16: front_device with the scenario rack records; `spec`: abi.rack_front_spec."""
+        t = abi.Tables()
+        t.out = out or None; t.scenario_results = scenario_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        ch = abi.Choice(rank or None, chosen or None, row_off or None, node_off or None, n_ok or None, rows or None, int(rows_cap),
+                        choice_nodes or None, int(nodes_cap))
+        fn = self._lib.kas_front_device16_racks if self.cells16 else self._lib.kas_front_device_racks
+        _check(fn(self._h, C.byref(t), C.byref(imp), rack_scenarios or None, C.byref(spec), C.byref(ch), counts or None,
+                  C.c_void_p(stream) if stream else None))
 
     def moves_device(self, mask, select: int, n_select: int, cur: int, out: int, topic_results: int, move_off: int, cell_off: int,
                      moves: int, moves_cap: int, cells: int, cells_cap: int, aux: int = 0, stream: int = 0):
@@ -798,6 +852,107 @@ def solve_host_front(fb: FlatBatch, spec, mask=None, rows: bool = True, cells16:
         ml.select = c.chosen
         ml = _trim(ml)
     return ho, c, ml
+
+
+def rank_device_racks(scenario_results: int, scenario_impact: int, rack_scenarios: int, n_scenarios: int, keys, k: int, rank: int,
+                      chosen: int, n_ok: int, stream: int = 0, ctx: Optional[DeviceContext] = None):
+    """kas_rank_device_racks: rank_device with the scenario rack records (a raw device pointer, or 0) as a third source of
+    criteria; `keys`: names of abi.KEY_NAMES and abi.RACK_KEY_NAMES."""
+    ctx = ctx or default_context()
+    spec = abi.rack_choose_spec(keys, k)
+    _check(load().kas_rank_device_racks(ctx._h, scenario_results or None, scenario_impact or None, rack_scenarios or None, int(n_scenarios),
+                                        C.byref(spec), rank or None, chosen or None, n_ok or None, C.c_void_p(stream) if stream else None))
+
+
+def front_rank_device_racks(scenario_results: int, scenario_impact: int, rack_scenarios: int, n_scenarios: int, spec, rank: int,
+                            chosen: int, counts: int, scratch: int, stream: int = 0, ctx: Optional[DeviceContext] = None):
+    """kas_front_rank_device_racks: front_rank_device with the scenario rack records; `spec`: abi.rack_front_spec."""
+    ctx = ctx or default_context()
+    _check(load().kas_front_rank_device_racks(ctx._h, scenario_results or None, scenario_impact or None, rack_scenarios or None,
+                                              int(n_scenarios), C.byref(spec), rank or None, chosen or None, counts or None,
+                                              scratch or None, C.c_void_p(stream) if stream else None))
+
+
+def _rack_arrays(fb: FlatBatch, report_rack, racks_cap):
+    """(report table or None, RackReport with zeroed arrays, abi.RackTables) for a call with the rack pass"""
+    rep = None if report_rack is None else np.ascontiguousarray(report_rack, dtype=np.int32)
+    S = fb.n_scenarios
+    cap = max(int(rack_counts(fb, rep).sum()), 0) if racks_cap is None else int(racks_cap)
+    rr = RackReport(racks=np.zeros(max(cap, 1), dtype=abi.RACK_IMPACT_DTYPE), scenarios=np.zeros(max(S, 1), dtype=abi.SCENARIO_RACK_IMPACT_DTYPE),
+                    rack_off=np.zeros(S + 1, dtype=np.int64))
+    return rep, rr, abi.RackTables(rr.racks.ctypes.data, rr.scenarios.ctypes.data, rr.rack_off.ctypes.data, cap)
+
+
+def _choice_racks(fb, spec, front, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx):
+    """the shared body of solve_host_choose_racks / solve_host_front_racks"""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)                 # (held until the call returns: the table only borrows it)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    S, kk = fb.n_scenarios, max(int(spec.k), 0)
+    rows_cap = int(np.sort(packed_cells(fb))[::-1][:kk].sum()) if rows else 0
+    nodes_cap = int(np.sort(np.clip(fb.scen["n_nodes"], 0, None).astype(np.int64))[::-1][:kk].sum())
+    c = (Front if front else Choice)(rank=np.full(max(S, 1), -9, np.int32)[:S], chosen=np.full(max(kk, 1), -9, np.int32)[:kk],
+                                     row_off=np.full(kk + 1, -9, np.int64), node_off=np.full(kk + 1, -9, np.int64), n_ok=-9,
+                                     rows=np.zeros(max(rows_cap, 1), np.uint16 if cells16 else np.int32)[:rows_cap],
+                                     nodes=np.zeros(max(nodes_cap, 1), abi.NODE_IMPACT_DTYPE)[:nodes_cap],
+                                     scenarios=np.zeros(max(S, 1), abi.SCENARIO_IMPACT_DTYPE)[:S])
+    n_ok = np.full(1, -9, np.int32)
+    counts = np.full(4, -9, np.int32)
+
+    def p(a):
+        return a.ctypes.data if a.size else None
+    ch = abi.Choice(p(c.rank), p(c.chosen), p(c.row_off), p(c.node_off), p(n_ok), p(c.rows), rows_cap, p(c.nodes), nodes_cap)
+    imp = abi.ImpactTables(None, p(c.scenarios))
+    ml = mv = None
+    if mask is not None:
+        room_rows = int(np.sort(scenario_rows(fb))[::-1][:kk].sum())
+        room_cells = int(np.sort(packed_cells(fb))[::-1][:kk].sum())
+        ml, mv = _move_arrays(mask, kk, room_rows if moves_cap is None else int(moves_cap),
+                              room_cells if cells_cap is None else int(cells_cap), cells16)
+    rep, rr, rk = _rack_arrays(fb, report_rack, racks_cap)
+    tail = (C.byref(imp), C.byref(mv) if mv is not None else None, None if rep is None else C.c_void_p(rep.ctypes.data), C.byref(rk))
+    if front:
+        fn = L.kas_solve_host16_front_racks if cells16 else L.kas_solve_host_front_racks
+        _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), counts.ctypes.data, *tail))
+        c.n_eligible, c.n_front = int(counts[1]), int(counts[2])
+        assert int(counts[0]) == int(n_ok[0]) and int(counts[3]) == 0
+    else:
+        fn = L.kas_solve_host16_choose_racks if cells16 else L.kas_solve_host_choose_racks
+        _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), *tail))
+    c.n_ok = int(n_ok[0])
+    c.rows = c.rows[:int(c.row_off[kk])] if rows else c.rows[:0]
+    c.nodes = c.nodes[:int(c.node_off[kk])]
+    if ml is not None:
+        ml.select = c.chosen
+        ml = _trim(ml)
+    rr.racks, rr.scenarios, rr.impact = rr.racks[:int(rr.rack_off[S])], rr.scenarios[:S], c.scenarios
+    return ho, c, ml, rr
+
+
+def solve_host_choose_racks(fb: FlatBatch, keys, k: int, report_rack=None, mask=None, rows: bool = True, cells16: bool = False,
+                            moves_cap: Optional[int] = None, cells_cap: Optional[int] = None, racks_cap: Optional[int] = None,
+                            ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_choose_racks / 16: solve_host_choose_moves plus the rack pass against `report_rack` (None: the batch's own
+    racks); `keys` may name rack criteria (abi.RACK_KEY_NAMES) beside abi.KEY_NAMES.  mask=None asks for no moves; rows=False
+    hands the library no rows array.  Rows, node blocks and moves come back for the chosen, the rack records for every scenario.
+    Returns (HostOutputs without rows, Choice, MoveList or None, RackReport without node records)."""
+    return _choice_racks(fb, abi.rack_choose_spec(keys, k), False, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx)
+
+
+def solve_host_front_racks(fb: FlatBatch, spec, report_rack=None, mask=None, rows: bool = True, cells16: bool = False,
+                           moves_cap: Optional[int] = None, cells_cap: Optional[int] = None, racks_cap: Optional[int] = None,
+                           ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_front_racks / 16: solve_host_front plus the rack pass; `spec` (abi.rack_front_spec) may name rack criteria
+    among its criteria and its bounds.  Returns (HostOutputs without rows, Front, MoveList or None, RackReport)."""
+    return _choice_racks(fb, spec, True, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx)
 
 
 def solve_host_sharded(fb: FlatBatch, ctxs) -> HostOutputs:

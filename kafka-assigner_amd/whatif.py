@@ -26,7 +26,10 @@ racks=True (with impact=True) adds the rack pass (kas_solve_host_rack_impact): r
 rack with another replica of their partition —, .single_rack_rows_after, .new_rack_replicas, ... and results[0].rack_impact() ->
 {rack name: {"nodes": ..., "replicas_after": ..., "inbound": ...}}.  The report is against the REAL racks (brokers / Variant.add; a
 broker without a rack is a rack of its own, named by its id) whatever rack_aware says, so a rack-unaware variant shows what it
-costs.  best() and front() do not rank by these figures yet.
+costs.  best() and front() rank and bound by these figures too (kas_solve_host_choose_racks / kas_solve_host_front_racks): name a
+rack criterion (abi.RACK_KEY_NAMES: the fields above plus rack_replica_spread and rack_leader_spread) in by= or within=, or pass
+racks=True — plan.best(variants, by=("colocated_after", "replica_spread")), plan.front(variants, by=("moved_replicas",
+"replica_spread"), within={"single_rack_rows_after": 0}) — and every winner carries the rack figures and rack_impact().
 
 moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for the rows that change instead of every row, compacted
 on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
@@ -296,24 +299,59 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ho.out if rows else None, **extra))
         return res
 
+    @staticmethod
+    def _criteria(names, racks: bool) -> bool:
+        """check criterion names; True when the call takes the rack path (racks=True, or a rack criterion among the names)"""
+        for name in names:
+            if name not in abi.KEYS and name not in abi.RACK_KEYS:
+                raise ValueError("unknown criterion %r (one of %s; rack criteria: %s)" %
+                                 (name, ", ".join(abi.KEY_NAMES), ", ".join(abi.RACK_KEY_NAMES)))
+        return bool(racks) or any(name in abi.RACK_KEYS for name in names)
+
+    def _winner(self, variants, fb, ho, ch, ml, j: int, rows: bool, rk=None, rack_names=None) -> VariantResult:
+        """chosen[j] of a choice or a front as a VariantResult"""
+        s = int(ch.chosen[j])
+        sr = ho.scenario_results[s]
+        off, n = int(fb.scen["node_off"][s]), int(fb.scen["n_nodes"][s])
+        extra = {f: int(ch.scenarios[f][s]) for f in abi.SCENARIO_IMPACT_FIELDS}
+        if ml is not None:
+            extra.update(_moves=ml.of(j), _moves_mask=ml.mask)
+        if rk is not None:
+            extra.update({f: int(rk.scenarios[f][s]) for f in abi.SCENARIO_RACK_FIELDS})
+            extra.update(_racks=rk.of(s), _rack_names=rack_names[s])
+        return VariantResult(label=variants[s].label, status=int(sr["status"]), fail_topic=None,
+                             fail_partition=int(sr["fail_partition"]), moved_replicas=int(sr["moved_replicas"]),
+                             moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]), rank=j,
+                             _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
+                             _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
+                             **extra)
+
     def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved"), moves=None,
-             rows: bool = True) -> List[VariantResult]:
+             rows: bool = True, racks: bool = False) -> List[VariantResult]:
         """The k best variants that solve, best first, chosen on the GPU (kas_solve_host_choose): variants are compared by the
         criteria named in `by` (abi.KEY_NAMES; one to four, smaller is better, the earlier variant wins a tie).  Every variant is
         solved and reduced to its records, but rows and per-broker impact come back for the winners only: each result has
         assignment(), broker_impact() and its rank.  Fewer than k results when fewer variants solve.
         moves=(kinds): also each winner's moves (kas_solve_host_choose_moves; moves(), reassignment()); with rows=False no rows
-        are fetched and assignment() raises."""
+        are fetched and assignment() raises.
+        A rack criterion in `by` (abi.RACK_KEY_NAMES), or racks=True, adds the rack pass against the real racks (report_racks)
+        and ranks on its records too (kas_solve_host_choose_racks): each winner then also has the rack figures and rack_impact()."""
         from . import native
         by = [by] if isinstance(by, str) else list(by)
-        for name in by:
-            if name not in abi.KEYS:
-                raise ValueError("unknown criterion %r (one of %s)" % (name, ", ".join(abi.KEY_NAMES)))
+        by_racks = self._criteria(by, racks)
         if not 1 <= len(by) <= abi.KAS_CHOOSE_MAX_KEYS:
             raise ValueError("by: one to four criteria")
         fb = self.flat_batch(variants)
         k = max(0, min(int(k), len(variants)))
         ml = None
+        if by_racks:
+            if moves is None and not rows:
+                raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
+            table, rack_names = self.report_racks(variants)
+            ho, ch, ml, rk = native.solve_host_choose_racks(fb, by, k, report_rack=table, rows=rows,
+                                                            mask=None if moves is None else abi.move_mask(moves))
+            self._fb = fb
+            return [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_ok))]
         if moves is None:
             if not rows:
                 raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
@@ -338,31 +376,40 @@ class WhatIf:
         return res
 
     def front(self, variants: Sequence[Variant], by: Sequence[str] = ("moved_replicas", "replica_spread"), within=None, k: int = 16,
-              moves=None, rows: bool = True) -> "Front":
+              moves=None, rows: bool = True, racks: bool = False) -> "Front":
         """The Pareto front of the variants, marked and ranked on the GPU (kas_solve_host_front): every variant that solves,
         respects the hard bounds in `within` ({criterion: limit}, e.g. {"max_inbound": 200}) and is beaten by no other such
         variant on all the criteria in `by` at once (abi.KEY_NAMES; one to four, smaller is better; of variants with identical
         criteria the earliest survives).  Up to k members come back in the order best() would give them, each with
         assignment(), broker_impact(), its rank and — with moves=(kinds) — moves(); rows=False fetches no rows.  The list also
         carries n_ok, n_eligible, n_front (> len when k cut it) and classes: per variant "member", "dominated", "over_limit"
-        or "failed"."""
+        or "failed".
+        A rack criterion in `by` or `within` (abi.RACK_KEY_NAMES), or racks=True, adds the rack pass against the real racks and
+        marks and ranks on its records too (kas_solve_host_front_racks): members then also have the rack figures and rack_impact()."""
         from . import native
         by = [by] if isinstance(by, str) else list(by)
         within = dict(within or {})
-        for name in by + list(within):
-            if name not in abi.KEYS:
-                raise ValueError("unknown criterion %r (one of %s)" % (name, ", ".join(abi.KEY_NAMES)))
+        by_racks = self._criteria(by + list(within), racks)
         if not 1 <= len(by) <= abi.KAS_CHOOSE_MAX_KEYS:
             raise ValueError("by: one to four criteria")
         if len(within) > abi.KAS_CHOOSE_MAX_KEYS or any(int(v) < 0 for v in within.values()):
             raise ValueError("within: at most four bounds, none negative")
         fb = self.flat_batch(variants)
         k = max(0, min(int(k), len(variants)))
-        ho, ch, ml = native.solve_host_front(fb, abi.front_spec(by, within, k), None if moves is None else abi.move_mask(moves), rows=rows)
+        rk = rack_names = None
+        if by_racks:
+            table, rack_names = self.report_racks(variants)
+            ho, ch, ml, rk = native.solve_host_front_racks(fb, abi.rack_front_spec(by, within, k), report_rack=table, rows=rows,
+                                                           mask=None if moves is None else abi.move_mask(moves))
+        else:
+            ho, ch, ml = native.solve_host_front(fb, abi.front_spec(by, within, k), None if moves is None else abi.move_mask(moves), rows=rows)
         self._fb = fb
         res = Front()
         res.n_ok, res.n_eligible, res.n_front = ch.n_ok, ch.n_eligible, ch.n_front
         res.classes = [abi.FRONT_CLASSES[min(int(r), 0)] for r in ch.rank]
+        if by_racks:
+            res.extend(self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_front)))
+            return res
         for j in range(min(k, ch.n_front)):
             s = int(ch.chosen[j])
             sr = ho.scenario_results[s]
