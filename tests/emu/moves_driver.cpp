@@ -121,14 +121,16 @@ void kas_emu_moves_room(const kas_batch_desc* b, const int32_t* select, int32_t 
 // rows (its other arrays are there); the kas_moves arrays are mv's own.
 // head [12] <- listed, room moves, room cells, device moves cap, device cells cap, K, launch stride, rows gathered, rows needed,
 //              scenarios of the moves table, segments of it, native16;  bytes [KAS_HB_ALL]
+// ranges_override: what the library reads from KAS_HOST_RANGES and passes in (0: not set)
 extern "C" __attribute__((visibility("default")))
 int kas_emu_moves_host_call(const kas_batch_desc* b, const int64_t* lens, unsigned missing, int cells16, const kas_choose_spec* spec,
-                            const int32_t* select, int32_t n_select, const kas_moves* mv, int64_t* head, int64_t* bytes, char* errbuf,
-                            int errlen) {
+                            const int32_t* select, int32_t n_select, const kas_moves* mv, int ranges_override, int64_t* head,
+                            int64_t* bytes, char* errbuf, int errlen) {
   std::vector<int32_t> ident_ids;
   uint64_t ident_stamp = 0;
   KasHostCallIn in;
   in.batch = b;
+  in.ranges_override = ranges_override;
   in.cur_len = lens[0]; in.out_len = 0; in.aux_len = lens[1]; in.ctx_len = lens[2];
   in.have_cur = !(missing & 1u); in.have_out = false; in.have_aux = !(missing & 4u); in.have_ctx = !(missing & 8u);
   in.have_topic_results = !(missing & 16u); in.have_scenario_results = !(missing & 32u);

@@ -64,37 +64,114 @@ def moves_ref(fb, ho, select, mask: int, cells16: bool = False, cur16=None):
         from kafka_assigner_amd.flatten import to_cells16
         cur16 = to_cells16(fb)
     recs, cells, move_off, cell_off, n_rest = [], [], [0], [0], []
+    n_recs = n_cells = 0
     for s in [int(x) for x in select]:
         at, rest = 0, 0
         if 0 <= s < fb.n_scenarios:
             for k, flags, olen, gained, lost, O, part in scenario_rows(fb, ho, s, cells16, cur16):
                 hit = (flags & mask) != 0
                 rest += int((~hit).sum())
-                for p in np.nonzero(hit)[0]:
-                    recs.append((k, int(part[p]), int(flags[p]), int(olen[p]), int(gained[p]), int(lost[p]), at))
-                    cells.extend(int(v) for v in O[p, :int(olen[p])])
-                    at += int(olen[p])
-        move_off.append(len(recs)); cell_off.append(len(cells)); n_rest.append(rest)
+                rows = np.nonzero(hit)[0]                           # the topic's moves, rows ascending
+                lens = olen[rows]
+                r = np.zeros(rows.size, abi.MOVE_DTYPE)
+                r["topic"], r["partition"], r["flags"], r["len"], r["gained"], r["lost"] = k, part[rows], flags[rows], lens, gained[rows], lost[rows]
+                r["cell_at"] = at + np.cumsum(lens) - lens          # lists lie back to back, in row order
+                recs.append(r)
+                cells.append(O[rows][np.arange(O.shape[1])[None, :] < lens[:, None]])      # each row's first olen cells
+                at += int(lens.sum())
+                n_recs += int(rows.size)
+            n_cells += at
+        move_off.append(n_recs); cell_off.append(n_cells); n_rest.append(rest)
     return SimpleNamespace(move_off=np.asarray(move_off, np.int64), cell_off=np.asarray(cell_off, np.int64),
-                           moves=np.array(recs, dtype=abi.MOVE_DTYPE) if recs else np.zeros(0, abi.MOVE_DTYPE),
-                           cells=np.asarray(cells, dtype=np.uint16 if cells16 else np.int32),
+                           moves=np.concatenate(recs) if recs else np.zeros(0, abi.MOVE_DTYPE),
+                           cells=(np.concatenate(cells) if cells else np.zeros(0, np.int64)).astype(np.uint16 if cells16 else np.int32),
                            n_moves=np.diff(np.asarray(move_off, np.int64)), n_rest=np.asarray(n_rest, np.int64))
+
+
+def moves_ref_long(fb, ho, select, mask: int, cells16: bool = False, cur16=None):
+    """moves_ref of a long list with repeats: each distinct entry's block is moves_ref of the one-entry list, computed once and
+    repeated behind shifted offsets (a record's cell_at counts from its block's first cell, so a block is the same wherever it
+    lies; that repeated listings hold equal contents is the contract, and test_select_lists pins it)"""
+    select = [int(s) for s in select]
+    if cells16 and cur16 is None:
+        from kafka_assigner_amd.flatten import to_cells16
+        cur16 = to_cells16(fb)
+    blocks = {s: moves_ref(fb, ho, [s], mask, cells16, cur16) for s in sorted(set(select))}
+    n_moves = np.array([blocks[s].moves.size for s in select], np.int64)
+    n_cells = np.array([blocks[s].cells.size for s in select], np.int64)
+    some = [s for s in select if blocks[s].moves.size]
+    return SimpleNamespace(move_off=np.concatenate([[0], np.cumsum(n_moves)]).astype(np.int64),
+                           cell_off=np.concatenate([[0], np.cumsum(n_cells)]).astype(np.int64),
+                           moves=np.concatenate([blocks[s].moves for s in some]) if some else np.zeros(0, abi.MOVE_DTYPE),
+                           cells=np.concatenate([blocks[s].cells for s in some]) if some else np.zeros(0, np.uint16 if cells16 else np.int32),
+                           n_moves=n_moves, n_rest=np.array([int(blocks[s].n_rest[0]) for s in select], np.int64))
+
+
+# ---- the guard of the tests that take the scan kernel across its tiles ---------------------------------------------------------
+ITEM_ROWS = 1024                        # KAS_MOVES_ITEM_ROWS: rows of an item
+SCAN_TILE = 256                         # KAS_MOVES_BLOCK: entries the scan kernel takes per step of its loop
+
+
+def scenario_items(fb) -> np.ndarray:
+    """int64 [S]: items of each scenario — every topic's ceil(P / ITEM_ROWS), whatever its status; the launch stride is the
+    largest of them, at least 1"""
+    per_topic = -(-np.clip(fb.topics["n_partitions"], 0, None).astype(np.int64) // ITEM_ROWS)
+    return np.array([int(per_topic[int(b):int(b) + max(int(c), 0)].sum()) for b, c in zip(fb.scen["topic_begin"], fb.scen["topic_count"])], np.int64)
+
+
+def scan_entries(fb, ho, select, mask: int, cells16: bool = False, cur16=None) -> np.ndarray:
+    """int64 [n * stride]: the moves of every (listed scenario, item) entry of the table the scan kernel walks, from the checker's
+    flags alone; entries of empty slots and of items a scenario does not have hold 0"""
+    items = scenario_items(fb)
+    stride = max(int(items.max()) if items.size else 0, 1)
+    select = [int(s) for s in select]
+    per = {}
+    for s in set(select):
+        row = np.zeros(stride, np.int64)
+        if 0 <= s < fb.n_scenarios:
+            b, c = int(fb.scen["topic_begin"][s]), max(int(fb.scen["topic_count"][s]), 0)
+            at = 0
+            for k in range(c):
+                P = max(int(fb.topics["n_partitions"][b + k]), 0)
+                blocks = -(-P // ITEM_ROWS)
+                if int(ho.topic_results["status"][b + k]) == abi.KAS_OK and P:
+                    hit = (topic_rows(fb, ho, b + k, cells16, cur16)[0] & mask) != 0
+                    row[at:at + blocks] = np.add.reduceat(hit.astype(np.int64), np.arange(0, P, ITEM_ROWS))
+                at += blocks
+        per[s] = row
+    return np.concatenate([per[s] for s in select]) if select else np.zeros(0, np.int64)
+
+
+def assert_spans_tiles(fb, ho, select, mask: int, want, cells16: bool = False, cur16=None, what: str = "") -> int:
+    """The guard: the table has more than SCAN_TILE entries, and at every multiple of SCAN_TILE below its size the list has a move
+    in an entry before the boundary and one at or behind it — a carry lost or doubled there changes move_off or the records.
+    Returns the number of boundaries."""
+    if cells16 and cur16 is None:
+        from kafka_assigner_amd.flatten import to_cells16
+        cur16 = to_cells16(fb)
+    per = scan_entries(fb, ho, select, mask, cells16, cur16)
+    n = len(select)
+    assert n and per.size % n == 0
+    assert np.array_equal(per.reshape(n, -1).sum(axis=1), np.diff(want.move_off)), (what, "the entries do not add up to the checker's list")
+    assert per.size > SCAN_TILE, (what, "one tile", per.size)
+    before = np.cumsum(per)
+    edges = list(range(SCAN_TILE, per.size, SCAN_TILE))
+    for b in edges:
+        assert before[b - 1] >= 1 and before[-1] - before[b - 1] >= 1, (what, "no move on one side of entry", b)
+    return len(edges)
 
 
 def written_prefix(want, moves_cap: int, cells_cap: int):
     """(records, cells) that the capacities let through: a move is written iff its index is below moves_cap and its list ends at
     or before cells_cap; list ends grow with the index, so these are prefixes"""
-    n = 0
-    used = 0
-    j = 0
-    for i in range(min(int(want.move_off[-1]), moves_cap)):
-        while want.move_off[j + 1] <= i:
-            j += 1
-        end = int(want.cell_off[j]) + int(want.moves["cell_at"][i]) + int(want.moves["len"][i])
-        if end > cells_cap:
-            break
-        n, used = i + 1, end
-    return n, used
+    m = min(int(want.move_off[-1]), max(int(moves_cap), 0))
+    if m == 0:
+        return 0, 0
+    block = np.searchsorted(want.move_off, np.arange(m), side="right") - 1     # the listed scenario whose block holds record i
+    ends = want.cell_off[block] + want.moves["cell_at"][:m].astype(np.int64) + want.moves["len"][:m].astype(np.int64)
+    over = np.nonzero(ends > cells_cap)[0]
+    n = int(over[0]) if over.size else m
+    return n, int(ends[n - 1]) if n else 0
 
 
 def assert_same_moves(want, got, what: str = "", moves_cap=None, cells_cap=None):

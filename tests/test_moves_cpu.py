@@ -3,8 +3,11 @@
 - The three kernel bodies of the moves pass (kafka-assigner_amd/csrc/kas_moves_body.h) compiled with g++ against tests/emu/kas_wave.h
   and stepped on CPU fibers (tests/emu/moves_driver.cpp), against the Python checker (tests/moves_ref.py): oracle-solved batches of
   tests/impact_batches.py in both cell layouts under masks 1, 2, 4, 3 and 7, with the guard that keeps them meaningful; synthetic
-  cur / out tables around every row count at which the code takes another path; select lists; capacities; invariants; determinism.
-- The host call planner (csrc/kas_host_call.h) with the moves arguments: refusals in order, buffer sizes, unchanged plans.
+  cur / out tables around every row count at which the code takes another path; select lists; capacities; invariants; determinism;
+  lists that take the scan kernel across its tiles of 256 entries (tile edges exactly, an edge inside one scenario's items, a tile
+  of full items, capacities that cut in a later tile), each behind a guard that a lost or doubled carry would show.
+- The host call planner (csrc/kas_host_call.h) with the moves arguments: refusals in order, buffer sizes, unchanged plans, the
+  scenario ranges of the calls the GPU tests cut.
 - The ABI: entries declared and exported, struct layouts against a compiled probe, version still 6.
 - WhatIf.solve / best with moves=..., the library's host calls replaced by the oracle and the checker.
 """
@@ -21,7 +24,8 @@ import pytest
 from impact_batches import solved, whatif_inputs
 from kafka_assigner_amd import abi, native
 from kafka_assigner_amd.flatten import FlatBatch, batch_desc, index_form, to_cells16
-from moves_ref import LEADER, ORDER, REPLICAS, assert_same_moves, moves_ref, scenario_rows, written_prefix
+from moves_ref import (ITEM_ROWS, LEADER, ORDER, REPLICAS, SCAN_TILE, assert_same_moves, assert_spans_tiles, moves_ref, moves_ref_long,
+                       scenario_items, scenario_rows, written_prefix)
 from oracle_lib import oracle_solve
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,7 +61,7 @@ def _emu_lib():
     L.kas_emu_moves_room.argtypes = [C.POINTER(abi.BatchDesc), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     L.kas_emu_moves_host_call.restype = C.c_int
     L.kas_emu_moves_host_call.argtypes = [C.POINTER(abi.BatchDesc), C.POINTER(C.c_int64), C.c_uint, C.c_int, C.POINTER(abi.ChooseSpec),
-                                          C.c_void_p, C.c_int32, C.POINTER(abi.Moves), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.c_void_p, C.c_int32, C.POINTER(abi.Moves), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.c_char_p, C.c_int]
     L.kas_emu_moves_buffers.restype = C.c_int
     L.kas_emu_moves_item_rows.restype = C.c_int
@@ -161,17 +165,16 @@ def test_invariants_against_the_solve_records(name):
 
 
 # ---- synthetic tables -----------------------------------------------------------------------------------------------------
-def synthetic(w, seed=0):
-    """cur / out tables with no solve, lists `w` wide.  Scenario 0: one topic per row count around the wavefront, the workgroup
-    and the item, rows of every kind mixed (unchanged, reordered, replaced, out all pad, ragged cur), alternately with a part_id
-    array with gaps.  Scenario 1: a topic whose every row is a move, one with none, a failed topic between two OK ones, a topic
-    of reordered rows only, one whose out is all pad, one without rows.  Scenario 2: no topics.  Scenario 3: one small topic."""
-    I = ITEM()
-    rng = np.random.default_rng([seed, w])
-    cur, out, aux, topics, status = [], [], [], [], []
-    scen = np.zeros(4, abi.SCENARIO_DESC_DTYPE)
+class _Tables:
+    """cur / out tables with no solve, lists `w` wide, topic by topic; rows of the kinds: unchanged, reordered, replaced, out all
+    pad, ragged cur, a lost replica ("mixed": all of them at random)"""
 
-    def topic(P, kind, part_ids=False, ok=True):
+    def __init__(self, w, rng):
+        self.w, self.rng = w, rng
+        self.cur, self.out, self.aux, self.topics, self.status = [], [], [], [], []
+
+    def topic(self, P, kind, part_ids=False, ok=True):
+        w, rng, cur, out, aux, topics, status = self.w, self.rng, self.cur, self.out, self.aux, self.topics, self.status
         O = np.full((P, w), -1, np.int64)
         Cc = np.full((P, w), -1, np.int64)
         clen = np.zeros(P, np.int64)
@@ -203,6 +206,25 @@ def synthetic(w, seed=0):
         cur.append(Cc.reshape(-1)); out.append(O.reshape(-1)); topics.append(t)
         status.append(abi.KAS_OK if ok else abi.KAS_FAIL_UNASSIGNABLE)
 
+    def batch(self, scen):
+        """(fb, the tables a solve would have left) over scenario descriptors `scen`"""
+        fb = FlatBatch(scen=scen, topics=np.array(self.topics, dtype=abi.TOPIC_DESC_DTYPE), node_id=np.arange(50, dtype=np.int32),
+                       node_rack=np.zeros(50, np.int32), cur=np.concatenate(self.cur).astype(np.int32),
+                       aux=np.concatenate(self.aux).astype(np.int32), ctx=np.zeros(0, np.int32), out_len=sum(x.size for x in self.out))
+        tr = np.zeros(len(self.topics), abi.TOPIC_RESULT_DTYPE)
+        tr["status"] = self.status
+        return fb, SimpleNamespace(out=np.concatenate(self.out).astype(np.int32), topic_results=tr)
+
+
+def synthetic(w, seed=0):
+    """Scenario 0: one topic per row count around the wavefront, the workgroup and the item, rows of every kind mixed, alternately
+    with a part_id array with gaps.  Scenario 1: a topic whose every row is a move, one with none, a failed topic between two OK
+    ones, a topic of reordered rows only, one whose out is all pad, one without rows.  Scenario 2: no topics.  Scenario 3: one
+    small topic."""
+    I = ITEM()
+    tb = _Tables(w, np.random.default_rng([seed, w]))
+    topic, topics = tb.topic, tb.topics
+    scen = np.zeros(4, abi.SCENARIO_DESC_DTYPE)
     sizes = [1, 63, 64, 65, 255, 256, 257, I - 1, I, I + 1, 2 * I + 1]
     for i, P in enumerate(sizes):
         topic(P, "mixed", part_ids=i % 2 == 1)
@@ -214,12 +236,7 @@ def synthetic(w, seed=0):
     scen[2] = (50, len(topics), 0, 0, 0, -1)
     topic(300, "mixed", part_ids=True)
     scen[3] = (50, len(topics) - 1, 1, 0, 0, -1)
-    fb = FlatBatch(scen=scen, topics=np.array(topics, dtype=abi.TOPIC_DESC_DTYPE), node_id=np.arange(50, dtype=np.int32),
-                   node_rack=np.zeros(50, np.int32), cur=np.concatenate(cur).astype(np.int32), aux=np.concatenate(aux).astype(np.int32),
-                   ctx=np.zeros(0, np.int32), out_len=sum(x.size for x in out))
-    tr = np.zeros(len(topics), abi.TOPIC_RESULT_DTYPE)
-    tr["status"] = status
-    return fb, SimpleNamespace(out=np.concatenate(out).astype(np.int32), topic_results=tr)
+    return tb.batch(scen)
 
 
 _SYN = {}
@@ -308,6 +325,142 @@ def test_same_bytes_run_after_run_whatever_the_lds_holds(fill):
     assert a.moves.tobytes() == b.moves.tobytes() and a.cells.tobytes() == b.cells.tobytes()
 
 
+# ---- the scan across its tiles --------------------------------------------------------------------------------------------
+# scan_all walks the n x stride table of (listed scenario, item) entries in tiles of SCAN_TILE and carries the totals from tile to
+# tile.  Every list below is checked by assert_spans_tiles first: more than one tile, and moves on both sides of every tile
+# boundary, so that a carry lost or doubled there shows in move_off and in where the records lie.
+def check_long(fb, cur, ho, select, mask, mode, what, spans=True, **kw):
+    """check() for a long list with repeats (moves_ref_long), behind the guard"""
+    c16 = cur if mode == 1 else None
+    want = moves_ref_long(fb, ho, select, mask, cells16=mode == 1, cur16=c16)
+    if spans:
+        assert_spans_tiles(fb, ho, select, mask, want, cells16=mode == 1, cur16=c16, what=what)
+    return want, emu_moves(fb, cur, ho.out, ho.topic_results, select, mask, want, mode=mode, what=what, **kw)
+
+
+def test_the_guard_knows_the_kernels_sizes_and_the_long_checker_the_short_one():
+    src = open(os.path.join(CSRC, "kas_moves.h")).read()
+    assert int(re.search(r"#define KAS_MOVES_BLOCK (\d+)", src).group(1)) == SCAN_TILE and ITEM() == ITEM_ROWS
+    fb, ho = syn(3)
+    select = [3, 3, -1, 1, 0, 2, 3, 1]
+    a, b = moves_ref(fb, ho, select, 7), moves_ref_long(fb, ho, select, 7)
+    for f in ("move_off", "cell_off", "moves", "cells", "n_moves", "n_rest"):
+        assert getattr(a, f).dtype == getattr(b, f).dtype and getattr(a, f).tobytes() == getattr(b, f).tobytes(), f
+    with pytest.raises(AssertionError):                            # 8 x 14 entries: one tile
+        assert_spans_tiles(fb, ho, select, 7, a)
+    with pytest.raises(AssertionError):                            # nothing moves behind the first boundary
+        assert_spans_tiles(fb, ho, [0] * 10 + [2] * 20, 7, moves_ref_long(fb, ho, [0] * 10 + [2] * 20, 7))
+    assert assert_spans_tiles(fb, ho, [0] * 19, 7, moves_ref_long(fb, ho, [0] * 19, 7)) == 1
+
+
+_ONE = {}
+
+
+def one_item_scenarios(w=3):
+    """Stride 1: scenarios of one topic of at most an item's rows.  0: mixed rows; 1: a full item of mixed rows under part ids with
+    gaps; 2: no topics; 3: its only topic failed; 4: every row a move; 5: reordered rows only."""
+    if w not in _ONE:
+        tb = _Tables(w, np.random.default_rng([7, w]))
+        scen = np.zeros(6, abi.SCENARIO_DESC_DTYPE)
+        tb.topic(300, "mixed"); scen[0] = (50, 0, 1, 0, 0, -1)
+        tb.topic(ITEM(), "mixed", part_ids=True); scen[1] = (50, 1, 1, 0, 0, -1)
+        scen[2] = (50, 2, 0, 0, 0, -1)
+        tb.topic(100, "mixed", ok=False); scen[3] = (50, 2, 1, 0, 0, -1)
+        tb.topic(70, "all"); scen[4] = (50, 3, 1, 0, 0, -1)
+        tb.topic(65, "order"); scen[5] = (50, 4, 1, 0, 0, -1)
+        _ONE[w] = tb.batch(scen)
+    return _ONE[w]
+
+
+EDGE_ENTRIES = (255, 256, 511, 512)      # a tile's last lane and the next tile's first, of the first two boundaries
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 511, 512, 513, 769])
+def test_scan_tile_edges_exactly(n):
+    """stride 1, so entry e is listed scenario e: lists that end one short of a tile, on it and one behind it; an empty slot, the
+    scenario without topics, the failed one and a scenario with moves on each of the edge entries in turn"""
+    fb, ho = one_item_scenarios()
+    base = [(0, 4, 1, 5, 4, 0, 1)[j % 7] for j in range(n)]                   # every one of them has moves under mask 7
+    kinds = (-1, 2, 3, None)
+    edges = [e for e in EDGE_ENTRIES if e < n]
+    for turn in range(4 if edges else 1):
+        select = list(base)
+        for q, e in enumerate(EDGE_ENTRIES):
+            if e < n and kinds[(q + turn) % 4] is not None:
+                select[e] = kinds[(q + turn) % 4]
+        # the guard cannot hold where the list ends on a tile's first entry and that entry is the empty one: nothing moves behind the
+        # boundary.  The entry's own move_off is then the carry (an empty slot's offsets are written too), and must not be 0.
+        alone = (n - 1) % SCAN_TILE == 0 and select[n - 1] in (-1, 2, 3)
+        for mask in (1, 7) if (n, turn) == (513, 0) else (7,):
+            want, _ = check_long(fb, fb.cur, ho, select, mask, 0, f"{n} entries, turn {turn}, mask {mask}", spans=n > SCAN_TILE and not alone)
+            if n <= SCAN_TILE or alone:
+                assert want.move_off[n - 1] > 0                                 # (one tile, full or one short of it: the edge itself)
+        for q, e in enumerate(EDGE_ENTRIES):
+            if e < n:
+                assert (want.move_off[e + 1] > want.move_off[e]) == (kinds[(q + turn) % 4] is None), (n, turn, e)
+
+
+LIST_19 = [1, 3, 0, -1, 0, 2, 0, 0, 1, 3, 0, 0, -1, 0, 1, 0, 3, 0, 0]           # x stride 14 = 266 entries
+LIST_300 = [(3, 0, -1, 0, 1)[j % 5] for j in range(300)]                        # x stride 14 = 4200 entries, 16 boundaries
+
+
+def _boundaries_inside(fb, select, s):
+    """tile boundaries that fall between two items of a listing of scenario s"""
+    items = scenario_items(fb)
+    stride = int(items.max())
+    return [b for b in range(SCAN_TILE, len(select) * stride, SCAN_TILE) if select[b // stride] == s and 1 <= b % stride < items[s]]
+
+
+@pytest.mark.parametrize("form", ["w3", "w8", "w3_cells16"])
+def test_scan_tile_edge_inside_one_scenarios_items(form):
+    """stride 14: scenario 0 has fourteen items, and the lists put it across tile boundaries — the carry arrives in the middle of
+    its block of records"""
+    w = int(form[1])
+    mode = 1 if form.endswith("cells16") else 0
+    fb, cur, ho = syn16(w) if mode else (syn(w)[0], syn(w)[0].cur, syn(w)[1])
+    assert _boundaries_inside(fb, LIST_19, 0) == [256] and len(_boundaries_inside(fb, LIST_300, 0)) >= 5
+    assert len(_boundaries_inside(fb, LIST_300, 1)) >= 1 and any(LIST_300[b // 14] == -1 for b in range(256, 4200, 256))
+    for select in (LIST_19, LIST_300):
+        for mask in (7, 1):
+            want, got = check_long(fb, cur, ho, select, mask, mode, f"{form}, {len(select)} entries, mask {mask}")
+            assert want.move_off[-1] > 1000 * len(select) // 5
+
+
+def test_scan_tile_of_full_items():
+    """one scenario of one topic of 1024 rows, lists 8 wide, every row a move, listed 257 times: every entry of the first tile
+    holds 1024 moves and 8192 cells, the most a tile's int32 sums have to take"""
+    tb = _Tables(8, np.random.default_rng(8))
+    tb.topic(ITEM(), "all")
+    scen = np.zeros(1, abi.SCENARIO_DESC_DTYPE)
+    scen[0] = (50, 0, 1, 0, 0, -1)
+    fb, ho = tb.batch(scen)
+    select = [0] * (SCAN_TILE + 1)
+    for mask in (7, 1):
+        want, got = check_long(fb, fb.cur, ho, select, mask, 0, f"full items, mask {mask}")
+        assert (np.diff(want.move_off) == ITEM()).all() and (np.diff(want.cell_off) == 8 * ITEM()).all()
+        assert got.move_off[SCAN_TILE] == SCAN_TILE * ITEM() and got.cell_off[SCAN_TILE] == SCAN_TILE * ITEM() * 8
+
+
+def test_capacities_that_cut_in_a_later_tile():
+    fb, ho = syn(3)
+    select = LIST_300
+    want = moves_ref_long(fb, ho, select, 7)
+    assert_spans_tiles(fb, ho, select, 7, want)
+    M, Cc = int(want.move_off[-1]), int(want.cell_off[-1])
+    first_tile = int(want.move_off[-(-SCAN_TILE // 14)])                       # moves of the listings that reach into the first tile
+    for mc, cc in ((M // 2, Cc), (M, Cc // 3), (M - 1, Cc - 1)):
+        got = emu_moves(fb, fb.cur, ho.out, ho.topic_results, select, 7, want, moves_cap=mc, cells_cap=cc, what=f"caps {mc} {cc}")
+        n, used = written_prefix(want, mc, cc)
+        assert got.moves.size == n and got.cells.size == used and first_tile < n < M, (mc, cc, n, first_tile)
+
+
+def test_same_bytes_across_tiles_whatever_the_lds_holds():
+    fb, ho = syn(3)
+    runs = [check_long(fb, fb.cur, ho, LIST_19, 7, 0, f"lds {fill:#x}", lds_fill=fill)[1] for fill in (0, 0xFFFFFFFF)]
+    for f in ("moves", "cells", "move_off", "cell_off"):
+        assert getattr(runs[0], f).tobytes() == getattr(runs[1], f).tobytes(), f
+
+
 def test_refusals_of_the_arguments():
     fb, ho = syn(3)
     ok = lambda **kw: emu_moves_raw(fb, fb.cur, ho.out, ho.topic_results, [0], kw.pop("mask", 7), moves_cap=4, cells_cap=16, **kw)
@@ -373,7 +526,7 @@ HEAD = ("listed", "room_moves", "room_cells", "moves_cap", "cells_cap", "K", "st
 _BUF = np.zeros(16, np.int64)
 
 
-def moves_host_call(fb, mv=None, select=None, spec=None, rows_cap=0, nodes_cap=None, missing=0, cells16=False):
+def moves_host_call(fb, mv=None, select=None, spec=None, rows_cap=0, nodes_cap=None, missing=0, cells16=False, ranges_override=0):
     L = _emu_lib()
     assert L.kas_emu_moves_buffers() == len(HOST_BUFS)
     bd = batch_desc(fb)
@@ -389,7 +542,7 @@ def moves_host_call(fb, mv=None, select=None, spec=None, rows_cap=0, nodes_cap=N
     err = C.create_string_buffer(512)
     rc = L.kas_emu_moves_host_call(C.byref(bd), lens, missing, int(cells16), None if spec is None else C.byref(spec),
                                    None if sel is None or not sel.size else sel.ctypes.data, -1 if sel is None else int(sel.size), C.byref(mv),
-                                   head, nbytes, err, 512)
+                                   ranges_override, head, nbytes, err, 512)
     if rc != 0:
         return rc, None, err.value.decode()
     plan = dict(zip(HEAD, [int(v) for v in head]))
@@ -468,6 +621,32 @@ def test_planner_buffer_sizes(cells16):
     rc, theirs, _ = tc.choose_host_call(fb, tc._spec(("moved_replicas",), 3), cells16=cells16)
     rc2, mine, _ = moves_host_call(fb, spec=_choose_spec(3), rows_cap=theirs["rows_need"], cells16=cells16)
     assert rc == 0 and rc2 == 0 and {n: mine["bytes"][n] for n in HOST_BUFS[:20]} == theirs["bytes"] and mine["K"] == theirs["K"]
+
+
+def test_planner_scenario_ranges_of_a_moves_call():
+    """S x 100k x 3 cells with a `cur` per scenario (descriptors only): a moves call uploads cur and downloads no out table, as a
+    choice does.  The counts tests/test_moves_gpu.py relies on when it asks for a call cut into ranges: 52.8 MB (44 scenarios of
+    int32 cells, 88 of 16-bit cells) are two ranges, 26.4 MB (44 of 16-bit cells, below KAS_HOST_SPLIT_MIN_BYTES) one, and the
+    KAS_HOST_RANGES override the library passes in decides otherwise"""
+    from kafka_assigner_amd import generator as G
+    from kafka_assigner_amd.flatten import node_set_batch
+    P, N, R = 100_000, 200, 10
+    sets = [G.scenario_action(61, s, N, R, actions=G.BENCH_ACTIONS)[1] for s in range(44)]
+
+    def shape(S):
+        return node_set_batch([sets[s % 44].node_id for s in range(S)], [sets[s % 44].node_rack for s in range(S)], P, 3, 3,
+                              cur=np.zeros((S, P, 3), np.int32))
+    fb44, fb88 = shape(44), shape(88)
+    select = [43, -1, 0, 22, 21, 43]
+    K = lambda fb, **kw: (lambda rc, plan, err: plan["K"] if rc == 0 else (rc, err))(*moves_host_call(fb, **kw))
+    assert K(fb44, select=select) == 2 and K(fb44) == 2
+    spec = _choose_spec(3, ("max_outbound", "moved_replicas"))
+    assert K(fb44, spec=spec, rows_cap=9 * P) == 2 and K(fb44, spec=spec, rows_cap=0, missing=8192) == 2
+    assert K(fb88, select=select + [87, 44], cells16=True) == 2
+    assert K(fb44, select=select, cells16=True) == 1
+    assert K(fb44, select=select, ranges_override=3) == 3
+    rc, plan, err = moves_host_call(fb44, select=select)
+    assert plan["stride"] == -(-P // ITEM()) == 98 and plan["listed"] * plan["stride"] > 2 * SCAN_TILE   # the list spans three tiles
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------
