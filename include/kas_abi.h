@@ -753,6 +753,82 @@ int kas_solve_host16_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, cons
                                  const kas_impact_tables* host_impact, const kas_moves* host_moves, const int32_t* report_rack,
                                  const kas_rack_tables* host_racks);
 
+/* ---- topic impact: what a scenario does to each of its topics, reduced on the device (added under ABI v6) ---------------
+ * A pass of its own behind a solve: nothing here depends on the impact pass having run.  Rows, C, O, clen, olen and "names a
+ * node" are exactly those of kas_node_impact above.  The scenario-level spread hides what happens inside a topic (two topics
+ * skewed in opposite directions sum to a flat cluster), and the reference bounds only a topic's maximum per broker, never the
+ * minimum, and the leaders not at all.
+ * Ranking or fronting by these figures is not part of this pass.  The scenario record is laid out (sixteen non-negative int32)
+ * so that its words can become criteria. */
+#define KAS_TOPIC_SCRATCH_LIMIT (256ll << 20)   /* bytes of global counters one topic pass may need (see the refusals below) */
+
+/* One per topic descriptor of the batch, in descriptor order: the fields of kas_scenario_impact, with the same meanings, taken
+ * over THIS TOPIC'S rows only.  Max and min are over all nodes of the topic's scenario; a node that holds nothing of the topic
+ * counts as 0.  Every field is 0 when the topic's status is not KAS_OK or the scenario has no nodes. */
+typedef struct kas_topic_impact {
+  int32_t departed_replicas;
+  int32_t leaders_moved;
+  int32_t max_inbound, max_outbound;              /* the most replicas of the topic one node receives / gives up */
+  int32_t min_replicas_after, max_replicas_after;
+  int32_t min_leaders_after, max_leaders_after;
+} kas_topic_impact;
+
+/* Per scenario, over its topics whose status is KAS_OK ("topics" below; a scenario without such topics gets zeros).  The
+ * replica spread of a topic is max_replicas_after - min_replicas_after, its leader spread the same for leaders. */
+typedef struct kas_scenario_topic_impact {
+  int32_t topics_ok;                   /* word 0: number of KAS_OK topics                                   */
+  int32_t topics_moved;                /*  1: topics with kas_topic_result.moved_replicas > 0               */
+  int32_t topics_leaders_moved;        /*  2: topics with leaders_moved > 0                                 */
+  int32_t topics_departed;             /*  3: topics with departed_replicas > 0                             */
+  int32_t max_topic_moved_replicas;    /*  4: max over topics of kas_topic_result.moved_replicas            */
+  int32_t max_topic_moved_partitions;  /*  5: ... of kas_topic_result.moved_partitions                      */
+  int32_t max_topic_leaders_moved;     /*  6: max over topics of leaders_moved                              */
+  int32_t max_topic_inbound;           /*  7: the most replicas of one topic that one node receives         */
+  int32_t max_topic_outbound;          /*  8: the most replicas of one topic that one node gives up         */
+  int32_t max_topic_replica_spread;    /*  9: max over topics of the replica spread                         */
+  int32_t max_topic_leader_spread;     /* 10: ... of the leader spread                                      */
+  int32_t max_topic_replicas_after;    /* 11: max over topics of max_replicas_after                         */
+  int32_t max_topic_leaders_after;     /* 12: ... of max_leaders_after                                      */
+  int32_t sum_topic_replica_spread;    /* 13: sum over topics of the replica spread                         */
+  int32_t sum_topic_leader_spread;     /* 14: ... of the leader spread                                      */
+  int32_t reserved;                    /* 15: 0                                                             */
+} kas_scenario_topic_impact;
+
+/* Where the records go: one kas_topic_impact per topic descriptor, one kas_scenario_topic_impact per scenario. */
+typedef struct kas_topic_impact_tables {
+  kas_topic_impact*          topics;      /* [n_topics]    */
+  kas_scenario_topic_impact* scenarios;   /* [n_scenarios] */
+} kas_topic_impact_tables;
+
+/* The topic impact of the plan's previous solve: device_tables are the tables that solve used (device pointers;
+ * device_out->topics and ->scenarios too).  Asynchronous, ordered behind the plan's previous solve (and its previous topic
+ * pass); a later solve of the plan waits for it, as it waits for the impact pass.  It writes every record of its outputs
+ * itself: nothing has to be cleared in front of the caller's arrays.  A plan's first call builds and uploads the pass's work
+ * list with blocking copies; later calls only enqueue.
+ * A topic whose scenario's n_nodes x 16 bytes of counters fit the LDS next to the id lookup (about 9,000 brokers) counts
+ * there; a topic cut into row ranges (batches of few topics, as in the impact pass) adds its ranges' counters up in global
+ * scratch, and a topic of a larger scenario counts in global scratch altogether: (4 n_nodes + 2) int32 per such topic.
+ * Refused before any GPU work, in this order: KAS_E_INVALID_ARG for a NULL argument or array (device_out->topics with
+ * n_topics > 0, ->scenarios with n_scenarios > 0, a table the pass reads); KAS_E_INVALID_ARG for a plan without a solve;
+ * KAS_E_UNSUPPORTED when that global scratch would exceed KAS_TOPIC_SCRATCH_LIMIT bytes.  No scenario is refused for its
+ * broker count up to KAS_N_LIMIT. */
+int kas_topic_impact_device(kas_plan* plan, const kas_tables* device_tables, const kas_topic_impact_tables* device_out,
+                            void* hip_stream);
+int kas_topic_impact_device16(kas_plan* plan, const kas_tables16* device_tables, const kas_topic_impact_tables* device_out,
+                              void* hip_stream);
+
+/* kas_solve_host_impact / 16 plus the topic pass on each scenario range's stream, behind its solve; the records come back in
+ * host_topics (host memory).  host_impact may be NULL: then no impact pass runs and no impact record is allocated or copied;
+ * host_impact->nodes may be NULL as in kas_solve_host_rack_impact (the node records then stay on the device).
+ * Refusals, behind those of kas_solve_host_impact and in the order above: KAS_E_INVALID_ARG for host_topics == NULL or an
+ * array of it that is NULL; KAS_E_UNSUPPORTED for the scratch limit (taken over the whole batch). */
+int kas_solve_host_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                                const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact,
+                                const kas_topic_impact_tables* host_topics);
+int kas_solve_host16_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                  const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact,
+                                  const kas_topic_impact_tables* host_topics);
+
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */
 int  kas_host_alloc(int64_t bytes, void** out_ptr);

@@ -265,6 +265,26 @@ class RackTables(C.Structure):
     _fields_ = [("racks", C.c_void_p), ("scenarios", C.c_void_p), ("rack_off", C.c_void_p), ("racks_cap", C.c_int64)]
 
 
+# the topic pass behind a solve (kas_topic_impact / kas_scenario_topic_impact) and where its records go (kas_topic_impact_tables)
+KAS_TOPIC_SCRATCH_LIMIT = 256 << 20
+TOPIC_IMPACT_FIELDS = ("departed_replicas", "leaders_moved", "max_inbound", "max_outbound", "min_replicas_after", "max_replicas_after",
+                       "min_leaders_after", "max_leaders_after")
+SCENARIO_TOPIC_FIELDS = ("topics_ok", "topics_moved", "topics_leaders_moved", "topics_departed", "max_topic_moved_replicas",
+                         "max_topic_moved_partitions", "max_topic_leaders_moved", "max_topic_inbound", "max_topic_outbound",
+                         "max_topic_replica_spread", "max_topic_leader_spread", "max_topic_replicas_after", "max_topic_leaders_after",
+                         "sum_topic_replica_spread", "sum_topic_leader_spread")
+TOPIC_IMPACT_DTYPE = _np.dtype([(f, "<i4") for f in TOPIC_IMPACT_FIELDS])
+SCENARIO_TOPIC_IMPACT_DTYPE = _np.dtype([(f, "<i4") for f in SCENARIO_TOPIC_FIELDS] + [("reserved", "<i4")])
+TOPIC_ENTRIES = ("kas_topic_impact_device", "kas_topic_impact_device16", "kas_solve_host_topic_impact", "kas_solve_host16_topic_impact")
+
+
+class TopicImpactTables(C.Structure):
+    _fields_ = [("topics", C.c_void_p), ("scenarios", C.c_void_p)]
+
+
+assert TOPIC_IMPACT_DTYPE.itemsize == 32 and SCENARIO_TOPIC_IMPACT_DTYPE.itemsize == 64 and C.sizeof(TopicImpactTables) == 16
+
+
 # rack criteria of the *_racks entries: key KAS_KEY_RACK_BASE + i is int32 word i of kas_scenario_rack_impact, two spreads behind
 KAS_KEY_RACK_BASE = 16
 RACK_KEY_NAMES = SCENARIO_RACK_FIELDS + ("rack_replica_spread", "rack_leader_spread")

@@ -30,6 +30,7 @@
 #include "kas_host_call.h"     // what a host call does: ranges, cell width, buffer sizes, the plan cache's choice
 #include "kas_impact.h"   // the impact pass (ABI v6): its kernels are kas_impact.hip's
 #include "kas_racks.h"    // the rack pass behind it: its kernels are kas_racks.hip's
+#include "kas_topics.h"   // the topic pass behind a solve: its kernels are kas_topics.hip's
 #include "kas_choose.h"   // ranking and gathering the best scenarios: its kernels are kas_choose.hip's
 #include "kas_front.h"    // marking and ranking the Pareto front: kas_choose.hip's as well
 #include "kas_moves.h"    // the move list of a solve: its kernels are kas_moves.hip's
@@ -398,7 +399,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_LAST];             // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_EVERY];            // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records, topic records (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -457,6 +458,14 @@ struct kas_plan {
   int rack_host_ready = 0;              // the two below have been read back (a rack call without the batch in host memory)
   std::vector<kas_scenario_desc> rk_scen;
   std::vector<int32_t> rk_node_rack;
+  // topic pass (kas_topic_impact_device / 16): the work list is built at the plan's first topic call and kept until the plan is
+  // rebuilt; an event of its own, so that the pass needs no impact pass and the passes behind the impact pass see only that one
+  int topics_ready = 0;
+  KasTopicPlan topics;
+  KasBuf b_tp_items, b_tp_merge, b_tp_roff, b_tp_region;
+  hipEvent_t ev_topics = nullptr;       // recorded behind the plan's last topic pass
+  hipStream_t topics_stream = nullptr;
+  int topics_pending = 0;               // ev_topics has been recorded
   // choosing on the device (kas_choose_device / 16): the size and segment tables, built at the plan's first such call
   int choose_ready = 0;
   KasChoosePlan choose;
@@ -635,7 +644,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_LAST; ++i) {
+  for (int i = 0; i < KAS_HB_EVERY; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -670,6 +679,9 @@ void kas_plan_destroy(kas_plan* p) {
   if (p->last_slot >= 0) (void)hipEventSynchronize(p->ev_stop[p->last_slot]);
   if (p->impact_pending) (void)hipEventSynchronize(p->ev_impact);
   if (p->moves_pending) (void)hipEventSynchronize(p->ev_moves);
+  if (p->topics_pending) (void)hipEventSynchronize(p->ev_topics);
+  for (KasBuf* b : {&p->b_tp_items, &p->b_tp_merge, &p->b_tp_roff, &p->b_tp_region}) kas_buf_free(b);
+  if (p->ev_topics) (void)hipEventDestroy(p->ev_topics);
   for (KasBuf* b : {&p->b_mv_scen, &p->b_mv_segs, &p->b_mv_scratch}) kas_buf_free(b);
   if (p->ev_moves) (void)hipEventDestroy(p->ev_moves);
   for (KasBuf* b : {&p->b_imp_items, &p->b_imp_merge, &p->b_imp_base, &p->b_imp_roff, &p->b_imp_region, &p->b_ch_sizes, &p->b_ch_segs, &p->b_fr_cls,
@@ -751,6 +763,8 @@ static int kas_plan_build(kas_plan* p, const kas_batch_desc* batch) {
   if (p->last_slot >= 0) KAS_HIP_TRY(hipEventSynchronize(p->ev_stop[p->last_slot]));
   if (p->impact_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_impact));   // (its work list is about to go)
   if (p->moves_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_moves));
+  if (p->topics_pending) KAS_HIP_TRY(hipEventSynchronize(p->ev_topics));   // (its work list too)
+  p->topics_ready = 0; p->topics_pending = 0;
   p->impact_ready = 0; p->impact_pending = 0; p->choose_ready = 0; p->moves_ready = 0; p->moves_pending = 0;
   p->rack_ready = 0; p->rack_host_ready = 0; p->node_pool_len = batch->node_pool_len;
   kas_moves_plan_build(batch, &p->moves);
@@ -940,6 +954,8 @@ static int kas_solve_device_impl(kas_plan* p, const kas_tables* t, void* hip_str
     KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
   if (p->moves_pending && p->moves_stream != st)             // (... and a moves pass: the same)
     KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_moves, 0));
+  if (p->topics_pending && p->topics_stream != st)           // (... and a topic pass: the same)
+    KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_topics, 0));
   p->last_stream = st;
   a.n_scenarios = p->n_scenarios; a.n_max = p->shape.n_max;
   a.idmap_entries = p->shape.idmap_entries; a.need_bsearch = p->shape.need_bsearch;
@@ -1178,6 +1194,94 @@ int kas_rack_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_imp
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_rack_impact_device16 needs a plan of kas_plan_create16");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_rack_impl(p, &t, imp, host_report_rack, out, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
+}
+
+// ---- the topic pass (kernels: kas_topics.hip) ---------------------------------------------------------------------------
+// The plan's work list: built at its first topic call from the batch in host memory (`hb`, the host path's slice) or, without
+// one, from the descriptors the plan holds on the device (read back once); kept until the plan is rebuilt.  Nothing is
+// uploaded or allocated before the scratch limit has been checked.
+static int kas_topic_prepare(kas_plan* p, const kas_batch_desc* hb) {
+  if (p->topics_ready) return KAS_E_OK;
+  std::vector<kas_scenario_desc> sc;
+  std::vector<kas_topic_desc> tp;
+  kas_batch_desc b;
+  memset(&b, 0, sizeof(b));
+  if (hb) {
+    b = *hb;
+  } else {
+    sc.resize((size_t)p->n_scenarios); tp.resize((size_t)p->n_topics);
+    if (!sc.empty()) KAS_HIP_TRY(hipMemcpy(sc.data(), p->b_scen.p, sizeof(kas_scenario_desc) * sc.size(), hipMemcpyDeviceToHost));
+    if (!tp.empty()) KAS_HIP_TRY(hipMemcpy(tp.data(), p->b_topics.p, sizeof(kas_topic_desc) * tp.size(), hipMemcpyDeviceToHost));
+    b.n_scenarios = p->n_scenarios; b.n_topics = p->n_topics; b.scenarios = sc.data(); b.topics = tp.data();
+  }
+  KasTopicPlan& k = p->topics;
+  kas_topic_plan_build(&b, p->shape.n_max, p->shape.idmap_entries, p->shape.need_bsearch, p->cells16, -1, kas_impact_rows_per_item(&b), &k);
+  if (!kas_topic_scratch_ok(k)) return set_error(KAS_E_UNSUPPORTED, KAS_TOPIC_SCRATCH_TEXT);
+  struct Up { KasBuf* b; const void* src; size_t bytes; const char* what; };
+  const Up ups[] = {
+      {&p->b_tp_items, k.items.data(), sizeof(KasImpactItem) * k.items.size(), "topic work list"},
+      {&p->b_tp_merge, k.merge.data(), sizeof(KasTopicMerge) * k.merge.size(), "topic merge list"},
+      {&p->b_tp_roff, k.region_off.data(), sizeof(int64_t) * k.region_off.size(), "topic counter offsets"},
+  };
+  int rc;
+  for (const Up& u : ups) {
+    if ((rc = kas_buf_reserve(u.b, u.bytes, p->allocs, u.what)) != KAS_E_OK) return rc;
+    if (u.bytes > 0) KAS_HIP_TRY(hipMemcpy(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice));
+  }
+  if ((rc = kas_buf_reserve(&p->b_tp_region, sizeof(int32_t) * (size_t)(k.region_ints + 1), p->allocs, "topic counters")) != KAS_E_OK)
+    return rc;
+  if (!p->ev_topics) KAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_topics, hipEventDisableTiming));
+  p->topics_ready = 1;
+  return KAS_E_OK;
+}
+
+// The topic impact of the plan's previous solve, from the tables `t` it used, into `out` (device pointers), on `st`.
+static int kas_topic_impl(kas_plan* p, const kas_tables* t, const kas_topic_impact_tables* out, hipStream_t st, const kas_batch_desc* hb) {
+  const int64_t S = p->n_scenarios, T = p->n_topics;
+  if ((T > 0 && !out->topics) || (S > 0 && !out->scenarios)) return set_error(KAS_E_INVALID_ARG, "kas_topic_impact_tables: topics / scenarios == NULL");
+  if (T > 0 && (!t->out || !t->topic_results || (p->shape.cur_need > 0 && !t->cur) || (p->shape.aux_need > 0 && !t->aux)))
+    return set_error(KAS_E_INVALID_ARG, "a table the topic pass reads is NULL");
+  if (S == 0) return KAS_E_OK;
+  if (p->last_slot < 0) return set_error(KAS_E_INVALID_ARG, "kas_topic_impact_device: the plan has no solve to report on");
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  int rc = kas_topic_prepare(p, hb);
+  if (rc != KAS_E_OK) return rc;
+  const KasTopicPlan& k = p->topics;
+  // ordered behind the plan's previous solve, and behind its previous topic pass (the counters are the plan's)
+  if (p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->topics_pending && p->topics_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_topics, 0));
+  if (k.region_ints > 0) KAS_HIP_TRY(hipMemsetAsync(p->b_tp_region.p, 0, sizeof(int32_t) * (size_t)k.region_ints, st));
+  KasTopicLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.scen = (const kas_scenario_desc*)p->b_scen.p; a.topics = (const kas_topic_desc*)p->b_topics.p;
+  a.node_id = (const int32_t*)p->b_node_id.p;
+  a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.topic_results = t->topic_results;
+  a.items = (const KasImpactItem*)p->b_tp_items.p; a.merge = (const KasTopicMerge*)p->b_tp_merge.p;
+  a.region_off = (const int64_t*)p->b_tp_roff.p; a.region = (int32_t*)p->b_tp_region.p;
+  a.topic_out = out->topics; a.scenarios = out->scenarios;
+  a.n_items = (int32_t)k.items.size(); a.n_merge = (int32_t)k.merge.size(); a.n_scenarios = (int32_t)S;
+  a.idmap_entries = p->shape.idmap_entries;
+  a.off_look = k.off_look; a.off_red = k.off_red; a.lds_bytes = k.lds_bytes;
+  a.cells16 = p->cells16;
+  const int e = kas_topic_launch(&a, p->Wc, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("topic pass: ") + hipGetErrorString((hipError_t)e));
+  KAS_HIP_TRY(hipEventRecord(p->ev_topics, st));
+  p->topics_stream = st;
+  p->topics_pending = 1;
+  return KAS_E_OK;
+}
+
+int kas_topic_impact_device(kas_plan* p, const kas_tables* t, const kas_topic_impact_tables* out, void* hip_stream) {
+  if (!p || !t || !out) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_topic_impact_device16");
+  return kas_topic_impl(p, t, out, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
+}
+
+int kas_topic_impact_device16(kas_plan* p, const kas_tables16* t16, const kas_topic_impact_tables* out, void* hip_stream) {
+  if (!p || !t16 || !out) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_topic_impact_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_topic_impl(p, &t, out, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr);
 }
 
 // ---- choosing the best scenarios (kernels: kas_choose.hip) --------------------------------------------------------------
@@ -1762,7 +1866,8 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
                                  int32_t n_select, const KasCells16* c16 = nullptr, const kas_impact_tables* himp = nullptr,
                                  const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
                                  bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
-                                 const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr, bool rack_keys = false) {
+                                 const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr, bool rack_keys = false,
+                                 bool topic_pass = false, const kas_topic_impact_tables* htp = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1794,6 +1899,10 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.racks = true; in.report_rack = report_rack; in.racks_cap = hrk->racks_cap;
     in.have_rk_racks = hrk->racks != nullptr; in.have_rk_scenarios = hrk->scenarios != nullptr; in.have_rk_off = hrk->rack_off != nullptr;
   }
+  if (topic_pass) {                                            // kas_solve_host_topic_impact / 16
+    in.topics = true; in.have_tp_tables = htp != nullptr;
+    in.have_tp_topics = htp && htp->topics; in.have_tp_scenarios = htp && htp->scenarios;
+  }
   in.lane_order_ok = ctx->lds_lane_order_ok;
   for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
   if (const char* e = getenv("KAS_HOST_RANGES")) in.ranges_override = atoi(e);
@@ -1813,7 +1922,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_LAST; ++i)
+  for (int i = 0; i < KAS_HB_EVERY; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -1923,6 +2032,13 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
         const int rrc = kas_rack_impl(plans[i], &d, &di, rep, &dr, st, &r.bd);
         if (rrc != KAS_E_OK) { fail_rc = rrc; break; }
       }
+    }
+    if (topic_pass) {                                          // the topic pass on the range's solve stream, behind its solve
+      kas_topic_impact_tables dt;
+      dt.topics = (kas_topic_impact*)ctx->hbuf[KAS_HB_TP_TOPICS].p + r.own[KAS_POOL_TOPICS].lo;
+      dt.scenarios = (kas_scenario_topic_impact*)ctx->hbuf[KAS_HB_TP_SCEN].p + r.lo;
+      const int trc = kas_topic_impl(plans[i], &d, &dt, st, &r.bd);
+      if (trc != KAS_E_OK) { fail_rc = trc; break; }
     }
     if (widened && all_rows && o.hi > o.lo && !narrow(st, o.lo, o.hi - o.lo)) break;
     if (K > 1) hip_ok(hipEventRecord(ctx->hev_done[i], st), "record");
@@ -2058,6 +2174,11 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (S > 0) copy(hrk->scenarios, ctx->hbuf[KAS_HB_RK_SCEN].p, sizeof(kas_scenario_rack_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario rack impact");
     memcpy(hrk->rack_off, hc.rack.rack_off.data(), sizeof(int64_t) * ((size_t)S + 1));
   }
+  if (topic_pass) {
+    const int64_t T = batch->n_topics;
+    if (T > 0) copy(htp->topics, ctx->hbuf[KAS_HB_TP_TOPICS].p, sizeof(kas_topic_impact) * (size_t)T, hipMemcpyDeviceToHost, s0, "download topic impact");
+    if (S > 0) copy(htp->scenarios, ctx->hbuf[KAS_HB_TP_SCEN].p, sizeof(kas_scenario_topic_impact) * (size_t)S, hipMemcpyDeviceToHost, s0, "download scenario topic impact");
+  }
   // the move list: the offsets (they are here already), then exactly the records that were written and the cells they use
   if (hmv && he == hipSuccess) {
     const int64_t total = p_mvh[mv_n], total_cells = p_mvh[2 * mv_n + 1];
@@ -2148,6 +2269,25 @@ int kas_solve_host16_rack_impact(kas_ctx* ctx, const kas_batch_desc* batch, cons
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp, nullptr, nullptr, nullptr, false, nullptr, nullptr,
                                hrk, report_rack);
+}
+
+// (host_impact may be NULL: no impact pass; host_topics == NULL is the planner's refusal, in its documented place)
+int kas_solve_host_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select, int32_t n_select,
+                                const kas_impact_tables* himp, const kas_topic_impact_tables* htp) {
+  if (!ctx || !batch || !h) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, select, n_select, nullptr, himp, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr,
+                               false, true, htp);
+}
+
+int kas_solve_host16_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
+                                  const kas_impact_tables* himp, const kas_topic_impact_tables* htp) {
+  if (!ctx || !batch || !h16) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp, nullptr, nullptr, nullptr, false, nullptr, nullptr,
+                               nullptr, nullptr, false, true, htp);
 }
 
 int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,

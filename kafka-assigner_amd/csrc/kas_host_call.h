@@ -18,6 +18,7 @@
 #include "kas_moves.h"         // the scenario and segment tables of kas_solve_host_moves / kas_solve_host_choose_moves
 #include "kas_front.h"         // the spec of kas_solve_host_front
 #include "kas_racks.h"         // the rack tables of kas_solve_host_rack_impact
+#include "kas_topics.h"        // the work list of kas_solve_host_topic_impact (its scratch decides a refusal)
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -207,7 +208,10 @@ enum KasHostBuf {
   KAS_HB_END,                                       // the buffers of the calls above end here
   // kas_solve_host_rack_impact / 16 alone (behind KAS_HB_END, for the same reason)
   KAS_HB_RK_RACKS = KAS_HB_END, KAS_HB_RK_SCEN,     // the rack records and the scenario rack records on the device
-  KAS_HB_LAST
+  KAS_HB_LAST,                                      // the buffers of the calls above end here
+  // kas_solve_host_topic_impact / 16 alone (behind KAS_HB_LAST, for the same reason)
+  KAS_HB_TP_TOPICS = KAS_HB_LAST, KAS_HB_TP_SCEN,   // the topic records and the scenario topic records on the device
+  KAS_HB_EVERY
 };
 static inline bool kas_host_buf_pinned(int32_t id) {
   return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN ||
@@ -253,6 +257,10 @@ struct KasHostCallIn {
   // follow the choice's and the moves'), and rack_keys: the spec may name rack criteria (KAS_KEY_RACK_BASE), which need `racks`;
   // the spec's refusals then come first, as a front's always do.  Defaults: every decision above as it was.
   bool rack_keys = false;
+  // kas_solve_host_topic_impact / 16: the topic pass behind the solve, with the impact pass (`impact`) or without it (defaults:
+  // no topic pass, and every decision above as it was); with `topics` the node records may stay on the device, as with `racks`
+  bool topics = false;
+  bool have_tp_tables = false, have_tp_topics = false, have_tp_scenarios = false;   // kas_topic_impact_tables
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -282,7 +290,7 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_LAST] = {};               // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_EVERY] = {};              // what to reserve of each buffer; 0: this call must not touch it
   // kas_solve_host_choose / 16
   KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
   int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
@@ -298,6 +306,8 @@ struct KasHostCall {
   int64_t mv_moves_cap = 0, mv_cells_cap = 0;   // the capacities on the device: the caller's, no more than the room
   // kas_solve_host_rack_impact / 16
   KasRackPlan rack;                             // the report table and rack_off of the whole call
+  // kas_solve_host_topic_impact / 16
+  int64_t tp_region_ints = 0;                   // global counters the pass needs over the whole batch (the ranges' plans hold their own)
 };
 
 // Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
@@ -368,7 +378,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.impact) {
     hc->imp_base.assign((size_t)S + 1, 0);
     for (int64_t s = 0; s < S; ++s) hc->imp_base[(size_t)s + 1] = hc->imp_base[(size_t)s] + (b->scenarios[s].n_nodes > 0 ? b->scenarios[s].n_nodes : 0);
-    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !choose && !in.racks))
+    if ((S > 0 && !in.have_imp_scenarios) || (hc->imp_base[(size_t)S] > 0 && !in.have_imp_nodes && !choose && !in.racks && !in.topics))
       return fail(KAS_E_INVALID_ARG, "kas_impact_tables: nodes / scenarios == NULL");
   }
   // the rack pass: the table (a negative entry, then too many racks), then the capacity, then the arrays
@@ -384,6 +394,15 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     return KAS_E_OK;
   };
   if (in.racks && !choose && (rc = rack_pass()) != KAS_E_OK) return rc;
+  // the topic pass: the arrays, then the global counters of its work list
+  if (in.topics) {
+    if (!in.have_tp_tables || (T > 0 && !in.have_tp_topics) || (S > 0 && !in.have_tp_scenarios))
+      return fail(KAS_E_INVALID_ARG, "kas_topic_impact_tables: topics / scenarios == NULL");
+    KasTopicPlan tp;
+    kas_topic_plan_build(b, full.n_max, full.idmap_entries, full.need_bsearch, in.cells16 ? 1 : 0, -1, kas_impact_rows_per_item(b), &tp);
+    hc->tp_region_ints = tp.region_ints;
+    if (!kas_topic_scratch_ok(tp)) return fail(KAS_E_UNSUPPORTED, KAS_TOPIC_SCRATCH_TEXT);
+  }
   // a choice: the spec, then the room for any k scenarios (which ones win is not known before the solve), then the arrays
   if (choose) {
     const char* bad = kas_choose_spec_error_keys(choose, S, in.rack_keys);
@@ -473,6 +492,10 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.racks) {
     by[KAS_HB_RK_RACKS] = sizeof(kas_rack_impact) * (size_t)(hc->rack.rack_off[(size_t)S] + 1);
     by[KAS_HB_RK_SCEN] = sizeof(kas_scenario_rack_impact) * (size_t)(S + 1);
+  }
+  if (in.topics) {
+    by[KAS_HB_TP_TOPICS] = sizeof(kas_topic_impact) * (size_t)(T + 1);
+    by[KAS_HB_TP_SCEN] = sizeof(kas_scenario_topic_impact) * (size_t)(S + 1);
   }
   if (in.front) {
     by[KAS_HB_FR_CLS] = 4 * (size_t)(S + 1);

@@ -86,6 +86,18 @@ struct RunRackImpact {
           single_rack_rows_before = 0, single_rack_rows_after = 0, new_rack_replicas = 0, rows_losing_racks = 0;
 };
 
+// What a run's reassignment does to each topic (the CLI's --print_topic_impact; kas_topic_impact / kas_scenario_topic_impact of
+// include/kas_abi.h).  The CLI solves topic by topic, so every topic's record comes from its own solve and the run's summary
+// is folded from them the way the summary kernel folds a scenario's topics: counts and sums add up, maxima are taken.
+struct TopicImpact {
+  int64_t moved_replicas = 0, moved_partitions = 0;   // kas_topic_result
+  kas_topic_impact record{};
+};
+struct RunTopicImpact {
+  std::vector<std::pair<std::string, TopicImpact>> byTopic;   // in the run's topic order
+  kas_scenario_topic_impact summary{};
+};
+
 // One process-wide device context (a HIP stream on device 0), created on first use.
 inline kas_ctx* deviceContext() {
   static kas_ctx* ctx = nullptr;
@@ -103,7 +115,7 @@ class KafkaAssignmentStrategy {
       const std::string& topicName, const std::map<int, std::vector<int>>& currentAssignment,
       const std::map<int, std::string>& nodeRackAssignment, const std::set<int>& nodes,
       const std::set<int>& partitions, int replicationFactor, Context* context, RunImpact* impact = nullptr,
-      RunRackImpact* rackImpact = nullptr) {
+      RunRackImpact* rackImpact = nullptr, RunTopicImpact* topicImpact = nullptr) {
     const int32_t N = (int32_t)nodes.size();
     std::vector<int32_t> node_id(nodes.begin(), nodes.end());           // ascending (KAS:78)
     std::vector<int32_t> node_rack(N);
@@ -202,18 +214,42 @@ class KafkaAssignmentStrategy {
     kas_rack_tables rt{};
     rt.racks = rack_recs.data(); rt.scenarios = &rack_scen; rt.rack_off = rack_off; rt.racks_cap = (int64_t)rack_names.size();
     const int32_t* rep = N > 0 ? report_rack.data() : nullptr;
+    // with `topicImpact`: ... plus the topic pass (kas_solve_host_topic_impact / 16, with or without the impact records).
+    // Together with `rackImpact` the rack call solves, and the topic records come from a second call that starts from the same
+    // Context counters, writes them to a copy and downloads no rows.
+    kas_topic_impact topic_rec{};
+    kas_scenario_topic_impact topic_scen{};
+    kas_topic_impact_tables tt{};
+    tt.topics = &topic_rec; tt.scenarios = &topic_scen;
+    const bool topicsAlone = topicImpact && !rackImpact;
+    std::vector<int32_t> ctx_before(topicImpact && rackImpact ? ctx : std::vector<int32_t>());
     if (cells16) {
       kas_tables16 t16{};
       t16.cur = cur16.data(); t16.out = out16.data(); t16.aux = t.aux; t16.ctx = t.ctx;
       t16.topic_results = &tr; t16.scenario_results = &sr;
       t16.cur_len = t.cur_len; t16.out_len = t.out_len; t16.aux_len = t.aux_len; t16.ctx_len = t.ctx_len;
-      rc = rackImpact ? kas_solve_host16_rack_impact(deviceContext(), &bd, &t16, nullptr, -1, &it, rep, &rt)
+      rc = topicsAlone ? kas_solve_host16_topic_impact(deviceContext(), &bd, &t16, nullptr, -1, impact ? &it : nullptr, &tt)
+           : rackImpact ? kas_solve_host16_rack_impact(deviceContext(), &bd, &t16, nullptr, -1, &it, rep, &rt)
            : impact   ? kas_solve_host16_impact(deviceContext(), &bd, &t16, nullptr, -1, &it)
                       : kas_solve_host16(deviceContext(), &bd, &t16, nullptr, -1);
+      if (rc == KAS_E_OK && topicImpact && rackImpact) {
+        kas_topic_result tr2{};
+        kas_scenario_result sr2{};
+        t16.ctx = ctx_before.data(); t16.topic_results = &tr2; t16.scenario_results = &sr2;
+        rc = kas_solve_host16_topic_impact(deviceContext(), &bd, &t16, nullptr, 0, nullptr, &tt);
+      }
     } else {
-      rc = rackImpact ? kas_solve_host_rack_impact(deviceContext(), &bd, &t, nullptr, -1, &it, rep, &rt)
+      rc = topicsAlone ? kas_solve_host_topic_impact(deviceContext(), &bd, &t, nullptr, -1, impact ? &it : nullptr, &tt)
+           : rackImpact ? kas_solve_host_rack_impact(deviceContext(), &bd, &t, nullptr, -1, &it, rep, &rt)
            : impact   ? kas_solve_host_impact(deviceContext(), &bd, &t, nullptr, -1, &it)
                       : kas_solve_host(deviceContext(), &bd, &t);
+      if (rc == KAS_E_OK && topicImpact && rackImpact) {
+        kas_topic_result tr2{};
+        kas_scenario_result sr2{};
+        kas_tables t2 = t;
+        t2.ctx = ctx_before.data(); t2.topic_results = &tr2; t2.scenario_results = &sr2;
+        rc = kas_solve_host_topic_impact(deviceContext(), &bd, &t2, nullptr, 0, nullptr, &tt);
+      }
     }
     if (rc != KAS_E_OK) throw SolverError(std::string(kas_strerror(rc)) + ": " + kas_last_error());
 
@@ -262,6 +298,17 @@ class KafkaAssignmentStrategy {
       rackImpact->single_rack_rows_after += rack_scen.single_rack_rows_after;
       rackImpact->new_rack_replicas += rack_scen.new_rack_replicas; rackImpact->rows_losing_racks += rack_scen.rows_losing_racks;
     }
+    if (topicImpact) {
+      TopicImpact ti;
+      ti.moved_replicas = tr.moved_replicas; ti.moved_partitions = tr.moved_partitions; ti.record = topic_rec;
+      topicImpact->byTopic.emplace_back(topicName, ti);
+      int32_t* sum = reinterpret_cast<int32_t*>(&topicImpact->summary);
+      const int32_t* one = reinterpret_cast<const int32_t*>(&topic_scen);
+      for (int w = 0; w < 15; ++w) {                                    // words 0-3, 13 and 14 are sums, the others maxima
+        const bool adds = w < 4 || w >= 13;
+        sum[w] = adds ? sum[w] + one[w] : (one[w] > sum[w] ? one[w] : sum[w]);
+      }
+    }
     std::map<int, std::vector<int>> result;
     {
       int32_t row = 0;
@@ -298,7 +345,8 @@ class KafkaTopicAssigner {
   std::map<int, std::vector<int>> generateAssignment(
       const std::string& topic, const std::map<int, std::vector<int>>& currentAssignment,
       const std::set<int>& brokers, const std::map<int, std::string>& rackAssignment,
-      int desiredReplicationFactor, RunImpact* impact = nullptr, RunRackImpact* rackImpact = nullptr) {
+      int desiredReplicationFactor, RunImpact* impact = nullptr, RunRackImpact* rackImpact = nullptr,
+      RunTopicImpact* topicImpact = nullptr) {
     int replicationFactor = desiredReplicationFactor;                   // KTA:49
     std::set<int> partitions;
     for (auto& e : currentAssignment) {                                 // KTA:50-62
@@ -317,7 +365,8 @@ class KafkaTopicAssigner {
       throw IllegalStateException("Topic " + topic + " has a higher replication factor (" +
                                   std::to_string(replicationFactor) + ") than available brokers!");
     return KafkaAssignmentStrategy::getRackAwareAssignment(topic, currentAssignment, rackAssignment, brokers,
-                                                           partitions, replicationFactor, &assignmentContext, impact, rackImpact);
+                                                           partitions, replicationFactor, &assignmentContext, impact, rackImpact,
+                                                           topicImpact);
   }
 
   Context assignmentContext;

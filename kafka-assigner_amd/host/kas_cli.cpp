@@ -184,11 +184,55 @@ static std::string rackImpactJson(const kas::RunRackImpact& imp) {
   return mjson::dump(doc);
 }
 
+// --print_topic_impact: one JSON document, per topic its record (kas_topic_result's movement counts and kas_topic_impact) and
+// the run's summary (kas_scenario_topic_impact folded over the run's topics)
+static std::string topicImpactJson(const kas::RunTopicImpact& imp) {
+  auto arr = mjson::make(mjson::Value::Array);
+  for (auto& e : imp.byTopic) {
+    const kas_topic_impact& r = e.second.record;
+    auto o = mjson::make(mjson::Value::Object);
+    o->o.emplace_back("topic", mjson::string(e.first));
+    o->o.emplace_back("moved_replicas", mjson::integer(e.second.moved_replicas));
+    o->o.emplace_back("moved_partitions", mjson::integer(e.second.moved_partitions));
+    o->o.emplace_back("departed_replicas", mjson::integer(r.departed_replicas));
+    o->o.emplace_back("leaders_moved", mjson::integer(r.leaders_moved));
+    o->o.emplace_back("max_inbound", mjson::integer(r.max_inbound));
+    o->o.emplace_back("max_outbound", mjson::integer(r.max_outbound));
+    o->o.emplace_back("min_replicas_after", mjson::integer(r.min_replicas_after));
+    o->o.emplace_back("max_replicas_after", mjson::integer(r.max_replicas_after));
+    o->o.emplace_back("min_leaders_after", mjson::integer(r.min_leaders_after));
+    o->o.emplace_back("max_leaders_after", mjson::integer(r.max_leaders_after));
+    arr->a.push_back(o);
+  }
+  const kas_scenario_topic_impact& s = imp.summary;
+  auto sum = mjson::make(mjson::Value::Object);
+  sum->o.emplace_back("topics_ok", mjson::integer(s.topics_ok));
+  sum->o.emplace_back("topics_moved", mjson::integer(s.topics_moved));
+  sum->o.emplace_back("topics_leaders_moved", mjson::integer(s.topics_leaders_moved));
+  sum->o.emplace_back("topics_departed", mjson::integer(s.topics_departed));
+  sum->o.emplace_back("max_topic_moved_replicas", mjson::integer(s.max_topic_moved_replicas));
+  sum->o.emplace_back("max_topic_moved_partitions", mjson::integer(s.max_topic_moved_partitions));
+  sum->o.emplace_back("max_topic_leaders_moved", mjson::integer(s.max_topic_leaders_moved));
+  sum->o.emplace_back("max_topic_inbound", mjson::integer(s.max_topic_inbound));
+  sum->o.emplace_back("max_topic_outbound", mjson::integer(s.max_topic_outbound));
+  sum->o.emplace_back("max_topic_replica_spread", mjson::integer(s.max_topic_replica_spread));
+  sum->o.emplace_back("max_topic_leader_spread", mjson::integer(s.max_topic_leader_spread));
+  sum->o.emplace_back("max_topic_replicas_after", mjson::integer(s.max_topic_replicas_after));
+  sum->o.emplace_back("max_topic_leaders_after", mjson::integer(s.max_topic_leaders_after));
+  sum->o.emplace_back("sum_topic_replica_spread", mjson::integer(s.sum_topic_replica_spread));
+  sum->o.emplace_back("sum_topic_leader_spread", mjson::integer(s.sum_topic_leader_spread));
+  auto doc = mjson::make(mjson::Value::Object);
+  doc->o.emplace_back("topics", arr);
+  doc->o.emplace_back("summary", sum);
+  return mjson::dump(doc);
+}
+
 int main(int argc, char** argv) {
   std::string snapshot, mode, brokerIds, brokerHosts, hostsToRemove, topicsArg;
   bool haveIds = false, haveHosts = false, haveTopics = false, disableRack = false, haveZk = false;
   bool printImpact = false;                  // --print_impact (not the reference's): what the reassignment does to each broker
   bool printRackImpact = false;              // --print_rack_impact (not the reference's): ... and to each rack of the snapshot
+  bool printTopicImpact = false;             // --print_topic_impact (not the reference's): ... and to each topic of the run
   int desiredRf = -1;
   bool bad = false;
   for (int i = 1; i < argc; ++i) {
@@ -206,6 +250,7 @@ int main(int argc, char** argv) {
     else if (a == "--disable_rack_awareness") disableRack = true;
     else if (a == "--print_impact") printImpact = true;
     else if (a == "--print_rack_impact") printRackImpact = true;
+    else if (a == "--print_topic_impact") printTopicImpact = true;
     else bad = true;
   }
   (void)haveZk;
@@ -271,16 +316,19 @@ int main(int argc, char** argv) {
     for (int b : brokers) impact.brokers[b];                             // (every broker of the run, also without topics)
     kas::RunRackImpact rackImpact;                                       // (the snapshot's racks, with or without --disable_rack_awareness)
     for (auto& b : snap.brokers) if (b.has_rack && brokers.count(b.id)) rackImpact.racks[b.id] = b.rack;
+    kas::RunTopicImpact topicImpact;
     for (auto& topic : topics) {                                         // KAG:173-184
       auto it = snap.assignment.find(topic);
       static const std::map<int, std::vector<int>> none;
       finalAssignment[topic] = assigner.generateAssignment(topic, it != snap.assignment.end() ? it->second : none,
                                                            brokers, rackAssignment, desiredRf, printImpact ? &impact : nullptr,
-                                                           printRackImpact ? &rackImpact : nullptr);
+                                                           printRackImpact ? &rackImpact : nullptr,
+                                                           printTopicImpact ? &topicImpact : nullptr);
     }
     std::cout << "NEW ASSIGNMENT:\n" << reassignmentJson(topics, finalAssignment) << std::endl;       // KAG:185-186
     if (printImpact) std::cout << "REASSIGNMENT IMPACT:\n" << impactJson(impact) << std::endl;
     if (printRackImpact) std::cout << "REASSIGNMENT RACK IMPACT:\n" << rackImpactJson(rackImpact) << std::endl;
+    if (printTopicImpact) std::cout << "REASSIGNMENT TOPIC IMPACT:\n" << topicImpactJson(topicImpact) << std::endl;
     return 0;
   } catch (const kas::IllegalStateException& e) {
     fprintf(stderr, "Exception in thread \"main\" java.lang.IllegalStateException: %s\n", e.what());

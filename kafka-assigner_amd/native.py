@@ -36,6 +36,7 @@ SYMBOLS = [
     "kas_rank_device_racks", "kas_front_rank_device_racks", "kas_choose_device_racks", "kas_choose_device16_racks",
     "kas_front_device_racks", "kas_front_device16_racks", "kas_solve_host_choose_racks", "kas_solve_host16_choose_racks",
     "kas_solve_host_front_racks", "kas_solve_host16_front_racks",
+    "kas_topic_impact_device", "kas_topic_impact_device16", "kas_solve_host_topic_impact", "kas_solve_host16_topic_impact",
 ]
 
 _LIB = None
@@ -137,6 +138,13 @@ def load():
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32,
                        C.POINTER(abi.ImpactTables), C.c_void_p, C.POINTER(abi.RackTables)]
+    for fn in (L.kas_topic_impact_device, L.kas_topic_impact_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.TopicImpactTables), C.c_void_p]
+    for fn in (L.kas_solve_host_topic_impact, L.kas_solve_host16_topic_impact):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32,
+                       C.POINTER(abi.ImpactTables), C.POINTER(abi.TopicImpactTables)]
     L.kas_rank_device.restype = C.c_int
     L.kas_rank_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.ChooseSpec), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]
@@ -302,6 +310,15 @@ class Plan:
         imp = abi.ImpactTables(nodes or None, scenarios or None)
         fn = self._lib.kas_impact_device16 if self.cells16 else self._lib.kas_impact_device
         _check(fn(self._h, C.byref(t), C.byref(imp), C.c_void_p(stream) if stream else None))
+
+    def topic_impact_device(self, cur: int, out: int, topic_results: int, topics: int, scenarios: int, aux: int = 0, stream: int = 0):
+        """kas_topic_impact_device / 16: the topic impact of this plan's previous solve, from the tables it used, into the device
+        arrays `topics` (kas_topic_impact [T]) and `scenarios` (kas_scenario_topic_impact [S]).  Raw device pointers (int)."""
+        t = abi.Tables()
+        t.cur = cur or None; t.out = out or None; t.aux = aux or None; t.topic_results = topic_results or None
+        tp = abi.TopicImpactTables(topics or None, scenarios or None)
+        fn = self._lib.kas_topic_impact_device16 if self.cells16 else self._lib.kas_topic_impact_device
+        _check(fn(self._h, C.byref(t), C.byref(tp), C.c_void_p(stream) if stream else None))
 
     def rack_impact_device(self, cur: int, out: int, topic_results: int, nodes: int, scenarios: int, racks: int, racks_cap: int,
                            rack_scenarios: int, report_rack=None, aux: int = 0, stream: int = 0) -> np.ndarray:
@@ -532,6 +549,49 @@ def solve_host_impact(fb: FlatBatch, select=None, cells16: bool = False, ctx: Op
     _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
               -1 if sel is None else int(sel.size), C.byref(imp)))
     return ho, nodes, scen
+
+
+def topic_impact_arrays(fb: FlatBatch):
+    """Zeroed host arrays for the topic pass's records of `fb`: (topics TOPIC_IMPACT_DTYPE [T], scenarios
+    SCENARIO_TOPIC_IMPACT_DTYPE [S])."""
+    return (np.zeros(max(fb.n_topics, 1), dtype=abi.TOPIC_IMPACT_DTYPE)[:fb.n_topics],
+            np.zeros(max(fb.n_scenarios, 1), dtype=abi.SCENARIO_TOPIC_IMPACT_DTYPE)[:fb.n_scenarios])
+
+
+@dataclass
+class TopicReport:
+    """What kas_solve_host_topic_impact returns beside the solve."""
+    topics: np.ndarray                   # TOPIC_IMPACT_DTYPE [T], in descriptor order
+    scenarios: np.ndarray                # SCENARIO_TOPIC_IMPACT_DTYPE [S]
+    nodes: Optional[np.ndarray] = None   # the node impact records, when they were asked for
+    impact: Optional[np.ndarray] = None  # every scenario's kas_scenario_impact, when the impact pass ran
+
+
+def solve_host_topic_impact(fb: FlatBatch, select=None, cells16: bool = False, impact: bool = True, nodes: bool = True,
+                            ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_topic_impact / 16: solve_host_impact plus the topic pass.  impact=False: host_impact == NULL, no impact
+    pass runs; nodes=False: the node records stay on the device (host_impact->nodes == NULL).  select, cells16: as in
+    solve_host_impact.  Returns (HostOutputs, TopicReport)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    out_len = None if sel is None else selected_out_len(fb, sel)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)
+        t, ho = host_tables16(fb, cur16, out_len=out_len)
+    else:
+        t, ho = host_tables(fb, out_len=out_len)
+    n_rec, scen = impact_arrays(fb)
+    imp = abi.ImpactTables(n_rec.ctypes.data if (n_rec.size and nodes) else None, scen.ctypes.data if scen.size else None)
+    topics, tscen = topic_impact_arrays(fb)
+    tp = abi.TopicImpactTables(topics.ctypes.data if topics.size else None, tscen.ctypes.data if tscen.size else None)
+    fn = L.kas_solve_host16_topic_impact if cells16 else L.kas_solve_host_topic_impact
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
+              -1 if sel is None else int(sel.size), C.byref(imp) if impact else None, C.byref(tp)))
+    return ho, TopicReport(topics=topics, scenarios=tscen, nodes=n_rec if (impact and nodes) else None, impact=scen if impact else None)
 
 
 def rack_counts(fb: FlatBatch, report_rack=None) -> np.ndarray:

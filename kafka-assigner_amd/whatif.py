@@ -31,6 +31,11 @@ rack criterion (abi.RACK_KEY_NAMES: the fields above plus rack_replica_spread an
 racks=True — plan.best(variants, by=("colocated_after", "replica_spread")), plan.front(variants, by=("moved_replicas",
 "replica_spread"), within={"single_rack_rows_after": 0}) — and every winner carries the rack figures and rack_impact().
 
+topics=True adds the topic pass (kas_solve_host_topic_impact), with or without impact=True: results[0].topics_moved,
+.max_topic_inbound — the most replicas of one topic a single broker must take in —, .max_topic_replica_spread, ... and
+results[0].topic_impact() -> {topic name: {"status": ..., "moved_replicas": ..., "max_inbound": ..., "min_replicas_after": ...}}.
+best() and front() do not read these figures.
+
 moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for the rows that change instead of every row, compacted
 on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
 results[0].reassignment() -> the Kafka reassignment JSON object of those partitions.  solve(..., moves=...) returns the moves of
@@ -91,6 +96,22 @@ class VariantResult:
     max_rack_replicas_after: Optional[int] = None
     min_rack_leaders_after: Optional[int] = None
     max_rack_leaders_after: Optional[int] = None
+    # topics=True (kas_scenario_topic_impact); None without it
+    topics_ok: Optional[int] = None
+    topics_moved: Optional[int] = None
+    topics_leaders_moved: Optional[int] = None
+    topics_departed: Optional[int] = None
+    max_topic_moved_replicas: Optional[int] = None
+    max_topic_moved_partitions: Optional[int] = None
+    max_topic_leaders_moved: Optional[int] = None
+    max_topic_inbound: Optional[int] = None
+    max_topic_outbound: Optional[int] = None
+    max_topic_replica_spread: Optional[int] = None
+    max_topic_leader_spread: Optional[int] = None
+    max_topic_replicas_after: Optional[int] = None
+    max_topic_leaders_after: Optional[int] = None
+    sum_topic_replica_spread: Optional[int] = None
+    sum_topic_leader_spread: Optional[int] = None
     rank: Optional[int] = None                   # best(): place among the variants that solve (0 = best); None from solve()
     _plan: "WhatIf" = field(repr=False, default=None)
     _index: int = field(repr=False, default=0)
@@ -102,6 +123,8 @@ class VariantResult:
     _moves_mask: int = field(repr=False, default=0)               # ... and the kinds that were asked for
     _racks: np.ndarray = field(repr=False, default=None)          # racks=True: this variant's block of kas_rack_impact records
     _rack_names: Optional[list] = field(repr=False, default=None)  # ... and the name of each rack index
+    _topics: np.ndarray = field(repr=False, default=None)         # topics=True: this variant's kas_topic_impact records
+    _topic_results: np.ndarray = field(repr=False, default=None)  # ... and its kas_topic_result records
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -154,6 +177,19 @@ class VariantResult:
         if self._racks is None:
             raise ValueError("no rack records: solve with impact=True, racks=True")
         return {name: {f: int(r[f]) for f in abi.RACK_IMPACT_FIELDS} for name, r in zip(self._rack_names, self._racks)}
+
+    def topic_impact(self) -> Dict[str, Dict[str, int]]:
+        """topic name -> {status, moved_replicas, moved_partitions, departed_replicas, leaders_moved, max_inbound, max_outbound,
+        min / max_replicas_after, min / max_leaders_after} under this variant (solve(..., topics=True)): the counts over that
+        topic's rows only, max and min over every broker of the variant."""
+        if self._topics is None:
+            raise ValueError("no topic records: solve with topics=True")
+        out = {}
+        for name, tr, r in zip(self._plan.topic_names, self._topic_results, self._topics):
+            rec = {"status": int(tr["status"]), "moved_replicas": int(tr["moved_replicas"]), "moved_partitions": int(tr["moved_partitions"])}
+            rec.update({f: int(r[f]) for f in abi.TOPIC_IMPACT_FIELDS})
+            out[name] = rec
+        return out
 
 
 class Front(list):
@@ -241,7 +277,7 @@ class WhatIf:
 
     # ---- solve ---------------------------------------------------------------------------------
     def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True, moves=None,
-              racks: bool = False) -> List[VariantResult]:
+              racks: bool = False, topics: bool = False) -> List[VariantResult]:
         """Solve every variant in one batch (default: the HIP path through the C ABI).
         impact=True: also the per-broker impact of every variant, computed on the GPU (kas_solve_host_impact).
         rows=False: no variant's rows come back (kas_solve_host_select / kas_solve_host_impact with n_select = 0) — the
@@ -249,10 +285,15 @@ class WhatIf:
         moves=(kinds): the moves of every variant instead of its rows (kas_solve_host_moves: no rows come back whatever `rows`
         says, and the call takes neither impact nor solve_fn); moves() and reassignment() then answer.
         racks=True (needs impact=True): also the rack pass (kas_solve_host_rack_impact) against the real racks (report_racks):
-        colocated_after, single_rack_rows_after, ... and rack_impact() then answer."""
+        colocated_after, single_rack_rows_after, ... and rack_impact() then answer.
+        topics=True (with or without impact, rows and racks; not with moves or solve_fn): also the topic pass
+        (kas_solve_host_topic_impact): topics_moved, max_topic_inbound, max_topic_replica_spread, ... and topic_impact() then
+        answer.  Together with racks=True the topic records come from a second host call that downloads no rows."""
         from . import native
         fb = self.flat_batch(variants)
-        nodes = scen_imp = ml = rk = rack_names = None
+        nodes = scen_imp = ml = rk = rack_names = tp = None
+        if topics and (moves is not None or solve_fn is not None):
+            raise ValueError("topics=True takes the library's own host call, without moves (no solve_fn)")
         if racks and (not impact or moves is not None):
             raise ValueError("racks=True is a pass behind the impact pass: solve(..., impact=True, racks=True), without moves")
         if moves is not None:
@@ -267,8 +308,15 @@ class WhatIf:
                 table, rack_names = self.report_racks(variants)
                 ho, rk = native.solve_host_rack_impact(fb, report_rack=table, select=None if rows else [])
                 nodes, scen_imp = rk.nodes, rk.impact
+                if topics:
+                    _, tp = native.solve_host_topic_impact(fb, select=[], impact=False)
+            elif topics:
+                ho, tp = native.solve_host_topic_impact(fb, select=None if rows else [])
+                nodes, scen_imp = tp.nodes, tp.impact
             else:
                 ho, nodes, scen_imp = native.solve_host_impact(fb, select=None if rows else [])
+        elif topics:
+            ho, tp = native.solve_host_topic_impact(fb, select=None if rows else [], impact=False)
         elif not rows:
             if solve_fn is not None:
                 raise ValueError("rows=False takes the library's own host call (no solve_fn)")
@@ -289,6 +337,10 @@ class WhatIf:
             if rk is not None:
                 extra.update({f: int(rk.scenarios[f][s]) for f in abi.SCENARIO_RACK_FIELDS})
                 extra.update(_racks=rk.of(s), _rack_names=rack_names[s])
+            if tp is not None:
+                tb, tc = int(fb.scen["topic_begin"][s]), int(fb.scen["topic_count"][s])
+                extra.update({f: int(tp.scenarios[f][s]) for f in abi.SCENARIO_TOPIC_FIELDS})
+                extra.update(_topics=tp.topics[tb:tb + tc], _topic_results=ho.topic_results[tb:tb + tc])
             if ml is not None:
                 extra.update(_moves=ml.of(s), _moves_mask=ml.mask)
             res.append(VariantResult(label=v.label, status=int(sr["status"]),
