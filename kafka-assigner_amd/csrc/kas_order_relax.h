@@ -196,6 +196,10 @@ KAS_DEV RelaxTags relax_tags_sorted(const RelaxTopic& t) {
 #ifndef KAS_M32_SORTED_TAGS
 #define KAS_M32_SORTED_TAGS(M32) (M32)
 #endif
+// (tuning builds: 0 = the final lists of dword mid rows through the 16-bit row layout and v_perm_b32, as in round 6)
+#ifndef KAS_RELAX_PICK_FIELDS
+#define KAS_RELAX_PICK_FIELDS 1
+#endif
 // The picks of a row with three holders: first pick | second pick << 2 (cell indices).
 KAS_DEV int32_t relax_eval3(const uint32_t (&x)[3], const RelaxTags& g) {
   // first pick: count[.][0], first strictly smaller in visit order == minimum of (count, visit position)
@@ -224,6 +228,31 @@ KAS_DEV void relax_list3(const Raw& raw, int32_t oc, uint32_t (&l)[3], uint32_t*
   l[1] = kasw::perm_bytes(raw.w[1], raw.w[0], 0x0c0c0100u + w1 * 0x0202u);
   l[2] = kasw::perm_bytes(raw.w[1], raw.w[0], 0x0c0c0100u + w2 * 0x0202u);
   if (cnt2) kasw::lds_add_u32(cnt2 + l[2], 1u);
+}
+
+// ... of a row on dword mid rows (round 7): its cells come as three fields (mid32_fields), so list position r takes v[w_r] by
+// selects and the last position what is left — v[0] ^ v[1] ^ v[2] ^ l[0] ^ l[1] — with no 16-bit row packed for v_perm_b32.
+// v: the row's cells (node indices) — or anything looked up by them: experiments/order_ids_read_at_top_of_tile.patch hands in
+// the cells' broker ids.
+// (m ? a : b) bit by bit — v_bfi_b32, spelled out: from `w == 1 ? .. : ..`, and from the same in plain bit operations, the compiler
+// makes compares and selects through the condition register (two instructions and a wait state each), or branches around values
+// whose LDS reads are still on their way
+KAS_DEV uint32_t relax_bits_select(uint32_t m, uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t r;
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+  return r;
+#else
+  return (a & m) | (b & ~m);
+#endif
+}
+KAS_DEV void relax_pick3(const uint32_t (&v)[3], int32_t oc, uint32_t (&l)[3]) {
+  // a cell index is 0, 1 or 2: bit 0 says "1", bit 1 says "2" — each bit spread over a word (v_bfe_i32)
+  const uint32_t m01 = (uint32_t)((int32_t)((uint32_t)oc << 31) >> 31), m02 = (uint32_t)((int32_t)((uint32_t)oc << 30) >> 31);   // w0 == 1, w0 == 2
+  const uint32_t m11 = (uint32_t)((int32_t)((uint32_t)oc << 29) >> 31), m12 = (uint32_t)((int32_t)((uint32_t)oc << 28) >> 31);   // w1 == 1, w1 == 2
+  l[0] = relax_bits_select(m02, v[2], relax_bits_select(m01, v[1], v[0]));
+  l[1] = relax_bits_select(m12, v[2], relax_bits_select(m11, v[1], v[0]));
+  l[2] = v[0] ^ v[1] ^ v[2] ^ l[0] ^ l[1];
 }
 
 // final rows on their way: the broker ids of NB rows per lane (rows p, p + 64), asked for (kasw::gload_u32_async) and
@@ -561,10 +590,13 @@ KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, 
         const int32_t p = (tile << 6) + lane;
         const bool active = p < P;
         // ---- cells of my row (row lane): node index or KAS_MID_NONE (0xffff, bit 15)
-        // (M32: the rows' dwords taken apart here, into the layout of the 16-bit rows — mid_view)
+        // (M32, rows of the batch's width: the dword's three fields as they come — mid32_fields; narrower rows go through the
+        //  layout of the 16-bit rows, mid_view, which masks the cells a row does not have)
         const MidRaw<W> ra = mid_view<W, FULLW, M32>(raw[0], ow);
         uint32_t c[3];
-        if constexpr (FULLW) {
+        if constexpr (M32 && FULLW) {
+          mid32_fields(raw[0].w[0], c);
+        } else if constexpr (FULLW) {
           c[0] = ra.w[0] & 0xffffu; c[1] = ra.w[0] >> 16; c[2] = W == 3 ? (ra.w[1] & 0xffffu) : KAS_MID_NONE;
         } else {
 #pragma unroll
@@ -593,7 +625,8 @@ KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, 
 #pragma unroll
           for (int b = 1; b < NR; ++b) {
             rv[b] = mid_view<W, FULLW, M32>(raw[b], ow);
-            cc[b][0] = rv[b].w[0] & 0xffffu; cc[b][1] = rv[b].w[0] >> 16; cc[b][2] = rv[b].w[1] & 0xffffu;
+            if constexpr (M32) mid32_fields(raw[b].w[0], cc[b]);
+            else { cc[b][0] = rv[b].w[0] & 0xffffu; cc[b][1] = rv[b].w[0] >> 16; cc[b][2] = rv[b].w[1] & 0xffffu; }
             short_row = short_row || (M32 ? cc[b][2] >= NONE_FROM : ((cc[b][0] | cc[b][1] | cc[b][2]) & 0x8000u) != 0u);
           }
           if constexpr (NR > 1) {
@@ -662,7 +695,11 @@ KAS_DEV void order_relax(const KasLaunch& a, int32_t s, unsigned char* lds_raw, 
           }
           // ---- the final rows: their lists as node indices now, broker ids and the stores one step later
 #pragma unroll
-          for (int b = 0; b < NR; ++b) relax_list3(rv[b], prev[b] < 0 ? 4 : prev[b], req_l[b], cnt2);
+          for (int b = 0; b < NR; ++b) {
+            const int32_t ocf = prev[b] < 0 ? 4 : prev[b];
+            if constexpr (M32 && KAS_RELAX_PICK_FIELDS) relax_pick3(cc[b], ocf, req_l[b]);
+            else relax_list3(rv[b], ocf, req_l[b], cnt2);
+          }
           req_n = NR;
           step = NR;
           return true;

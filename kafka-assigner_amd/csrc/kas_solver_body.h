@@ -652,16 +652,32 @@ KAS_DEV void for_tile_batches(const TopicView& T, int32_t tile0, int32_t stride,
 // P3 for one row per lane (KAS:133-160): holders of the row from its accepted replicas, orphan
 // count, movement bookkeeping and the out row (node indices for now).
 // ---------------------------------------------------------------------------------------------
-template <int W>
+#ifndef KAS_P3_SORTED_OUT
+#define KAS_P3_SORTED_OUT 1                                 // (tuning builds: 0 = the slim fill's pass B with the general p3_rows)
+#endif
+// SORTED_OUT (round 7): the caller knows at compile time that the row goes out as a dword mid row (T.m32, lists 3 wide), whose
+// dword depends only on the SET of holders (mid32_pack sorts them): hold[r] is the accepted replica's node or -1 where it stands,
+// nothing is compacted into acceptance order, hc is a population count and hrack — which only the general fill's ring reads — is
+// not produced.
+// DISTINCT (round 7): the caller is pass B of the rack-diverse form — pass A has proved that the row's known brokers sit on
+// pairwise different racks, so no two of them are equal, and an unknown broker is never accepted: a replica that was not accepted
+// has no accepted twin, and the W x W comparison of broker ids comes to "kept_else == accbits".
+template <int W, bool SORTED_OUT = false, bool DISTINCT = false>
 KAS_DEV void p3_rows(const LdsView& L, const TopicView& T, int32_t p, int32_t len,
                      const int32_t (&ids)[W], const int32_t (&idx)[W], uint32_t accbits,
                      int32_t& need, int32_t& hc, int32_t (&hrack)[W], int32_t& moved_r,
                      int32_t& moved_p, const int32_t* racks = nullptr, bool inplace = false) {
+  static_assert(!SORTED_OUT || W == 3, "dword mid rows: lists 3 wide");
   const bool active = p < T.P;
   int32_t hold[W];
 #pragma unroll
   for (int k = 0; k < W; ++k) { hold[k] = -1; hrack[k] = -1; }
   hc = 0;
+  if constexpr (SORTED_OUT) {
+#pragma unroll
+    for (int r = 0; r < W; ++r) hold[r] = ((accbits >> r) & 1u) ? (idx[r] >= 0 ? idx[r] : 0) : -1;
+    hc = kasw::popc((uint64_t)(accbits & ((1u << W) - 1u)));
+  } else {
 #pragma unroll
   for (int r = 0; r < W; ++r) {
     const bool acc = (accbits >> r) & 1u;
@@ -675,6 +691,7 @@ KAS_DEV void p3_rows(const LdsView& L, const TopicView& T, int32_t p, int32_t le
     }
     hc += acc ? 1 : 0;
   }
+  }
   const bool in_parts = active && (T.inp_arr ? T.inp_arr[p] != 0 : true);
   need = in_parts ? (T.rf - hc > 0 ? T.rf - hc : 0) : 0;   // KAS:151-157
 #if defined(KAS_TUNE_NO_ORPHANS)                            // (tuning builds, WRONG results: what would the job run at if P4 cost the fill nothing?
@@ -686,7 +703,7 @@ KAS_DEV void p3_rows(const LdsView& L, const TopicView& T, int32_t p, int32_t le
 #endif
   // inplace (index rows, fill_pass_a_fused<EMIT>): the row's cells already lie where its mid row goes — a row that keeps every
   // one of them, in order, is not stored again (KAS_IXROWS_SKIP_SAME=0: tuning builds store every row)
-  bool same = inplace && KAS_IXROWS_SKIP_SAME;
+  bool same = !SORTED_OUT && inplace && KAS_IXROWS_SKIP_SAME;  // (SORTED_OUT: not for index rows, whose cells keep their order)
 #pragma unroll
   for (int k = 0; k < W; ++k) same = same && hold[k] == idx[k];
 #if defined(KAS_TUNE_NO_MID_STORES)                          // (tuning builds: how much of the fill's time is its 8-byte row stores)
@@ -694,7 +711,7 @@ KAS_DEV void p3_rows(const LdsView& L, const TopicView& T, int32_t p, int32_t le
 #else
   if (active && !same) {
 #endif
-    if (W == 3 && T.m32) {                                  // wave-uniform: the row's holders sorted, in one dword
+    if (SORTED_OUT || (W == 3 && T.m32)) {                  // wave-uniform: the row's holders sorted, in one dword
       if constexpr (W == 3) reinterpret_cast<uint32_t*>(T.mid)[p] = mid32_pack(hold[0], hold[1], hold[2]);
     } else if (T.ow == W) {                                 // wave-uniform: the mid row as W / 2 dwords (+ a halfword)
       uint16_t* row = T.mid + (int64_t)p * mid_width_of<W>();
@@ -710,11 +727,15 @@ KAS_DEV void p3_rows(const LdsView& L, const TopicView& T, int32_t p, int32_t le
   }
   // a distinct current broker that was not kept => set(new) != set(cur)
   uint32_t kept_else = 0;
+  if constexpr (DISTINCT) {
+    kept_else = accbits;
+  } else {
 #pragma unroll
   for (int r = 0; r < W; ++r)
 #pragma unroll
     for (int r2 = 0; r2 < W; ++r2)
       kept_else |= (((accbits >> r2) & 1u) != 0u && ids[r2] == ids[r]) ? (1u << r) : 0u;
+  }
   const uint32_t present = len >= W ? ((1u << W) - 1u) : ((1u << len) - 1u);
   const bool dropped = (present & ~accbits & ~kept_else) != 0u;
   moved_r += need;
@@ -1089,7 +1110,8 @@ KAS_DEV void fill_chunk_prefix(const LdsView& L, const TopicView& T, int32_t tid
 // (kas_wave.h, lds_add_rtn_u32; the launcher sets KAS_FLAG_LANE_ORDER where kas_ctx_create's self-test saw that order):
 // what comes back is the quota left for exactly this row, no read before, no read after, no ranking of a tile in
 // which a quota runs out.
-template <int W, bool DIRECT, int QS, bool RTN = false, bool INPLACE = false>
+// SORTED: the rows go out as dword mid rows, known at compile time (p3_rows' SORTED_OUT and DISTINCT forms)
+template <int W, bool DIRECT, int QS, bool RTN = false, bool INPLACE = false, bool SORTED = false>
 KAS_DEV int32_t fill_pass_b_range(const LdsView& L, const TopicView& T, const NodeMap& nm, int32_t t0, int32_t t1,
                                   int32_t* qc, int32_t& moved_r, int32_t& moved_p, int64_t (&st)[8]) {
   const int lane = kasw::lane();
@@ -1166,20 +1188,20 @@ KAS_DEV int32_t fill_pass_b_range(const LdsView& L, const TopicView& T, const No
       }
     }
     int32_t need, hc, hrack[W];
-    p3_rows<W>(L, T, p, len, ids, idx, accbits, need, hc, hrack, moved_r, moved_p, nullptr, INPLACE);
+    p3_rows<W, SORTED, SORTED>(L, T, p, len, ids, idx, accbits, need, hc, hrack, moved_r, moved_p, nullptr, INPLACE);
     const uint64_t om = kasw::ballot(need > 0);
     if (need > 0) olist[ocount + kasw::count_below(om)] = p;
     ocount += kasw::popc(om);
   });
   return ocount;
 }
-template <int W, int NW, bool DIRECT, bool FUSED = false, bool RTN = false, bool INPLACE = false>
+template <int W, int NW, bool DIRECT, bool FUSED = false, bool RTN = false, bool INPLACE = false, bool SORTED = false>
 KAS_DEV int32_t fill_pass_b(const LdsView& L, const TopicView& T, const NodeMap& nm, int32_t wave,
                             int32_t& moved_r, int32_t& moved_p, int64_t (&st)[8]) {
   const int32_t t0 = chunk_begin<NW>(T.nt, wave), t1 = chunk_begin<NW>(T.nt, wave + 1);
   constexpr int QS = FUSED ? fused_block_words<W, NW>() : 1;     // stride of a node's quota word
   int32_t* qc = FUSED ? L.x + wave : L.x + wave * T.N;
-  return fill_pass_b_range<W, DIRECT, QS, RTN, INPLACE>(L, T, nm, t0, t1, qc, moved_r, moved_p, st);
+  return fill_pass_b_range<W, DIRECT, QS, RTN, INPLACE, SORTED>(L, T, nm, t0, t1, qc, moved_r, moved_p, st);
 }
 
 // ---- what the fill kernel, first fit (kas_first_fit.h) and the spread fill derive and write the same way ----
@@ -1460,7 +1482,8 @@ KAS_DEV TopicOutcome fill_topic(const KasLaunch& a, const kas_topic_desc& td, co
     phase_tick(st, 1, tmark);
     pack_idmap_with_rstar<NT, true>(L, N, g_node_id, nm.min_id);
     int32_t moved_r = 0, moved_p = 0;
-    const int32_t oc = fill_pass_b<W, NW, true, true, true>(L, T, nm, wave, moved_r, moved_p, st);
+    // (dword mid rows, known at compile time: the rows' holders go out as a set — p3_rows' SORTED_OUT and DISTINCT forms)
+    const int32_t oc = fill_pass_b<W, NW, true, true, true, false, W == 3 && M32C == 1 && KAS_P3_SORTED_OUT>(L, T, nm, wave, moved_r, moved_p, st);
     if (lane == 0) L.ctl[KAS_CTL_OC + wave] = oc;
     kasw::sync();
     phase_tick(st, 2, tmark);

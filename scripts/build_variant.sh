@@ -1,7 +1,8 @@
 #!/bin/bash
 # scripts/build_variant.sh NAME [PATCH ...] [-- extra hipcc flags]
 # Tuning build of the C-ABI library: copies kafka-assigner_amd/csrc to a scratch directory, applies
-# the given patches (-p0 paths as in experiments/*.patch), compiles only the kernels BASELINE
+# the given patches (-p0 paths as in experiments/*.patch), compiles every source of the library (kafka_assigner_amd/build.py,
+# SOURCES) with only the solve kernels BASELINE
 # configs[2] launches (KAS_MINIMAL_INSTANCES: seconds instead of minutes; pass
 # -DKAS_MINIMAL_INSTANCES=5 among the extra flags for the configs[4] kernels instead) into
 # variants/libkas_hip_NAME.so.  Select it with KAS_HIP_LIB=variants/libkas_hip_NAME.so.
@@ -23,6 +24,8 @@ rm -f "$W"/kafka-assigner_amd/csrc/*.so
 for p in "${PATCHES[@]}"; do (cd "$W" && patch -p0 -s < "$ROOT/$p"); done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -fvisibility=hidden \
   $MIN "${FLAGS[@]}" -I"$ROOT/include" -I"$W/kafka-assigner_amd/csrc" \
-  -o "$ROOT/variants/libkas_hip_$NAME.so" "$W/kafka-assigner_amd/csrc/kas_hip.hip"
+  -o "$ROOT/variants/libkas_hip_$NAME.so" "$W"/kafka-assigner_amd/csrc/kas_hip.hip "$W"/kafka-assigner_amd/csrc/kas_impact.hip \
+  "$W"/kafka-assigner_amd/csrc/kas_choose.hip "$W"/kafka-assigner_amd/csrc/kas_moves.hip "$W"/kafka-assigner_amd/csrc/kas_racks.hip \
+  "$W"/kafka-assigner_amd/csrc/kas_topics.hip
 rm -rf "$W"
 echo "variants/libkas_hip_$NAME.so"

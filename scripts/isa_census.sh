@@ -1,10 +1,12 @@
 #!/bin/bash
-# scripts/isa_census.sh: profiles/r06_isa_census_*.txt of the two kernels the headline launches, from the sources as they are
+# scripts/isa_census.sh: profiles/r07_isa_census_*.txt (CENSUS_TAG, default r07; CENSUS_OUT: another directory) of the two kernels the headline launches, from the sources as they are
 # (hipcc -S cross-compiles without a GPU; seconds): the slim fill kernel alone in a translation unit of its own, the relaxation
 # instances from tests/asm/relax_instances.hip.  MEASUREMENT TOOLING (tools/isa_stats.py, tools/isa_loops.py), not a product path.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 W=$(mktemp -d /tmp/kascensus.XXXXXX)
+OUT=${CENSUS_OUT:-$ROOT/profiles}; TAG=${CENSUS_TAG:-r07}
+mkdir -p "$OUT"
 SHA=$(cd "$ROOT" && python -c "import bench; print(bench.sources_sha16())")
 HIPCC="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -I$ROOT/include -I$ROOT/kafka-assigner_amd/csrc"
 cat > $W/slim.hip <<'SRC'
@@ -34,7 +36,7 @@ echo "# ds_read_u16 (id -> index) / ds_read_i16 (rack) / ds_add_u32 (per-chunk h
 echo "# global_store_dword (the dword mid row: v_med3_u32 / v_min3_u32 in front of it sort the holders); the blocks with ds_write_b16 / ds_write2_b32 in front are the node tables going into the LDS."
 python $ROOT/tools/isa_stats.py $W/slim.s kas_fill_slim | head -1
 python $ROOT/tools/isa_loops.py $W/slim.s kas_fill_slim 2
-} > $ROOT/profiles/r06_isa_census_fill_slim_kernel_3.txt
+} > $OUT/${TAG}_isa_census_fill_slim_kernel_3.txt
 K=_Z22kas_order_relax_kernelILi3ELb0ELb0ELb0ELb0ELb1ELb1ELb0EEv9KasLaunch
 {
 echo "# ISA census of kas_order_relax_kernel<3, DUAL=false, CTX=false, VERIFY=false, C16=false, IDL=true, M32=true> - the headline's order kernel (int32 cells, ids in the LDS, tiles of 64 rows, dword mid rows);"
@@ -43,6 +45,6 @@ echo "# The fast path (64 rows of three holders) = the block with 1 x global_loa
 echo "# the slow path (rows with fewer than three holders) is the pair with v_min_u32 clamps and the rank computation."
 python $ROOT/tools/isa_stats.py $W/relax.s $K --blocks
 python $ROOT/tools/isa_loops.py $W/relax.s $K 2
-} > $ROOT/profiles/r06_isa_census_order_relax_3_idl.txt
+} > $OUT/${TAG}_isa_census_order_relax_3_idl.txt
 rm -rf $W
 echo "census for sources $SHA"
