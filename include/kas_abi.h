@@ -758,8 +758,8 @@ int kas_solve_host16_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, cons
  * node" are exactly those of kas_node_impact above.  The scenario-level spread hides what happens inside a topic (two topics
  * skewed in opposite directions sum to a flat cluster), and the reference bounds only a topic's maximum per broker, never the
  * minimum, and the leaders not at all.
- * Ranking or fronting by these figures is not part of this pass.  The scenario record is laid out (sixteen non-negative int32)
- * so that its words can become criteria. */
+ * Ranking or fronting by these figures is not part of this pass: the scenario record is laid out (sixteen non-negative int32)
+ * so that its words are criteria of the *_topics entries below (KAS_KEY_TOPIC_BASE). */
 #define KAS_TOPIC_SCRATCH_LIMIT (256ll << 20)   /* bytes of global counters one topic pass may need (see the refusals below) */
 
 /* One per topic descriptor of the batch, in descriptor order: the fields of kas_scenario_impact, with the same meanings, taken
@@ -828,6 +828,90 @@ int kas_solve_host_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, const
 int kas_solve_host16_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
                                   const int32_t* select, int32_t n_select, const kas_impact_tables* host_impact,
                                   const kas_topic_impact_tables* host_topics);
+
+/* ---- ranking and fronting by topic criteria (added under ABI v6: purely additive) -------------------------------------
+ * A *topic criterion* is a non-negative int32 taken from a scenario's kas_scenario_topic_impact: key KAS_KEY_TOPIC_BASE + i,
+ * i = 0..14, is int32 word i of the record (word 15, `reserved`, is no criterion, and there are no derived keys: the record
+ * holds the spreads).  kas_choose_spec and kas_front_spec take these keys as they take the others (key[], limit_key[]), in
+ * any mix with the broker and the rack criteria, but only in the *_topics entries below: the plain entries keep refusing a
+ * key >= KAS_KEY_COUNT and the *_racks entries a key >= KAS_KEY_RACK_END as an unknown criterion, and keys 10..15 and 33..47
+ * are unknown everywhere. */
+#define KAS_KEY_TOPIC_BASE                  48
+#define KAS_KEY_TOPICS_OK                   48  /* kas_scenario_topic_impact.topics_ok                       */
+#define KAS_KEY_TOPICS_MOVED                49  /* .topics_moved                                             */
+#define KAS_KEY_TOPICS_LEADERS_MOVED        50  /* .topics_leaders_moved                                     */
+#define KAS_KEY_TOPICS_DEPARTED             51  /* .topics_departed                                          */
+#define KAS_KEY_MAX_TOPIC_MOVED_REPLICAS    52  /* .max_topic_moved_replicas                                 */
+#define KAS_KEY_MAX_TOPIC_MOVED_PARTITIONS  53  /* .max_topic_moved_partitions                               */
+#define KAS_KEY_MAX_TOPIC_LEADERS_MOVED     54  /* .max_topic_leaders_moved                                  */
+#define KAS_KEY_MAX_TOPIC_INBOUND           55  /* .max_topic_inbound                                        */
+#define KAS_KEY_MAX_TOPIC_OUTBOUND          56  /* .max_topic_outbound                                       */
+#define KAS_KEY_MAX_TOPIC_REPLICA_SPREAD    57  /* .max_topic_replica_spread                                 */
+#define KAS_KEY_MAX_TOPIC_LEADER_SPREAD     58  /* .max_topic_leader_spread                                  */
+#define KAS_KEY_MAX_TOPIC_REPLICAS_AFTER    59  /* .max_topic_replicas_after                                 */
+#define KAS_KEY_MAX_TOPIC_LEADERS_AFTER     60  /* .max_topic_leaders_after                                  */
+#define KAS_KEY_SUM_TOPIC_REPLICA_SPREAD    61  /* .sum_topic_replica_spread                                 */
+#define KAS_KEY_SUM_TOPIC_LEADER_SPREAD     62  /* .sum_topic_leader_spread                                  */
+#define KAS_KEY_TOPIC_END                   63
+
+/* Every entry below is its *_racks parent (the same name with _racks for _topics) with one more source of criteria, and
+ * orders, ties, classes, offsets and determinism are the parent's.  A spec that names no topic criterion gives, with or
+ * without topic records, the bytes the *_racks entry gives.  Refused with KAS_E_INVALID_ARG before any GPU work, in this
+ * order: the spec refusals of the parent entry, with the same texts (a key is known when it is below KAS_KEY_COUNT, in
+ * KAS_KEY_RACK_BASE .. KAS_KEY_RACK_END - 1 or in KAS_KEY_TOPIC_BASE .. KAS_KEY_TOPIC_END - 1); "rack criterion without rack
+ * records"; "topic criterion without topic records" when a key or a limit key is a topic criterion and the topic records are
+ * NULL; then everything the *_racks entry refuses, in its order; then, in the host entries, the topic refusals of
+ * kas_solve_host_topic_impact, in its order (KAS_E_UNSUPPORTED for the scratch limit among them).
+ *
+ * kas_rank_device_topics / kas_front_rank_device_topics: the *_racks entries plus topic_scenarios[S], a device array complete
+ * on the stream.  Either of rack_scenarios and topic_scenarios may be NULL: no criterion of that set may then be named. */
+int kas_rank_device_topics(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                           const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                           int32_t n_scenarios, const kas_choose_spec* spec, int32_t* rank, int32_t* chosen, int32_t* n_ok,
+                           void* hip_stream);
+int kas_front_rank_device_topics(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                                 const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                                 int32_t n_scenarios, const kas_front_spec* spec, int32_t* rank, int32_t* chosen, int32_t* counts,
+                                 int32_t* scratch, void* hip_stream);
+
+/* kas_choose_device_racks / 16 and kas_front_device_racks / 16 plus topic_scenarios: the DEVICE array of scenario topic
+ * records that the plan's topic pass (kas_topic_impact_device / 16: device_out->scenarios) wrote for the plan's previous
+ * solve.  A choice that names a topic criterion is ordered behind that pass (which records an event of its own) as well as
+ * behind the impact pass, and a later topic pass or solve of the plan waits for the choice; the gather is the parent's. */
+int kas_choose_device_topics(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                             const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                             const kas_choose_spec* spec, const kas_choice* device_choice, void* hip_stream);
+int kas_choose_device16_topics(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                               const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                               const kas_choose_spec* spec, const kas_choice* device_choice, void* hip_stream);
+int kas_front_device_topics(kas_plan* plan, const kas_tables* device_tables, const kas_impact_tables* device_impact,
+                            const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                            const kas_front_spec* spec, const kas_choice* device_choice, int32_t* counts, void* hip_stream);
+int kas_front_device16_topics(kas_plan* plan, const kas_tables16* device_tables, const kas_impact_tables* device_impact,
+                              const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                              const kas_front_spec* spec, const kas_choice* device_choice, int32_t* counts, void* hip_stream);
+
+/* kas_solve_host_choose_racks / 16 and kas_solve_host_front_racks / 16 plus the topic pass of kas_solve_host_topic_impact on
+ * each scenario range's stream, behind its solve; the ranking or the front waits for every range's passes.  ALL topic records
+ * and scenario topic records come back in host_topics as from kas_solve_host_topic_impact.  host_topics == NULL: no topic
+ * pass, and no topic criterion may be named; host_racks == NULL: no rack pass, and no rack criterion may be named.  The two
+ * are independent. */
+int kas_solve_host_choose_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                                 const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
+                                 const kas_moves* host_moves, const int32_t* report_rack, const kas_rack_tables* host_racks,
+                                 const kas_topic_impact_tables* host_topics);
+int kas_solve_host16_choose_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                   const kas_choose_spec* spec, const kas_choice* host_choice, const kas_impact_tables* host_impact,
+                                   const kas_moves* host_moves, const int32_t* report_rack, const kas_rack_tables* host_racks,
+                                   const kas_topic_impact_tables* host_topics);
+int kas_solve_host_front_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables,
+                                const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
+                                const kas_impact_tables* host_impact, const kas_moves* host_moves, const int32_t* report_rack,
+                                const kas_rack_tables* host_racks, const kas_topic_impact_tables* host_topics);
+int kas_solve_host16_front_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables,
+                                  const kas_front_spec* spec, const kas_choice* host_choice, int32_t* counts,
+                                  const kas_impact_tables* host_impact, const kas_moves* host_moves, const int32_t* report_rack,
+                                  const kas_rack_tables* host_racks, const kas_topic_impact_tables* host_topics);
 
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */

@@ -341,6 +341,61 @@ def rack_front_spec(by, within=None, k: int = 0) -> "FrontSpec":
     return spec
 
 
+# topic criteria of the *_topics entries: key KAS_KEY_TOPIC_BASE + i is int32 word i of kas_scenario_topic_impact (no derived keys)
+KAS_KEY_TOPIC_BASE = 48
+TOPIC_KEY_NAMES = SCENARIO_TOPIC_FIELDS
+TOPIC_KEYS = {name: KAS_KEY_TOPIC_BASE + i for i, name in enumerate(TOPIC_KEY_NAMES)}
+KAS_KEY_TOPIC_END = KAS_KEY_TOPIC_BASE + len(TOPIC_KEY_NAMES)
+TOPIC_CHOOSE_ENTRIES = ("kas_rank_device_topics", "kas_front_rank_device_topics", "kas_choose_device_topics", "kas_choose_device16_topics",
+                        "kas_front_device_topics", "kas_front_device16_topics", "kas_solve_host_choose_topics",
+                        "kas_solve_host16_choose_topics", "kas_solve_host_front_topics", "kas_solve_host16_front_topics")
+assert KAS_KEY_TOPIC_END == 63 and not (set(KEYS) | set(RACK_KEYS)) & set(TOPIC_KEYS)
+
+
+def is_topic_key(name) -> bool:
+    """is `name` (a criterion name or a KAS_KEY_* number) a topic criterion"""
+    return name in TOPIC_KEYS if isinstance(name, str) else KAS_KEY_TOPIC_BASE <= int(name) < KAS_KEY_TOPIC_END
+
+
+def topic_key_id(name) -> int:
+    """KAS_KEY_* of a criterion name of any of the three sets (KEY_NAMES, RACK_KEY_NAMES, TOPIC_KEY_NAMES), or the number itself;
+    unknown names raise ValueError listing the three sets."""
+    if isinstance(name, str):
+        for keys in (KEYS, RACK_KEYS, TOPIC_KEYS):
+            if name in keys:
+                return keys[name]
+        raise ValueError("unknown criterion %r (one of %s; rack criteria: %s; topic criteria: %s)" %
+                         (name, ", ".join(KEY_NAMES), ", ".join(RACK_KEY_NAMES), ", ".join(TOPIC_KEY_NAMES)))
+    return int(name)
+
+
+def topic_choose_spec(keys, k: int) -> "ChooseSpec":
+    """kas_choose_spec for the *_topics entries: names of the three sets (or KAS_KEY_* numbers), in any mix."""
+    ids = [topic_key_id(n) for n in ([keys] if isinstance(keys, (str, int)) else list(keys))]
+    spec = ChooseSpec()
+    spec.n_keys = len(ids)
+    for i, v in enumerate(ids[:KAS_CHOOSE_MAX_KEYS]):
+        spec.key[i] = v
+    spec.k = int(k)
+    return spec
+
+
+def topic_front_spec(by, within=None, k: int = 0) -> "FrontSpec":
+    """kas_front_spec for the *_topics entries: front_spec with the three name sets, among the criteria and among the bounds."""
+    ids = [topic_key_id(n) for n in ([by] if isinstance(by, (str, int)) else list(by))]
+    pairs = list(within.items()) if isinstance(within, dict) else list(within or ())
+    spec = FrontSpec()
+    spec.n_keys = len(ids)
+    for i, v in enumerate(ids[:KAS_CHOOSE_MAX_KEYS]):
+        spec.key[i] = v
+    spec.n_limits = len(pairs)
+    for i, (name, limit) in enumerate(pairs[:KAS_CHOOSE_MAX_KEYS]):
+        spec.limit_key[i] = topic_key_id(name)
+        spec.limit[i] = int(limit)
+    spec.k = int(k)
+    return spec
+
+
 # the move list (kas_move / kas_moves): a row's flags, the 16-byte record, where a list goes
 KAS_MOVE_REPLICAS, KAS_MOVE_LEADER, KAS_MOVE_ORDER = 1, 2, 4
 MOVE_KINDS = {"replicas": KAS_MOVE_REPLICAS, "leader": KAS_MOVE_LEADER, "order": KAS_MOVE_ORDER}

@@ -3,8 +3,9 @@
 //
 // Pure C++ (no HIP calls), so that the same tables are built in the library and in the CPU emulation under tests/emu/.
 //
-// Two kernels behind a solve and its impact pass (the rank kernel in two instances: the second also reads the scenario rack
-// records of a rack pass, for the rack criteria of KAS_KEY_RACK_BASE):
+// Two kernels behind a solve and its impact pass (the rank kernel in three instances: the second also reads the scenario rack
+// records of a rack pass, for the rack criteria of KAS_KEY_RACK_BASE, the third those and the scenario topic records of a topic
+// pass, for the topic criteria of KAS_KEY_TOPIC_BASE):
 //   rank    one lane per scenario, KAS_CHOOSE_BLOCK lanes a workgroup.  Every workgroup streams all S keys through the LDS in
 //           tiles of KAS_CHOOSE_TILE entries, built from the 64 bytes of records per scenario; a lane counts the entries whose
 //           key is smaller than its own — its rank — and in the same loop sums their packed cells and node counts: the offsets
@@ -122,14 +123,18 @@ static inline int64_t kas_choose_chunks(const KasChoosePlan& cp, int32_t dst_cel
 
 // Rack criteria (KAS_KEY_RACK_BASE .. KAS_KEY_RACK_END - 1) are known to the *_racks entries only: `racks` widens the key set.
 static inline bool kas_key_is_rack(int32_t key) { return key >= KAS_KEY_RACK_BASE && key < KAS_KEY_RACK_END; }
-static inline bool kas_key_known(int32_t key, bool racks) { return (key >= 0 && key < KAS_KEY_COUNT) || (racks && kas_key_is_rack(key)); }
+// Topic criteria (KAS_KEY_TOPIC_BASE .. KAS_KEY_TOPIC_END - 1) are known to the *_topics entries only: `topics` widens it again.
+static inline bool kas_key_is_topic(int32_t key) { return key >= KAS_KEY_TOPIC_BASE && key < KAS_KEY_TOPIC_END; }
+static inline bool kas_key_known(int32_t key, bool racks, bool topics = false) {
+  return (key >= 0 && key < KAS_KEY_COUNT) || (racks && kas_key_is_rack(key)) || (topics && kas_key_is_topic(key));
+}
 
 // "" or what is wrong with a spec for S scenarios (the text of the KAS_E_INVALID_ARG)
-static inline const char* kas_choose_spec_error_keys(const kas_choose_spec* spec, int64_t S, bool racks) {
+static inline const char* kas_choose_spec_error_keys(const kas_choose_spec* spec, int64_t S, bool racks, bool topics = false) {
   if (!spec) return "kas_choose_spec == NULL";
   if (spec->n_keys < 1 || spec->n_keys > KAS_CHOOSE_MAX_KEYS) return "kas_choose_spec: n_keys outside 1..4";
   for (int32_t i = 0; i < spec->n_keys; ++i)
-    if (!kas_key_known(spec->key[i], racks)) return "kas_choose_spec: unknown criterion";
+    if (!kas_key_known(spec->key[i], racks, topics)) return "kas_choose_spec: unknown criterion";
   if (spec->k < 0 || spec->k > S) return "kas_choose_spec: k outside 0..n_scenarios";
   return "";
 }
@@ -142,6 +147,14 @@ static inline bool kas_choose_spec_uses_racks(const kas_choose_spec* spec) {
   return false;
 }
 #define KAS_NO_RACK_RECORDS "rack criterion without rack records"   // the refusal of a rack criterion with NULL records
+
+// ... and a topic criterion: what the *_topics entries need topic records for
+static inline bool kas_choose_spec_uses_topics(const kas_choose_spec* spec) {
+  for (int32_t i = 0; i < spec->n_keys; ++i)
+    if (kas_key_is_topic(spec->key[i])) return true;
+  return false;
+}
+#define KAS_NO_TOPIC_RECORDS "topic criterion without topic records"
 
 // the spec's words of the launch arguments
 static inline void kas_choose_fill_spec(KasChooseLaunch* a, const kas_choose_spec* spec, int32_t S) {
@@ -156,7 +169,16 @@ struct KasRackChooseLaunch {
   const kas_scenario_rack_impact* srk;
 };
 
+// ... and of the instance that reads scenario rack records and scenario topic records.  stp: [S], never NULL here; srk: [S], or
+// NULL when the spec names no rack criterion (it is then never dereferenced).
+struct KasTopicChooseLaunch {
+  KasChooseLaunch c;
+  const kas_scenario_rack_impact* srk;
+  const kas_scenario_topic_impact* stp;
+};
+
 // kas_choose.hip.  All return a hipError_t (0 = hipSuccess).  kas_gather_launch needs a.chunks * a.k below 2^31.
 int kas_rank_launch(const KasChooseLaunch* a, void* hip_stream);
 int kas_gather_launch(const KasChooseLaunch* a, void* hip_stream);
 int kas_rank_racks_launch(const KasRackChooseLaunch* a, void* hip_stream);
+int kas_rank_topics_launch(const KasTopicChooseLaunch* a, void* hip_stream);

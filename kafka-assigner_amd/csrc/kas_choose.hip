@@ -1,9 +1,9 @@
 // kas_choose.hip — gfx950 kernels that choose the best scenarios of a solve (kas_rank_device / kas_choose_device /
 // kas_solve_host_choose in kas_hip.hip) or mark and rank their Pareto front (kas_front_rank_device / kas_front_device /
 // kas_solve_host_front), and the instances of the rank, mark and front rank kernels that read the scenario rack records too
-// (the *_racks entries).  Tables and launch arguments: kas_choose.h, kas_front.h; device code: kas_choose_body.h,
-// kas_front_body.h.  A translation unit of its own, so that nothing here changes how the kernels of kas_hip.hip and
-// kas_impact.hip are compiled.
+// (the *_racks entries) or those and the scenario topic records (the *_topics entries).  Tables and launch arguments:
+// kas_choose.h, kas_front.h; device code: kas_choose_body.h, kas_front_body.h.  A translation unit of its own, so that nothing
+// here changes how the kernels of kas_hip.hip and kas_impact.hip are compiled.
 #include <hip/hip_runtime.h>
 
 #include "kas_choose_body.h"
@@ -48,6 +48,23 @@ __global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_front_rank_racks_kernel(
   kasf::rank_block(a.f, (int32_t)blockIdx.x, tile, kasc::RackRecords{a.srk});
 }
 
+// The instances that read the scenario rack records and the scenario topic records (topic criteria, KAS_KEY_TOPIC_BASE): same
+// grids, same tiles; they differ in the loads of entry_of alone.
+__global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_rank_topics_kernel(KasTopicChooseLaunch a) {
+  __shared__ kasc::Entry tile[KAS_CHOOSE_TILE];
+  kasc::rank_block(a.c, (int32_t)blockIdx.x, tile, kasc::ByStatus(), kasc::TopicRecords{a.srk, a.stp});
+}
+
+__global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_front_mark_topics_kernel(KasTopicFrontLaunch a) {
+  __shared__ kasf::Entry tile[KAS_CHOOSE_TILE];
+  kasf::mark_block(a.f, (int32_t)blockIdx.x, tile, kasc::TopicRecords{a.srk, a.stp});
+}
+
+__global__ __launch_bounds__(KAS_CHOOSE_BLOCK) void kas_front_rank_topics_kernel(KasTopicFrontLaunch a) {
+  __shared__ kasc::Entry tile[KAS_CHOOSE_TILE];
+  kasf::rank_block(a.f, (int32_t)blockIdx.x, tile, kasc::TopicRecords{a.srk, a.stp});
+}
+
 int kas_rank_launch(const KasChooseLaunch* a, void* hip_stream) {
   const unsigned grid = (unsigned)(((int64_t)a->S + 1 + KAS_CHOOSE_BLOCK - 1) / KAS_CHOOSE_BLOCK);
   hipLaunchKernelGGL(kas_rank_kernel, dim3(grid), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
@@ -87,5 +104,22 @@ int kas_front_mark_racks_launch(const KasRackFrontLaunch* a, void* hip_stream) {
 int kas_front_rank_racks_launch(const KasRackFrontLaunch* a, void* hip_stream) {
   const unsigned grid = (unsigned)(((int64_t)a->f.c.S + 1 + KAS_CHOOSE_BLOCK - 1) / KAS_CHOOSE_BLOCK);
   hipLaunchKernelGGL(kas_front_rank_racks_kernel, dim3(grid), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
+  return (int)hipGetLastError();
+}
+
+int kas_rank_topics_launch(const KasTopicChooseLaunch* a, void* hip_stream) {
+  const unsigned grid = (unsigned)(((int64_t)a->c.S + 1 + KAS_CHOOSE_BLOCK - 1) / KAS_CHOOSE_BLOCK);
+  hipLaunchKernelGGL(kas_rank_topics_kernel, dim3(grid), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
+  return (int)hipGetLastError();
+}
+
+int kas_front_mark_topics_launch(const KasTopicFrontLaunch* a, void* hip_stream) {
+  hipLaunchKernelGGL(kas_front_mark_topics_kernel, dim3((unsigned)kas_front_mark_grid(a->f.c.S)), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
+  return (int)hipGetLastError();
+}
+
+int kas_front_rank_topics_launch(const KasTopicFrontLaunch* a, void* hip_stream) {
+  const unsigned grid = (unsigned)(((int64_t)a->f.c.S + 1 + KAS_CHOOSE_BLOCK - 1) / KAS_CHOOSE_BLOCK);
+  hipLaunchKernelGGL(kas_front_rank_topics_kernel, dim3(grid), dim3(KAS_CHOOSE_BLOCK), 0, (hipStream_t)hip_stream, *a);
   return (int)hipGetLastError();
 }

@@ -54,6 +54,17 @@ KAS_DEV int32_t criterion_of(const RackRecords& x, const kas_scenario_result& r,
   return w[key - KAS_KEY_RACK_BASE];
 }
 
+// TopicRecords: also the scenario topic records.  A topic criterion is int32 word key - KAS_KEY_TOPIC_BASE of the 64-byte record,
+// one 4-byte load (the record holds the spreads: no derived keys); a rack criterion is loaded as RackRecords loads it, and srk may
+// be NULL when the spec names none.
+struct TopicRecords { const kas_scenario_rack_impact* srk; const kas_scenario_topic_impact* stp; };
+static_assert(sizeof(kas_scenario_topic_impact) == 64 && KAS_KEY_TOPIC_END - KAS_KEY_TOPIC_BASE == 15, "fifteen words, the sixteenth reserved");
+KAS_DEV int32_t criterion_of(const TopicRecords& x, const kas_scenario_result& r, const kas_scenario_impact& m, int32_t s, int32_t key) {
+  if (key < KAS_KEY_RACK_BASE) return criterion(r, m, key);
+  if (key < KAS_KEY_TOPIC_BASE) return criterion_of(RackRecords{x.srk}, r, m, s, key);
+  return reinterpret_cast<const int32_t*>(x.stp + s)[key - KAS_KEY_TOPIC_BASE];
+}
+
 // Who takes part in a ranking, and what the ranking leaves for those who do not.  ByStatus: the scenarios that solved
 // (kas_choose_spec); kas_front_body.h has the other one, the members of a front.
 struct ByStatus {};

@@ -27,14 +27,14 @@ struct KasFrontLaunch {
 
 // "" or what is wrong with a spec for S scenarios (the text of the KAS_E_INVALID_ARG); racks: rack criteria are known (the
 // *_racks entries)
-static inline const char* kas_front_spec_error_keys(const kas_front_spec* spec, int64_t S, bool racks) {
+static inline const char* kas_front_spec_error_keys(const kas_front_spec* spec, int64_t S, bool racks, bool topics = false) {
   if (!spec) return "kas_front_spec == NULL";
   if (spec->n_keys < 1 || spec->n_keys > KAS_CHOOSE_MAX_KEYS) return "kas_front_spec: n_keys outside 1..4";
   for (int32_t i = 0; i < spec->n_keys; ++i)
-    if (!kas_key_known(spec->key[i], racks)) return "kas_front_spec: unknown criterion";
+    if (!kas_key_known(spec->key[i], racks, topics)) return "kas_front_spec: unknown criterion";
   if (spec->n_limits < 0 || spec->n_limits > KAS_CHOOSE_MAX_KEYS) return "kas_front_spec: n_limits outside 0..4";
   for (int32_t i = 0; i < spec->n_limits; ++i)
-    if (!kas_key_known(spec->limit_key[i], racks)) return "kas_front_spec: unknown limit criterion";
+    if (!kas_key_known(spec->limit_key[i], racks, topics)) return "kas_front_spec: unknown limit criterion";
   for (int32_t i = 0; i < spec->n_limits; ++i)
     if (spec->limit[i] < 0) return "kas_front_spec: negative limit";
   if (spec->k < 0 || spec->k > S) return "kas_front_spec: k outside 0..n_scenarios";
@@ -48,6 +48,15 @@ static inline bool kas_front_spec_uses_racks(const kas_front_spec* spec) {
     if (kas_key_is_rack(spec->key[i])) return true;
   for (int32_t i = 0; i < spec->n_limits; ++i)
     if (kas_key_is_rack(spec->limit_key[i])) return true;
+  return false;
+}
+
+// ... or a topic criterion
+static inline bool kas_front_spec_uses_topics(const kas_front_spec* spec) {
+  for (int32_t i = 0; i < spec->n_keys; ++i)
+    if (kas_key_is_topic(spec->key[i])) return true;
+  for (int32_t i = 0; i < spec->n_limits; ++i)
+    if (kas_key_is_topic(spec->limit_key[i])) return true;
   return false;
 }
 
@@ -82,8 +91,17 @@ struct KasRackFrontLaunch {
   const kas_scenario_rack_impact* srk;  // [S], never NULL here
 };
 
+// ... and of the instances that read scenario rack records and scenario topic records (as KasTopicChooseLaunch).
+struct KasTopicFrontLaunch {
+  KasFrontLaunch f;
+  const kas_scenario_rack_impact* srk;  // [S], or NULL when the spec names no rack criterion
+  const kas_scenario_topic_impact* stp; // [S], never NULL here
+};
+
 // kas_choose.hip.  All return a hipError_t (0 = hipSuccess).
 int kas_front_mark_launch(const KasFrontLaunch* a, void* hip_stream);
 int kas_front_rank_launch(const KasFrontLaunch* a, void* hip_stream);
 int kas_front_mark_racks_launch(const KasRackFrontLaunch* a, void* hip_stream);
 int kas_front_rank_racks_launch(const KasRackFrontLaunch* a, void* hip_stream);
+int kas_front_mark_topics_launch(const KasTopicFrontLaunch* a, void* hip_stream);
+int kas_front_rank_topics_launch(const KasTopicFrontLaunch* a, void* hip_stream);

@@ -463,7 +463,7 @@ struct kas_plan {
   int topics_ready = 0;
   KasTopicPlan topics;
   KasBuf b_tp_items, b_tp_merge, b_tp_roff, b_tp_region;
-  hipEvent_t ev_topics = nullptr;       // recorded behind the plan's last topic pass
+  hipEvent_t ev_topics = nullptr;       // recorded behind the plan's last topic pass, and again behind a choice that reads its records
   hipStream_t topics_stream = nullptr;
   int topics_pending = 0;               // ev_topics has been recorded
   // choosing on the device (kas_choose_device / 16): the size and segment tables, built at the plan's first such call
@@ -1378,6 +1378,61 @@ int kas_front_rank_device_racks(kas_ctx* ctx, const kas_scenario_result* scenari
   return KAS_E_OK;
 }
 
+// ... and with the scenario topic records as a fourth.  A spec without a topic criterion goes to the *_racks entry (which sends
+// one without a rack criterion on to the oldest entry): its kernel instances, its bytes.
+int kas_rank_device_topics(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                           const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                           int32_t n_scenarios, const kas_choose_spec* spec, int32_t* rank, int32_t* chosen, int32_t* n_ok, void* hip_stream) {
+  if (!ctx) return set_error(KAS_E_INVALID_ARG, "ctx == NULL");
+  if (n_scenarios < 0) return set_error(KAS_E_INVALID_ARG, "n_scenarios < 0");
+  const char* bad = kas_choose_spec_error_keys(spec, n_scenarios, true, true);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (kas_choose_spec_uses_racks(spec) && !rack_scenarios) return set_error(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+  if (!kas_choose_spec_uses_topics(spec))
+    return kas_rank_device_racks(ctx, scenario_results, scenario_impact, rack_scenarios, n_scenarios, spec, rank, chosen, n_ok, hip_stream);
+  if (!topic_scenarios) return set_error(KAS_E_INVALID_ARG, KAS_NO_TOPIC_RECORDS);
+  if (!n_ok || (n_scenarios > 0 && (!scenario_results || !scenario_impact || !rank)) || (spec->k > 0 && !chosen))
+    return set_error(KAS_E_INVALID_ARG, "kas_rank_device: an array the call reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(ctx->device));
+  KasTopicChooseLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.c.sr = scenario_results; a.c.si = scenario_impact; a.srk = rack_scenarios; a.stp = topic_scenarios;
+  kas_choose_fill_spec(&a.c, spec, n_scenarios);
+  a.c.rank = rank; a.c.chosen = chosen; a.c.n_ok = n_ok;
+  const int e = kas_rank_topics_launch(&a, hip_stream ? hip_stream : (void*)ctx->stream);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("kas_rank_topics_kernel: ") + hipGetErrorString((hipError_t)e));
+  return KAS_E_OK;
+}
+
+int kas_front_rank_device_topics(kas_ctx* ctx, const kas_scenario_result* scenario_results, const kas_scenario_impact* scenario_impact,
+                                 const kas_scenario_rack_impact* rack_scenarios, const kas_scenario_topic_impact* topic_scenarios,
+                                 int32_t n_scenarios, const kas_front_spec* spec, int32_t* rank, int32_t* chosen, int32_t* counts,
+                                 int32_t* scratch, void* hip_stream) {
+  if (!ctx) return set_error(KAS_E_INVALID_ARG, "ctx == NULL");
+  if (n_scenarios < 0) return set_error(KAS_E_INVALID_ARG, "n_scenarios < 0");
+  const char* bad = kas_front_spec_error_keys(spec, n_scenarios, true, true);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (kas_front_spec_uses_racks(spec) && !rack_scenarios) return set_error(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+  if (!kas_front_spec_uses_topics(spec))
+    return kas_front_rank_device_racks(ctx, scenario_results, scenario_impact, rack_scenarios, n_scenarios, spec, rank, chosen, counts, scratch,
+                                       hip_stream);
+  if (!topic_scenarios) return set_error(KAS_E_INVALID_ARG, KAS_NO_TOPIC_RECORDS);
+  if (!counts || (n_scenarios > 0 && (!scenario_results || !scenario_impact || !rank || !scratch)) || (spec->k > 0 && !chosen))
+    return set_error(KAS_E_INVALID_ARG, "kas_front_rank_device: an array the call reads or writes is NULL");
+  KAS_HIP_TRY(hipSetDevice(ctx->device));
+  KasTopicFrontLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.f.c.sr = scenario_results; a.f.c.si = scenario_impact; a.srk = rack_scenarios; a.stp = topic_scenarios;
+  kas_front_fill_spec(&a.f, spec, n_scenarios);
+  a.f.c.rank = rank; a.f.c.chosen = chosen; a.f.c.n_ok = counts;   // (n_ok is counts[0])
+  a.f.cls = scratch; a.f.counts = counts;
+  void* st = hip_stream ? hip_stream : (void*)ctx->stream;
+  int e = kas_front_mark_topics_launch(&a, st);
+  if (e == 0) e = kas_front_rank_topics_launch(&a, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("front kernels: ") + hipGetErrorString((hipError_t)e));
+  return KAS_E_OK;
+}
+
 // The plan's size and segment tables (built on the host with the plan) on the device: allocated and uploaded at the plan's first
 // choice — blocking copies, once — and kept until the plan is rebuilt.
 static int kas_choose_prepare(kas_plan* p) {
@@ -1394,21 +1449,25 @@ static int kas_choose_prepare(kas_plan* p) {
 
 // front: the Pareto front in place of the ranking (kas_front_device / 16; `spec` is then not read, `counts` is the call's).
 // rack_keys: the spec may name rack criteria (the *_racks entries), read from srk, the scenario rack records of the plan's rack pass.
+// topic_keys: ... and topic criteria (the *_topics entries), read from stp, the scenario topic records of the plan's topic pass.
 static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_choose_spec* spec,
                            const kas_choice* ch, hipStream_t st, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
-                           bool rack_keys = false, const kas_scenario_rack_impact* srk = nullptr) {
+                           bool rack_keys = false, const kas_scenario_rack_impact* srk = nullptr, bool topic_keys = false,
+                           const kas_scenario_topic_impact* stp = nullptr) {
   const int32_t S = p->n_scenarios;
   kas_choose_spec front_cs;
   if (front) {
-    const char* bad = kas_front_spec_error_keys(front, S, rack_keys);
+    const char* bad = kas_front_spec_error_keys(front, S, rack_keys, topic_keys);
     if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
     front_cs = kas_front_choose_spec(front);
     spec = &front_cs;
   }
-  const char* bad = kas_choose_spec_error_keys(spec, S, rack_keys);
+  const char* bad = kas_choose_spec_error_keys(spec, S, rack_keys, topic_keys);
   if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
   const bool by_racks = rack_keys && (front ? kas_front_spec_uses_racks(front) : kas_choose_spec_uses_racks(spec));
   if (by_racks && !srk) return set_error(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+  const bool by_topics = topic_keys && (front ? kas_front_spec_uses_topics(front) : kas_choose_spec_uses_topics(spec));
+  if (by_topics && !stp) return set_error(KAS_E_INVALID_ARG, KAS_NO_TOPIC_RECORDS);
   const KasChoosePlan& cp = p->choose;
   int64_t rows_need = 0, nodes_need = 0;
   kas_choose_k_largest(cp, spec->k, &rows_need, &nodes_need);
@@ -1437,6 +1496,8 @@ static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_ta
   // ordered behind the plan's previous solve and its impact pass; a later solve waits for the gather as it waits for that pass
   if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
   if (p->impact_pending && p->impact_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_impact, 0));
+  // a choice by topic criteria reads what the plan's topic pass wrote: that pass records ev_topics, not ev_impact
+  if (by_topics && p->topics_pending && p->topics_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_topics, 0));
   KasChooseLaunch a;
   memset(&a, 0, sizeof(a));
   a.sr = t->scenario_results; a.si = imp->scenarios;
@@ -1453,17 +1514,23 @@ static int kas_choose_impl(kas_plan* p, const kas_tables* t, const kas_impact_ta
     f.c = a;
     f.cls = (int32_t*)p->b_fr_cls.p; f.counts = counts;
     const KasRackFrontLaunch fr{f, srk};
-    e = by_racks ? kas_front_mark_racks_launch(&fr, st) : kas_front_mark_launch(&f, st);
-    if (e == 0) e = by_racks ? kas_front_rank_racks_launch(&fr, st) : kas_front_rank_launch(&f, st);
+    const KasTopicFrontLaunch ft{f, srk, stp};
+    e = by_topics ? kas_front_mark_topics_launch(&ft, st) : by_racks ? kas_front_mark_racks_launch(&fr, st) : kas_front_mark_launch(&f, st);
+    if (e == 0) e = by_topics ? kas_front_rank_topics_launch(&ft, st) : by_racks ? kas_front_rank_racks_launch(&fr, st) : kas_front_rank_launch(&f, st);
   } else {
     const KasRackChooseLaunch ar{a, srk};
-    e = by_racks ? kas_rank_racks_launch(&ar, st) : kas_rank_launch(&a, st);
+    const KasTopicChooseLaunch at{a, srk, stp};
+    e = by_topics ? kas_rank_topics_launch(&at, st) : by_racks ? kas_rank_racks_launch(&ar, st) : kas_rank_launch(&a, st);
   }
   if (e == 0) e = kas_gather_launch(&a, st);
   if (e != 0) return set_error(KAS_E_HIP, std::string("choose kernels: ") + hipGetErrorString((hipError_t)e));
   if (p->impact_pending) {
     KAS_HIP_TRY(hipEventRecord(p->ev_impact, st));
     p->impact_stream = st;
+  }
+  if (by_topics && p->topics_pending) {                         // (a later topic pass rewrites the records this choice reads)
+    KAS_HIP_TRY(hipEventRecord(p->ev_topics, st));
+    p->topics_stream = st;
   }
   return KAS_E_OK;
 }
@@ -1531,6 +1598,41 @@ int kas_front_device16_racks(kas_plan* p, const kas_tables16* t16, const kas_imp
   if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_choose_impl(p, &t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts, true, srk);
+}
+
+// ... and with the scenario topic records of the plan's topic pass as well (ordered behind it through the plan's topic event)
+int kas_choose_device_topics(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                             const kas_scenario_topic_impact* stp, const kas_choose_spec* spec, const kas_choice* ch, void* hip_stream) {
+  if (!p || !t || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_choose_device16");
+  return kas_choose_impl(p, t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr, nullptr, true, srk, true, stp);
+}
+
+int kas_choose_device16_topics(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                               const kas_scenario_topic_impact* stp, const kas_choose_spec* spec, const kas_choice* ch, void* hip_stream) {
+  if (!p || !t16 || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_choose_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_choose_impl(p, &t, imp, spec, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, nullptr, nullptr, true, srk, true, stp);
+}
+
+int kas_front_device_topics(kas_plan* p, const kas_tables* t, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                            const kas_scenario_topic_impact* stp, const kas_front_spec* spec, const kas_choice* ch, int32_t* counts,
+                            void* hip_stream) {
+  if (!p || !t || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_front_device16");
+  if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
+  return kas_choose_impl(p, t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts, true, srk, true, stp);
+}
+
+int kas_front_device16_topics(kas_plan* p, const kas_tables16* t16, const kas_impact_tables* imp, const kas_scenario_rack_impact* srk,
+                              const kas_scenario_topic_impact* stp, const kas_front_spec* spec, const kas_choice* ch, int32_t* counts,
+                              void* hip_stream) {
+  if (!p || !t16 || !imp || !ch) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_front_device16 needs a plan of kas_plan_create16");
+  if (!spec) return set_error(KAS_E_INVALID_ARG, "kas_front_spec == NULL");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_choose_impl(p, &t, imp, nullptr, ch, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream, spec, counts, true, srk, true, stp);
 }
 
 // ---- the move list (kernels: kas_moves.hip) ----------------------------------------------------------------------------
@@ -1867,7 +1969,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
                                  const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
                                  bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
                                  const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr, bool rack_keys = false,
-                                 bool topic_pass = false, const kas_topic_impact_tables* htp = nullptr) {
+                                 bool topic_pass = false, const kas_topic_impact_tables* htp = nullptr, bool topic_keys = false) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -1899,7 +2001,8 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.racks = true; in.report_rack = report_rack; in.racks_cap = hrk->racks_cap;
     in.have_rk_racks = hrk->racks != nullptr; in.have_rk_scenarios = hrk->scenarios != nullptr; in.have_rk_off = hrk->rack_off != nullptr;
   }
-  if (topic_pass) {                                            // kas_solve_host_topic_impact / 16
+  in.topic_keys = topic_keys;                                  // kas_solve_host_choose_topics / kas_solve_host_front_topics / 16
+  if (topic_pass) {                                            // kas_solve_host_topic_impact / 16, and those
     in.topics = true; in.have_tp_tables = htp != nullptr;
     in.have_tp_topics = htp && htp->topics; in.have_tp_scenarios = htp && htp->scenarios;
   }
@@ -2046,7 +2149,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   }
   for (int i = K - lag < 0 ? 0 : K - lag; i < K && he == hipSuccess && fail_rc == KAS_E_OK; ++i) download(i);
   // a choice: rank and gather on s0 behind every range (one range: s0 solved it; several: their done events, which are recorded
-  // behind a range's rack pass: a ranking by rack criteria sees every range's rack records), then its header
+  // behind a range's rack pass and its topic pass: a ranking by rack or topic criteria sees every range's records), then its header
   const int64_t ch_k = hch ? spec->k : 0;
   char* const d_head = (char*)ctx->hbuf[KAS_HB_CH_HEAD].p;
   char* const p_head = (char*)ctx->hbuf[KAS_HB_CH_HEAD_PIN].p;
@@ -2079,6 +2182,9 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
       // (the planner refused a rack criterion without a rack pass: the records are this call's)
       const kas_scenario_rack_impact* srk = (const kas_scenario_rack_impact*)ctx->hbuf[KAS_HB_RK_SCEN].p;
       const bool by_racks = rack_keys && hrk && (front ? kas_front_spec_uses_racks(front) : kas_choose_spec_uses_racks(spec));
+      // (... and a topic criterion without a topic pass; srk is not read when the spec names no rack criterion)
+      const kas_scenario_topic_impact* stp = (const kas_scenario_topic_impact*)ctx->hbuf[KAS_HB_TP_SCEN].p;
+      const bool by_topics = topic_keys && topic_pass && (front ? kas_front_spec_uses_topics(front) : kas_choose_spec_uses_topics(spec));
       if (front) {                                              // mark and front rank where the rank kernel runs
         KasFrontLaunch f;
         memset(&f, 0, sizeof(f));
@@ -2086,11 +2192,13 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
         f.c = a;
         f.cls = (int32_t*)ctx->hbuf[KAS_HB_FR_CLS].p; f.counts = (int32_t*)ctx->hbuf[KAS_HB_FR_COUNTS].p;
         const KasRackFrontLaunch fr{f, srk};
-        e = by_racks ? kas_front_mark_racks_launch(&fr, s0) : kas_front_mark_launch(&f, s0);
-        if (e == 0) e = by_racks ? kas_front_rank_racks_launch(&fr, s0) : kas_front_rank_launch(&f, s0);
+        const KasTopicFrontLaunch ft{f, hrk ? srk : nullptr, stp};
+        e = by_topics ? kas_front_mark_topics_launch(&ft, s0) : by_racks ? kas_front_mark_racks_launch(&fr, s0) : kas_front_mark_launch(&f, s0);
+        if (e == 0) e = by_topics ? kas_front_rank_topics_launch(&ft, s0) : by_racks ? kas_front_rank_racks_launch(&fr, s0) : kas_front_rank_launch(&f, s0);
       } else {
         const KasRackChooseLaunch ar{a, srk};
-        e = by_racks ? kas_rank_racks_launch(&ar, s0) : kas_rank_launch(&a, s0);
+        const KasTopicChooseLaunch at{a, hrk ? srk : nullptr, stp};
+        e = by_topics ? kas_rank_topics_launch(&at, s0) : by_racks ? kas_rank_racks_launch(&ar, s0) : kas_rank_launch(&a, s0);
       }
       if (!hc.ch_gather_rows) a.sizes = (const KasChooseSize*)ctx->hbuf[KAS_HB_MV_SIZES0].p;
       if (e == 0) e = kas_gather_launch(&a, s0);
@@ -2388,6 +2496,47 @@ int kas_solve_host16_front_racks(kas_ctx* ctx, const kas_batch_desc* batch, cons
   const kas_tables h = kas_tables_of16(h16, &c16);
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, nullptr, hch, hmv, true, spec, counts, hrk, report_rack, true);
+}
+
+// kas_solve_host_choose_racks / kas_solve_host_front_racks / 16 plus the topic pass (htp != NULL); the spec may name topic criteria
+int kas_solve_host_choose_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,
+                                 const kas_impact_tables* himp, const kas_moves* hmv, const int32_t* report_rack, const kas_rack_tables* hrk,
+                                 const kas_topic_impact_tables* htp) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, spec, hch, hmv, true, nullptr, nullptr, hrk, report_rack, true,
+                               htp != nullptr, htp, true);
+}
+
+int kas_solve_host16_choose_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_choose_spec* spec,
+                                   const kas_choice* hch, const kas_impact_tables* himp, const kas_moves* hmv, const int32_t* report_rack,
+                                   const kas_rack_tables* hrk, const kas_topic_impact_tables* htp) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, spec, hch, hmv, true, nullptr, nullptr, hrk, report_rack, true,
+                               htp != nullptr, htp, true);
+}
+
+int kas_solve_host_front_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_front_spec* spec, const kas_choice* hch,
+                                int32_t* counts, const kas_impact_tables* himp, const kas_moves* hmv, const int32_t* report_rack,
+                                const kas_rack_tables* hrk, const kas_topic_impact_tables* htp) {
+  if (!ctx || !batch || !h || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, nullptr, 0, nullptr, himp, nullptr, hch, hmv, true, spec, counts, hrk, report_rack, true,
+                               htp != nullptr, htp, true);
+}
+
+int kas_solve_host16_front_topics(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const kas_front_spec* spec,
+                                  const kas_choice* hch, int32_t* counts, const kas_impact_tables* himp, const kas_moves* hmv,
+                                  const int32_t* report_rack, const kas_rack_tables* hrk, const kas_topic_impact_tables* htp) {
+  if (!ctx || !batch || !h16 || !spec || !hch || !himp) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, nullptr, 0, &c16, himp, nullptr, hch, hmv, true, spec, counts, hrk, report_rack, true,
+                               htp != nullptr, htp, true);
 }
 
 int kas_solve_host_sharded(kas_ctx* const* ctxs, int32_t n_ctx, const kas_batch_desc* batch, const kas_tables* h) {

@@ -261,6 +261,10 @@ struct KasHostCallIn {
   // no topic pass, and every decision above as it was); with `topics` the node records may stay on the device, as with `racks`
   bool topics = false;
   bool have_tp_tables = false, have_tp_topics = false, have_tp_scenarios = false;   // kas_topic_impact_tables
+  // kas_solve_host_choose_topics / kas_solve_host_front_topics / 16: `topics` together with `choose` or `front` (the topic refusals
+  // then follow the rack pass's, which follow the choice's and the moves'), and topic_keys beside rack_keys: the spec may name
+  // topic criteria (KAS_KEY_TOPIC_BASE), which need `topics`.  Defaults: every decision above as it was.
+  bool topic_keys = false;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -325,15 +329,17 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   auto fail = [&](int code, const char* m) { if (err) *err = m; return code; };
   int rc;
   if (in.front) {                                               // a front's own refusals come first
-    const char* bad = kas_front_spec_error_keys(in.front, in.batch->n_scenarios, in.rack_keys);
+    const char* bad = kas_front_spec_error_keys(in.front, in.batch->n_scenarios, in.rack_keys, in.topic_keys);
     if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
     if (in.rack_keys && !in.racks && kas_front_spec_uses_racks(in.front)) return fail(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+    if (in.topic_keys && !in.topics && kas_front_spec_uses_topics(in.front)) return fail(KAS_E_INVALID_ARG, KAS_NO_TOPIC_RECORDS);
     hc->ch_spec = kas_front_choose_spec(in.front);
   } else if (in.choose) {
-    if (in.rack_keys) {                                         // ... and so do those of a choice that may name rack criteria
-      const char* bad = kas_choose_spec_error_keys(in.choose, in.batch->n_scenarios, true);
+    if (in.rack_keys || in.topic_keys) {                        // ... and so do those of a choice that may name rack or topic criteria
+      const char* bad = kas_choose_spec_error_keys(in.choose, in.batch->n_scenarios, in.rack_keys, in.topic_keys);
       if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
-      if (!in.racks && kas_choose_spec_uses_racks(in.choose)) return fail(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+      if (in.rack_keys && !in.racks && kas_choose_spec_uses_racks(in.choose)) return fail(KAS_E_INVALID_ARG, KAS_NO_RACK_RECORDS);
+      if (in.topic_keys && !in.topics && kas_choose_spec_uses_topics(in.choose)) return fail(KAS_E_INVALID_ARG, KAS_NO_TOPIC_RECORDS);
     }
     hc->ch_spec = *in.choose;
   }
@@ -395,17 +401,19 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   };
   if (in.racks && !choose && (rc = rack_pass()) != KAS_E_OK) return rc;
   // the topic pass: the arrays, then the global counters of its work list
-  if (in.topics) {
+  auto topic_pass = [&]() -> int {
     if (!in.have_tp_tables || (T > 0 && !in.have_tp_topics) || (S > 0 && !in.have_tp_scenarios))
       return fail(KAS_E_INVALID_ARG, "kas_topic_impact_tables: topics / scenarios == NULL");
     KasTopicPlan tp;
     kas_topic_plan_build(b, full.n_max, full.idmap_entries, full.need_bsearch, in.cells16 ? 1 : 0, -1, kas_impact_rows_per_item(b), &tp);
     hc->tp_region_ints = tp.region_ints;
     if (!kas_topic_scratch_ok(tp)) return fail(KAS_E_UNSUPPORTED, KAS_TOPIC_SCRATCH_TEXT);
-  }
+    return KAS_E_OK;
+  };
+  if (in.topics && !choose && (rc = topic_pass()) != KAS_E_OK) return rc;
   // a choice: the spec, then the room for any k scenarios (which ones win is not known before the solve), then the arrays
   if (choose) {
-    const char* bad = kas_choose_spec_error_keys(choose, S, in.rack_keys);
+    const char* bad = kas_choose_spec_error_keys(choose, S, in.rack_keys, in.topic_keys);
     if (bad[0]) return fail(KAS_E_INVALID_ARG, bad);
     const int64_t k = choose->k;
     kas_choose_plan_build(b, &hc->choose);
@@ -448,6 +456,7 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     hc->mv_cells_cap = in.moves->cells_cap < hc->mv_room_cells ? in.moves->cells_cap : hc->mv_room_cells;
   }
   if (in.racks && choose && (rc = rack_pass()) != KAS_E_OK) return rc;   // (behind a choice's refusals and its moves')
+  if (in.topics && choose && (rc = topic_pass()) != KAS_E_OK) return rc; // (... and behind the rack pass's)
   // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
   const int64_t cell = in.cells16 ? 2 : 4;                     // bytes of a cur / out cell as it travels
   const int64_t cur_cells = full.cur_need - full.cur_lo, out_cells = full.out_need - full.out_lo;

@@ -37,6 +37,9 @@ SYMBOLS = [
     "kas_front_device_racks", "kas_front_device16_racks", "kas_solve_host_choose_racks", "kas_solve_host16_choose_racks",
     "kas_solve_host_front_racks", "kas_solve_host16_front_racks",
     "kas_topic_impact_device", "kas_topic_impact_device16", "kas_solve_host_topic_impact", "kas_solve_host16_topic_impact",
+    "kas_rank_device_topics", "kas_front_rank_device_topics", "kas_choose_device_topics", "kas_choose_device16_topics",
+    "kas_front_device_topics", "kas_front_device16_topics", "kas_solve_host_choose_topics", "kas_solve_host16_choose_topics",
+    "kas_solve_host_front_topics", "kas_solve_host16_front_topics",
 ]
 
 _LIB = None
@@ -201,6 +204,32 @@ def load():
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.FrontSpec), C.POINTER(abi.Choice),
                        C.c_void_p, C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves), C.c_void_p, C.POINTER(abi.RackTables)]
+    # the *_topics entries: the *_racks prototypes with the scenario topic records (device entries) or kas_topic_impact_tables
+    # (host entries) added
+    L.kas_rank_device_topics.restype = C.c_int
+    L.kas_rank_device_topics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.ChooseSpec),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kas_front_rank_device_topics.restype = C.c_int
+    L.kas_front_rank_device_topics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.FrontSpec),
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for fn in (L.kas_choose_device_topics, L.kas_choose_device16_topics):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p, C.c_void_p, C.POINTER(abi.ChooseSpec),
+                       C.POINTER(abi.Choice), C.c_void_p]
+    for fn in (L.kas_front_device_topics, L.kas_front_device16_topics):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.POINTER(abi.ImpactTables), C.c_void_p, C.c_void_p, C.POINTER(abi.FrontSpec),
+                       C.POINTER(abi.Choice), C.c_void_p, C.c_void_p]
+    for fn in (L.kas_solve_host_choose_topics, L.kas_solve_host16_choose_topics):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec), C.POINTER(abi.Choice),
+                       C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves), C.c_void_p, C.POINTER(abi.RackTables),
+                       C.POINTER(abi.TopicImpactTables)]
+    for fn in (L.kas_solve_host_front_topics, L.kas_solve_host16_front_topics):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.FrontSpec), C.POINTER(abi.Choice),
+                       C.c_void_p, C.POINTER(abi.ImpactTables), C.POINTER(abi.Moves), C.c_void_p, C.POINTER(abi.RackTables),
+                       C.POINTER(abi.TopicImpactTables)]
     if L.kas_abi_version() != abi.KAS_ABI_VERSION:
         raise ImportError("libkas_hip.so ABI version mismatch")
     _LIB = L
@@ -391,6 +420,35 @@ class Plan:
         fn = self._lib.kas_front_device16_racks if self.cells16 else self._lib.kas_front_device_racks
         _check(fn(self._h, C.byref(t), C.byref(imp), rack_scenarios or None, C.byref(spec), C.byref(ch), counts or None,
                   C.c_void_p(stream) if stream else None))
+
+    def choose_device_topics(self, keys, k: int, out: int, scenario_results: int, nodes: int, scenarios: int, rack_scenarios: int,
+                             topic_scenarios: int, rank: int, chosen: int, row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int,
+                             choice_nodes: int, nodes_cap: int, stream: int = 0):
+        """kas_choose_device_topics / 16: choose_device_racks with `topic_scenarios`, the device array of scenario topic records
+        this plan's topic pass wrote (topic_impact_device), as a further source of criteria: `keys` names abi.KEY_NAMES,
+        abi.RACK_KEY_NAMES and abi.TOPIC_KEY_NAMES.  rack_scenarios / topic_scenarios may be 0 when no criterion of the set is named."""
+        t = abi.Tables()
+        t.out = out or None; t.scenario_results = scenario_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        spec = abi.topic_choose_spec(keys, k)
+        ch = abi.Choice(rank or None, chosen or None, row_off or None, node_off or None, n_ok or None, rows or None, int(rows_cap),
+                        choice_nodes or None, int(nodes_cap))
+        fn = self._lib.kas_choose_device16_topics if self.cells16 else self._lib.kas_choose_device_topics
+        _check(fn(self._h, C.byref(t), C.byref(imp), rack_scenarios or None, topic_scenarios or None, C.byref(spec), C.byref(ch),
+                  C.c_void_p(stream) if stream else None))
+
+    def front_device_topics(self, spec, out: int, scenario_results: int, nodes: int, scenarios: int, rack_scenarios: int,
+                            topic_scenarios: int, rank: int, chosen: int, row_off: int, node_off: int, n_ok: int, rows: int, rows_cap: int,
+                            choice_nodes: int, nodes_cap: int, counts: int, stream: int = 0):
+        """kas_front_device_topics / 16: front_device_racks with the scenario topic records; `spec`: abi.topic_front_spec."""
+        t = abi.Tables()
+        t.out = out or None; t.scenario_results = scenario_results or None
+        imp = abi.ImpactTables(nodes or None, scenarios or None)
+        ch = abi.Choice(rank or None, chosen or None, row_off or None, node_off or None, n_ok or None, rows or None, int(rows_cap),
+                        choice_nodes or None, int(nodes_cap))
+        fn = self._lib.kas_front_device16_topics if self.cells16 else self._lib.kas_front_device_topics
+        _check(fn(self._h, C.byref(t), C.byref(imp), rack_scenarios or None, topic_scenarios or None, C.byref(spec), C.byref(ch),
+                  counts or None, C.c_void_p(stream) if stream else None))
 
     def moves_device(self, mask, select: int, n_select: int, cur: int, out: int, topic_results: int, move_off: int, cell_off: int,
                      moves: int, moves_cap: int, cells: int, cells_cap: int, aux: int = 0, stream: int = 0):
@@ -943,8 +1001,10 @@ def _rack_arrays(fb: FlatBatch, report_rack, racks_cap):
     return rep, rr, abi.RackTables(rr.racks.ctypes.data, rr.scenarios.ctypes.data, rr.rack_off.ctypes.data, cap)
 
 
-def _choice_racks(fb, spec, front, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx):
-    """the shared body of solve_host_choose_racks / solve_host_front_racks"""
+def _choice_records(fb, spec, front, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx, racks=True, topics=False):
+    """the shared body of solve_host_choose_racks / solve_host_front_racks and, with topics=True, of solve_host_choose_topics /
+    solve_host_front_topics (the *_topics entries; host_racks == NULL when racks=False).  Always five results: (HostOutputs, Choice or
+    Front, MoveList or None, RackReport or None, TopicReport or None)"""
     from .flatten import host_tables16, to_cells16
     L = load()
     ctx = ctx or default_context()
@@ -977,15 +1037,22 @@ def _choice_racks(fb, spec, front, report_rack, mask, rows, cells16, moves_cap, 
         room_cells = int(np.sort(packed_cells(fb))[::-1][:kk].sum())
         ml, mv = _move_arrays(mask, kk, room_rows if moves_cap is None else int(moves_cap),
                               room_cells if cells_cap is None else int(cells_cap), cells16)
-    rep, rr, rk = _rack_arrays(fb, report_rack, racks_cap)
-    tail = (C.byref(imp), C.byref(mv) if mv is not None else None, None if rep is None else C.c_void_p(rep.ctypes.data), C.byref(rk))
+    rep, rr, rk = _rack_arrays(fb, report_rack, racks_cap) if racks else (None, None, None)
+    tail = (C.byref(imp), C.byref(mv) if mv is not None else None, None if rep is None else C.c_void_p(rep.ctypes.data),
+            C.byref(rk) if racks else None)
+    tr = None
+    if topics:
+        tt, tscen = topic_impact_arrays(fb)
+        tp = abi.TopicImpactTables(tt.ctypes.data if tt.size else None, tscen.ctypes.data if tscen.size else None)
+        tr = TopicReport(topics=tt, scenarios=tscen, impact=c.scenarios)
+        tail += (C.byref(tp),)
     if front:
-        fn = L.kas_solve_host16_front_racks if cells16 else L.kas_solve_host_front_racks
+        fn = getattr(L, "kas_solve_host%s_front_%s" % ("16" if cells16 else "", "topics" if topics else "racks"))
         _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), counts.ctypes.data, *tail))
         c.n_eligible, c.n_front = int(counts[1]), int(counts[2])
         assert int(counts[0]) == int(n_ok[0]) and int(counts[3]) == 0
     else:
-        fn = L.kas_solve_host16_choose_racks if cells16 else L.kas_solve_host_choose_racks
+        fn = getattr(L, "kas_solve_host%s_choose_%s" % ("16" if cells16 else "", "topics" if topics else "racks"))
         _check(fn(ctx._h, C.byref(bd), C.byref(t), C.byref(spec), C.byref(ch), *tail))
     c.n_ok = int(n_ok[0])
     c.rows = c.rows[:int(c.row_off[kk])] if rows else c.rows[:0]
@@ -993,8 +1060,9 @@ def _choice_racks(fb, spec, front, report_rack, mask, rows, cells16, moves_cap, 
     if ml is not None:
         ml.select = c.chosen
         ml = _trim(ml)
-    rr.racks, rr.scenarios, rr.impact = rr.racks[:int(rr.rack_off[S])], rr.scenarios[:S], c.scenarios
-    return ho, c, ml, rr
+    if racks:
+        rr.racks, rr.scenarios, rr.impact = rr.racks[:int(rr.rack_off[S])], rr.scenarios[:S], c.scenarios
+    return ho, c, ml, rr, tr
 
 
 def solve_host_choose_racks(fb: FlatBatch, keys, k: int, report_rack=None, mask=None, rows: bool = True, cells16: bool = False,
@@ -1004,7 +1072,7 @@ def solve_host_choose_racks(fb: FlatBatch, keys, k: int, report_rack=None, mask=
     racks); `keys` may name rack criteria (abi.RACK_KEY_NAMES) beside abi.KEY_NAMES.  mask=None asks for no moves; rows=False
     hands the library no rows array.  Rows, node blocks and moves come back for the chosen, the rack records for every scenario.
     Returns (HostOutputs without rows, Choice, MoveList or None, RackReport without node records)."""
-    return _choice_racks(fb, abi.rack_choose_spec(keys, k), False, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx)
+    return _choice_records(fb, abi.rack_choose_spec(keys, k), False, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx)[:4]
 
 
 def solve_host_front_racks(fb: FlatBatch, spec, report_rack=None, mask=None, rows: bool = True, cells16: bool = False,
@@ -1012,7 +1080,48 @@ def solve_host_front_racks(fb: FlatBatch, spec, report_rack=None, mask=None, row
                            ctx: Optional[DeviceContext] = None):
     """kas_solve_host_front_racks / 16: solve_host_front plus the rack pass; `spec` (abi.rack_front_spec) may name rack criteria
     among its criteria and its bounds.  Returns (HostOutputs without rows, Front, MoveList or None, RackReport)."""
-    return _choice_racks(fb, spec, True, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx)
+    return _choice_records(fb, spec, True, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx)[:4]
+
+
+def rank_device_topics(scenario_results: int, scenario_impact: int, rack_scenarios: int, topic_scenarios: int, n_scenarios: int, keys,
+                       k: int, rank: int, chosen: int, n_ok: int, stream: int = 0, ctx: Optional[DeviceContext] = None):
+    """kas_rank_device_topics: rank_device_racks with the scenario topic records (a raw device pointer, or 0) as a further source
+    of criteria; `keys`: names of abi.KEY_NAMES, abi.RACK_KEY_NAMES and abi.TOPIC_KEY_NAMES."""
+    ctx = ctx or default_context()
+    spec = abi.topic_choose_spec(keys, k)
+    _check(load().kas_rank_device_topics(ctx._h, scenario_results or None, scenario_impact or None, rack_scenarios or None,
+                                         topic_scenarios or None, int(n_scenarios), C.byref(spec), rank or None, chosen or None,
+                                         n_ok or None, C.c_void_p(stream) if stream else None))
+
+
+def front_rank_device_topics(scenario_results: int, scenario_impact: int, rack_scenarios: int, topic_scenarios: int, n_scenarios: int,
+                             spec, rank: int, chosen: int, counts: int, scratch: int, stream: int = 0,
+                             ctx: Optional[DeviceContext] = None):
+    """kas_front_rank_device_topics: front_rank_device_racks with the scenario topic records; `spec`: abi.topic_front_spec."""
+    ctx = ctx or default_context()
+    _check(load().kas_front_rank_device_topics(ctx._h, scenario_results or None, scenario_impact or None, rack_scenarios or None,
+                                               topic_scenarios or None, int(n_scenarios), C.byref(spec), rank or None, chosen or None,
+                                               counts or None, scratch or None, C.c_void_p(stream) if stream else None))
+
+
+def solve_host_choose_topics(fb: FlatBatch, keys, k: int, racks: bool = False, report_rack=None, mask=None, rows: bool = True,
+                             cells16: bool = False, moves_cap: Optional[int] = None, cells_cap: Optional[int] = None,
+                             racks_cap: Optional[int] = None, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_choose_topics / 16: solve_host_choose_racks plus the topic pass; `keys` may name topic criteria
+    (abi.TOPIC_KEY_NAMES) beside abi.KEY_NAMES and, with racks=True (the rack pass, against `report_rack`), abi.RACK_KEY_NAMES.
+    racks=False hands the library no rack tables (host_racks == NULL).  Every scenario's topic records come back.
+    Returns (HostOutputs without rows, Choice, MoveList or None, RackReport or None, TopicReport)."""
+    return _choice_records(fb, abi.topic_choose_spec(keys, k), False, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx,
+                         racks=racks, topics=True)
+
+
+def solve_host_front_topics(fb: FlatBatch, spec, racks: bool = False, report_rack=None, mask=None, rows: bool = True,
+                            cells16: bool = False, moves_cap: Optional[int] = None, cells_cap: Optional[int] = None,
+                            racks_cap: Optional[int] = None, ctx: Optional[DeviceContext] = None):
+    """kas_solve_host_front_topics / 16: solve_host_front_racks plus the topic pass; `spec` (abi.topic_front_spec) may name topic
+    criteria among its criteria and its bounds.  Returns (HostOutputs without rows, Front, MoveList or None, RackReport or None,
+    TopicReport)."""
+    return _choice_records(fb, spec, True, report_rack, mask, rows, cells16, moves_cap, cells_cap, racks_cap, ctx, racks=racks, topics=True)
 
 
 def solve_host_sharded(fb: FlatBatch, ctxs) -> HostOutputs:

@@ -34,7 +34,10 @@ racks=True — plan.best(variants, by=("colocated_after", "replica_spread")), pl
 topics=True adds the topic pass (kas_solve_host_topic_impact), with or without impact=True: results[0].topics_moved,
 .max_topic_inbound — the most replicas of one topic a single broker must take in —, .max_topic_replica_spread, ... and
 results[0].topic_impact() -> {topic name: {"status": ..., "moved_replicas": ..., "max_inbound": ..., "min_replicas_after": ...}}.
-best() and front() do not read these figures.
+best() and front() rank and bound by these figures too (kas_solve_host_choose_topics / kas_solve_host_front_topics): name a topic
+criterion (abi.TOPIC_KEY_NAMES) in by= or within=, or pass topics=True — plan.best(variants, by=("max_topic_inbound",
+"moved_replicas")), plan.front(variants, by=("moved_replicas", "max_topic_replica_spread"), within={"max_topic_inbound": 40}) — in
+any mix with the broker and the rack criteria, and every winner carries the topic figures and topic_impact().
 
 moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for the rows that change instead of every row, compacted
 on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
@@ -353,14 +356,19 @@ class WhatIf:
 
     @staticmethod
     def _criteria(names, racks: bool) -> bool:
-        """check criterion names; True when the call takes the rack path (racks=True, or a rack criterion among the names)"""
+        """check criterion names; True when the call takes the rack pass (racks=True, or a rack criterion among the names)"""
         for name in names:
-            if name not in abi.KEYS and name not in abi.RACK_KEYS:
-                raise ValueError("unknown criterion %r (one of %s; rack criteria: %s)" %
-                                 (name, ", ".join(abi.KEY_NAMES), ", ".join(abi.RACK_KEY_NAMES)))
+            if name not in abi.KEYS and name not in abi.RACK_KEYS and name not in abi.TOPIC_KEYS:
+                raise ValueError("unknown criterion %r (one of %s; rack criteria: %s; topic criteria: %s)" %
+                                 (name, ", ".join(abi.KEY_NAMES), ", ".join(abi.RACK_KEY_NAMES), ", ".join(abi.TOPIC_KEY_NAMES)))
         return bool(racks) or any(name in abi.RACK_KEYS for name in names)
 
-    def _winner(self, variants, fb, ho, ch, ml, j: int, rows: bool, rk=None, rack_names=None) -> VariantResult:
+    @staticmethod
+    def _by_topics(names, topics: bool) -> bool:
+        """True when the call takes the topic entries (topics=True, or a topic criterion among the names)"""
+        return bool(topics) or any(name in abi.TOPIC_KEYS for name in names)
+
+    def _winner(self, variants, fb, ho, ch, ml, j: int, rows: bool, rk=None, rack_names=None, tp=None) -> VariantResult:
         """chosen[j] of a choice or a front as a VariantResult"""
         s = int(ch.chosen[j])
         sr = ho.scenario_results[s]
@@ -371,6 +379,10 @@ class WhatIf:
         if rk is not None:
             extra.update({f: int(rk.scenarios[f][s]) for f in abi.SCENARIO_RACK_FIELDS})
             extra.update(_racks=rk.of(s), _rack_names=rack_names[s])
+        if tp is not None:
+            tb, tc = int(fb.scen["topic_begin"][s]), int(fb.scen["topic_count"][s])
+            extra.update({f: int(tp.scenarios[f][s]) for f in abi.SCENARIO_TOPIC_FIELDS})
+            extra.update(_topics=tp.topics[tb:tb + tc], _topic_results=ho.topic_results[tb:tb + tc])
         return VariantResult(label=variants[s].label, status=int(sr["status"]), fail_topic=None,
                              fail_partition=int(sr["fail_partition"]), moved_replicas=int(sr["moved_replicas"]),
                              moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]), rank=j,
@@ -379,7 +391,7 @@ class WhatIf:
                              **extra)
 
     def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved"), moves=None,
-             rows: bool = True, racks: bool = False) -> List[VariantResult]:
+             rows: bool = True, racks: bool = False, topics: bool = False) -> List[VariantResult]:
         """The k best variants that solve, best first, chosen on the GPU (kas_solve_host_choose): variants are compared by the
         criteria named in `by` (abi.KEY_NAMES; one to four, smaller is better, the earlier variant wins a tie).  Every variant is
         solved and reduced to its records, but rows and per-broker impact come back for the winners only: each result has
@@ -387,15 +399,27 @@ class WhatIf:
         moves=(kinds): also each winner's moves (kas_solve_host_choose_moves; moves(), reassignment()); with rows=False no rows
         are fetched and assignment() raises.
         A rack criterion in `by` (abi.RACK_KEY_NAMES), or racks=True, adds the rack pass against the real racks (report_racks)
-        and ranks on its records too (kas_solve_host_choose_racks): each winner then also has the rack figures and rack_impact()."""
+        and ranks on its records too (kas_solve_host_choose_racks): each winner then also has the rack figures and rack_impact().
+        A topic criterion in `by` (abi.TOPIC_KEY_NAMES), or topics=True, adds the topic pass and ranks on its records too
+        (kas_solve_host_choose_topics, with the rack pass when a rack criterion is named or racks=True): each winner then also
+        has the topic figures and topic_impact()."""
         from . import native
         by = [by] if isinstance(by, str) else list(by)
         by_racks = self._criteria(by, racks)
+        by_topics = self._by_topics(by, topics)
         if not 1 <= len(by) <= abi.KAS_CHOOSE_MAX_KEYS:
             raise ValueError("by: one to four criteria")
         fb = self.flat_batch(variants)
         k = max(0, min(int(k), len(variants)))
         ml = None
+        if by_topics:
+            if moves is None and not rows:
+                raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
+            table, rack_names = self.report_racks(variants) if by_racks else (None, None)
+            ho, ch, ml, rk, tp = native.solve_host_choose_topics(fb, by, k, racks=by_racks, report_rack=table, rows=rows,
+                                                                 mask=None if moves is None else abi.move_mask(moves))
+            self._fb = fb
+            return [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_ok))]
         if by_racks:
             if moves is None and not rows:
                 raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
@@ -428,7 +452,7 @@ class WhatIf:
         return res
 
     def front(self, variants: Sequence[Variant], by: Sequence[str] = ("moved_replicas", "replica_spread"), within=None, k: int = 16,
-              moves=None, rows: bool = True, racks: bool = False) -> "Front":
+              moves=None, rows: bool = True, racks: bool = False, topics: bool = False) -> "Front":
         """The Pareto front of the variants, marked and ranked on the GPU (kas_solve_host_front): every variant that solves,
         respects the hard bounds in `within` ({criterion: limit}, e.g. {"max_inbound": 200}) and is beaten by no other such
         variant on all the criteria in `by` at once (abi.KEY_NAMES; one to four, smaller is better; of variants with identical
@@ -437,19 +461,26 @@ class WhatIf:
         carries n_ok, n_eligible, n_front (> len when k cut it) and classes: per variant "member", "dominated", "over_limit"
         or "failed".
         A rack criterion in `by` or `within` (abi.RACK_KEY_NAMES), or racks=True, adds the rack pass against the real racks and
-        marks and ranks on its records too (kas_solve_host_front_racks): members then also have the rack figures and rack_impact()."""
+        marks and ranks on its records too (kas_solve_host_front_racks): members then also have the rack figures and rack_impact().
+        A topic criterion in `by` or `within` (abi.TOPIC_KEY_NAMES), or topics=True, adds the topic pass and marks and ranks on
+        its records too (kas_solve_host_front_topics): members then also have the topic figures and topic_impact()."""
         from . import native
         by = [by] if isinstance(by, str) else list(by)
         within = dict(within or {})
         by_racks = self._criteria(by + list(within), racks)
+        by_topics = self._by_topics(by + list(within), topics)
         if not 1 <= len(by) <= abi.KAS_CHOOSE_MAX_KEYS:
             raise ValueError("by: one to four criteria")
         if len(within) > abi.KAS_CHOOSE_MAX_KEYS or any(int(v) < 0 for v in within.values()):
             raise ValueError("within: at most four bounds, none negative")
         fb = self.flat_batch(variants)
         k = max(0, min(int(k), len(variants)))
-        rk = rack_names = None
-        if by_racks:
+        rk = rack_names = tp = None
+        if by_topics:
+            table, rack_names = self.report_racks(variants) if by_racks else (None, None)
+            ho, ch, ml, rk, tp = native.solve_host_front_topics(fb, abi.topic_front_spec(by, within, k), racks=by_racks, report_rack=table,
+                                                                rows=rows, mask=None if moves is None else abi.move_mask(moves))
+        elif by_racks:
             table, rack_names = self.report_racks(variants)
             ho, ch, ml, rk = native.solve_host_front_racks(fb, abi.rack_front_spec(by, within, k), report_rack=table, rows=rows,
                                                            mask=None if moves is None else abi.move_mask(moves))
@@ -459,8 +490,8 @@ class WhatIf:
         res = Front()
         res.n_ok, res.n_eligible, res.n_front = ch.n_ok, ch.n_eligible, ch.n_front
         res.classes = [abi.FRONT_CLASSES[min(int(r), 0)] for r in ch.rank]
-        if by_racks:
-            res.extend(self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_front)))
+        if by_racks or by_topics:
+            res.extend(self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_front)))
             return res
         for j in range(min(k, ch.n_front)):
             s = int(ch.chosen[j])
