@@ -913,6 +913,89 @@ int kas_solve_host16_front_topics(kas_ctx* ctx, const kas_batch_desc* batch, con
                                   const kas_impact_tables* host_impact, const kas_moves* host_moves, const int32_t* report_rack,
                                   const kas_rack_tables* host_racks, const kas_topic_impact_tables* host_topics);
 
+/* ---- execution batches: a scenario's replica moves cut by per-broker caps, on the device (added under ABI v6: purely
+ * additive) ------------------------------------------------------------------------------------------------------------
+ * Nobody submits a move list of thousands of partitions to a live cluster as one reassignment: it is executed in batches,
+ * with a limit on how many replicas a broker may be receiving at a time, how many it may be giving up, and how many
+ * partitions a batch may hold.  Rows, C, O, clen, olen and "names a node" are exactly those of the kas_node_impact and
+ * kas_move sections above; only topics whose kas_topic_result.status == KAS_OK contribute.
+ * The *moves of a scenario* are its rows with the KAS_MOVE_REPLICAS flag, in (topic in descriptor order, row ascending)
+ * order: the list kas_moves_device produces under mask == KAS_MOVE_REPLICAS; move i of that list is move i here.  For move i
+ *   In(i)  = the set of nodes named by cells of O that are not in C,
+ *   Out(i) = the set of nodes named by cells of C that are not in O (a cell of C that names no node of the scenario — a
+ *            departed broker, KAS_CELL16_NONE — is in neither set: as kas_node_impact.outbound). */
+typedef struct kas_batch_spec {      /* 0 = no bound; negative, or all three 0, or reserved != 0: KAS_E_INVALID_ARG */
+  int32_t cap_inbound;               /* most moves of one batch that may have the same node in In()  */
+  int32_t cap_outbound;              /* ... in Out()                                                   */
+  int32_t max_moves;                 /* most moves in one batch                                        */
+  int32_t reserved;
+} kas_batch_spec;
+/* Batches are consecutive ranges of the move list, defined by this loop:
+ *   batch = empty; in[*] = out[*] = 0
+ *   for i in moves, in order:
+ *       why = MAX_MOVES if max_moves and batch.n_moves == max_moves
+ *             else INBOUND  if cap_inbound  and any b in In(i)  has in[b]  == cap_inbound
+ *             else OUTBOUND if cap_outbound and any b in Out(i) has out[b] == cap_outbound
+ *             else none                         (tested in this order; the first that fails names the reason)
+ *       if why: batch.closed_by = why; emit batch; batch = empty; in[*] = out[*] = 0
+ *       add i to batch: in[b]++ for b in In(i); out[b]++ for b in Out(i)
+ *   if batch not empty: batch.closed_by = END_OF_LIST; emit batch
+ * A move adds at most 1 per node to each counter, so with caps >= 1 every batch holds a move and every batch is maximal. */
+#define KAS_BATCH_END_OF_LIST 0
+#define KAS_BATCH_MAX_MOVES   1
+#define KAS_BATCH_INBOUND     2
+#define KAS_BATCH_OUTBOUND    3
+typedef struct kas_move_batch {      /* 32 bytes */
+  int32_t first_move, n_moves;       /* moves [first_move, first_move + n_moves) of the scenario's REPLICAS move list */
+  int32_t topic, partition;          /* of its first move, as kas_move.topic / .partition: a move list of ANY mask can be cut by these */
+  int32_t replicas;                  /* sum of |In(i)| over its moves */
+  int32_t max_inbound, max_outbound; /* max over nodes of the batch's counters */
+  int32_t closed_by;                 /* KAS_BATCH_* */
+} kas_move_batch;
+typedef struct kas_scenario_batches {/* 32 bytes, eight non-negative int32; all 0 for an empty slot or a scenario without moves */
+  int32_t n_batches;                 /* the TRUE count, whatever the room */
+  int32_t n_moves, replicas;         /* over all batches */
+  int32_t max_batch_moves, max_batch_replicas;
+  int32_t closed_by_max_moves, closed_by_inbound, closed_by_outbound;   /* batches closed for that reason */
+} kas_scenario_batches;
+/* Where the records go (device pointers for kas_batches_device / 16, host pointers for the host forms).  A fixed stride per
+ * listed scenario: the pass needs no second run and no scan between scenarios; a caller learns of truncation from
+ * n_batches > stride, and records at or beyond min(n_batches, stride) are not touched.  A list entry of -1 is an empty slot;
+ * a scenario may be listed twice (each listing gets a record and a block of its own); the same inputs give the same bytes. */
+typedef struct kas_batches {
+  kas_scenario_batches* scenarios;   /* [n]: one per LISTED scenario j */
+  kas_move_batch* batches;           /* listed scenario j owns batches[j*stride .. j*stride + min(n_batches, stride)) */
+  int64_t stride;                    /* >= 0; 0 with batches == NULL: the counts only */
+} kas_batches;
+/* A scenario's two counters per node live in the LDS next to the id lookup and the queue of moves: more nodes than this in
+ * a LISTED scenario are KAS_E_UNSUPPORTED ((160 KiB - the queue of lists 8 wide - 288 bytes) / 12 bytes a node: kas_batches.h). */
+#define KAS_BATCH_NODE_LIMIT 9362
+
+/* The batches of the plan's previous solve, from the tables it used.  select: a DEVICE array of n_select scenario indices
+ * (the chosen[] of a kas_choice is accepted as it is, with its -1 tail; an entry outside 0..S-1 is an empty slot).
+ * Asynchronous; ordering, first-call allocation and the alignment refusals are those of kas_moves_device.
+ * kas_batches_device16: the same for a plan of kas_plan_create16.
+ * Refused before any GPU work, in this order: KAS_E_INVALID_ARG for the spec, a negative stride, a NULL array the call writes
+ * (scenarios with n_select > 0; batches with stride > 0), misaligned pointers (records 4 bytes, cur / out to the cell
+ * size); KAS_E_UNSUPPORTED for a plan with a scenario of more than KAS_BATCH_NODE_LIMIT nodes (the list is on the device:
+ * every scenario of the plan counts), and for n_select x stride x 32 beyond 2^31 bytes. */
+int kas_batches_device(kas_plan* plan, const kas_tables* device_tables, const int32_t* select, int32_t n_select,
+                       const kas_batch_spec* spec, const kas_batches* device_out, void* hip_stream);
+int kas_batches_device16(kas_plan* plan, const kas_tables16* device_tables, const int32_t* select, int32_t n_select,
+                         const kas_batch_spec* spec, const kas_batches* device_out, void* hip_stream);
+
+/* The host call that returns batches: the batch is solved, every topic record and scenario record comes back, no rows do
+ * (host_tables->out may be NULL), plus the records of the scenarios in the HOST list select[0..n_select) (n_select < 0: every
+ * scenario, in order).  The pass runs where the moves pass of kas_solve_host_moves runs: behind every scenario range.
+ * Exactly the written records come back: n scenario records, and min(n_batches, stride) batch records per listed scenario.
+ * Refused before any GPU work, in this order: what kas_solve_host_select refuses; the spec; a negative stride; a NULL array
+ * the call writes; misaligned pointers (records 4 bytes); a list entry outside -1..S-1; KAS_E_UNSUPPORTED for a listed
+ * scenario of more than KAS_BATCH_NODE_LIMIT nodes; KAS_E_UNSUPPORTED for n_select x stride x 32 beyond 2^31 bytes. */
+int kas_solve_host_batches(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables, const int32_t* select,
+                           int32_t n_select, const kas_batch_spec* spec, const kas_batches* host_out);
+int kas_solve_host16_batches(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables, const int32_t* select,
+                             int32_t n_select, const kas_batch_spec* spec, const kas_batches* host_out);
+
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */
 int  kas_host_alloc(int64_t bytes, void** out_ptr);

@@ -427,6 +427,41 @@ def move_mask(kinds) -> int:
     return mask
 
 
+# execution batches (kas_batch_spec / kas_move_batch / kas_scenario_batches / kas_batches): a scenario's REPLICAS moves cut by caps
+KAS_BATCH_END_OF_LIST, KAS_BATCH_MAX_MOVES, KAS_BATCH_INBOUND, KAS_BATCH_OUTBOUND = 0, 1, 2, 3
+BATCH_CLOSED_BY = ("end_of_list", "max_moves", "inbound", "outbound")
+KAS_BATCH_NODE_LIMIT = 9362
+MOVE_BATCH_FIELDS = ("first_move", "n_moves", "topic", "partition", "replicas", "max_inbound", "max_outbound", "closed_by")
+SCENARIO_BATCHES_FIELDS = ("n_batches", "n_moves", "replicas", "max_batch_moves", "max_batch_replicas", "closed_by_max_moves",
+                           "closed_by_inbound", "closed_by_outbound")
+MOVE_BATCH_DTYPE = _np.dtype([(f, "<i4") for f in MOVE_BATCH_FIELDS])
+SCENARIO_BATCHES_DTYPE = _np.dtype([(f, "<i4") for f in SCENARIO_BATCHES_FIELDS])
+BATCHES_ENTRIES = ("kas_batches_device", "kas_batches_device16", "kas_solve_host_batches", "kas_solve_host16_batches")
+
+
+class BatchSpec(C.Structure):
+    _fields_ = [("cap_inbound", C.c_int32), ("cap_outbound", C.c_int32), ("max_moves", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Batches(C.Structure):
+    _fields_ = [("scenarios", C.c_void_p), ("batches", C.c_void_p), ("stride", C.c_int64)]
+
+
+def batch_spec(caps) -> "BatchSpec":
+    """kas_batch_spec from a BatchSpec or a dict with the keys inbound, outbound, max_moves (missing: 0 = no bound); other keys
+    raise ValueError.  The library refuses negative bounds and a spec without any bound."""
+    if isinstance(caps, BatchSpec):
+        return caps
+    caps = dict(caps)
+    unknown = set(caps) - {"inbound", "outbound", "max_moves"}
+    if unknown:
+        raise ValueError("unknown batch bound %s (inbound, outbound, max_moves)" % ", ".join(sorted(map(repr, unknown))))
+    spec = BatchSpec()
+    spec.cap_inbound, spec.cap_outbound, spec.max_moves = (int(caps.get(k, 0)) for k in ("inbound", "outbound", "max_moves"))
+    return spec
+
+
+assert MOVE_BATCH_DTYPE.itemsize == 32 and SCENARIO_BATCHES_DTYPE.itemsize == 32 and C.sizeof(BatchSpec) == 16 and C.sizeof(Batches) == 24
 assert MOVE_DTYPE.itemsize == C.sizeof(Move) == 16 and C.sizeof(Moves) == 56
 assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32
 assert RACK_IMPACT_DTYPE.itemsize == 32 and SCENARIO_RACK_IMPACT_DTYPE.itemsize == 64 and C.sizeof(RackTables) == 32

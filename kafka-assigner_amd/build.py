@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libkas_hip.so")
-SOURCES = ["kas_hip.hip", "kas_impact.hip", "kas_choose.hip", "kas_moves.hip", "kas_racks.hip", "kas_topics.hip"]
+SOURCES = ["kas_hip.hip", "kas_impact.hip", "kas_choose.hip", "kas_moves.hip", "kas_racks.hip", "kas_topics.hip",
+           "kas_batches.hip"]
 
 
 def hipcc() -> str:

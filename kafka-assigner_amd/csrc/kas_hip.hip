@@ -34,6 +34,7 @@
 #include "kas_choose.h"   // ranking and gathering the best scenarios: its kernels are kas_choose.hip's
 #include "kas_front.h"    // marking and ranking the Pareto front: kas_choose.hip's as well
 #include "kas_moves.h"    // the move list of a solve: its kernels are kas_moves.hip's
+#include "kas_batches.h"  // the execution batches of a solve: its kernel is kas_batches.hip's
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -399,7 +400,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_EVERY];            // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records, topic records (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_FINAL];            // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records, topic records, batch records (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -644,7 +645,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_EVERY; ++i) {
+  for (int i = 0; i < KAS_HB_FINAL; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -1636,6 +1637,20 @@ int kas_front_device16_topics(kas_plan* p, const kas_tables16* t16, const kas_im
 }
 
 // ---- the move list (kernels: kas_moves.hip) ----------------------------------------------------------------------------
+// the plan's scenario and segment tables on the device (the moves pass and the batches pass read them): blocking copies, once
+static int kas_moves_tables_ready(kas_plan* p) {
+  if (p->moves_ready) return KAS_E_OK;
+  const KasMovesPlan& mp = p->moves;
+  int rc;
+  if ((rc = kas_buf_reserve(&p->b_mv_scen, sizeof(KasMovesScen) * mp.scen.size(), p->allocs, "moves scenario table")) != KAS_E_OK) return rc;
+  if ((rc = kas_buf_reserve(&p->b_mv_segs, sizeof(KasMovesSeg) * mp.segs.size(), p->allocs, "moves segment table")) != KAS_E_OK) return rc;
+  if (!mp.scen.empty()) KAS_HIP_TRY(hipMemcpy(p->b_mv_scen.p, mp.scen.data(), sizeof(KasMovesScen) * mp.scen.size(), hipMemcpyHostToDevice));
+  if (!mp.segs.empty()) KAS_HIP_TRY(hipMemcpy(p->b_mv_segs.p, mp.segs.data(), sizeof(KasMovesSeg) * mp.segs.size(), hipMemcpyHostToDevice));
+  if (!p->ev_moves) KAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_moves, hipEventDisableTiming));
+  p->moves_ready = 1;
+  return KAS_E_OK;
+}
+
 static int kas_moves_impl(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_moves* mv, hipStream_t st) {
   const int32_t cell = p->cells16 ? 2 : 4;
   const char* bad = kas_moves_args_error(mv, cell);
@@ -1651,14 +1666,7 @@ static int kas_moves_impl(kas_plan* p, const kas_tables* t, const int32_t* selec
   if (p->n_scenarios > 0 && p->last_slot < 0) return set_error(KAS_E_INVALID_ARG, "kas_moves_device: the plan has no solve to list the moves of");
   KAS_HIP_TRY(hipSetDevice(p->ctx->device));
   int rc;
-  if (!p->moves_ready) {                                        // blocking copies, once: the plan's tables
-    if ((rc = kas_buf_reserve(&p->b_mv_scen, sizeof(KasMovesScen) * mp.scen.size(), p->allocs, "moves scenario table")) != KAS_E_OK) return rc;
-    if ((rc = kas_buf_reserve(&p->b_mv_segs, sizeof(KasMovesSeg) * mp.segs.size(), p->allocs, "moves segment table")) != KAS_E_OK) return rc;
-    if (!mp.scen.empty()) KAS_HIP_TRY(hipMemcpy(p->b_mv_scen.p, mp.scen.data(), sizeof(KasMovesScen) * mp.scen.size(), hipMemcpyHostToDevice));
-    if (!mp.segs.empty()) KAS_HIP_TRY(hipMemcpy(p->b_mv_segs.p, mp.segs.data(), sizeof(KasMovesSeg) * mp.segs.size(), hipMemcpyHostToDevice));
-    if (!p->ev_moves) KAS_HIP_TRY(hipEventCreateWithFlags(&p->ev_moves, hipEventDisableTiming));
-    p->moves_ready = 1;
-  }
+  if ((rc = kas_moves_tables_ready(p)) != KAS_E_OK) return rc;
   // the (listed scenario, item) table: sized at the first call for a list as long as the batch; a longer list grows it, behind
   // the pass that may still be using it
   const size_t entries = (size_t)(n_select > p->n_scenarios ? n_select : p->n_scenarios) * (size_t)mp.max_items + 1;
@@ -1698,6 +1706,59 @@ int kas_moves_device16(kas_plan* p, const kas_tables16* t16, const int32_t* sele
   if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_moves_device16 needs a plan of kas_plan_create16");
   const kas_tables t = kas_tables_of16(t16, nullptr);
   return kas_moves_impl(p, &t, select, n_select, mv, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+// ---- execution batches (kernel: kas_batches.hip) -------------------------------------------------------------------------
+// The batches of the plan's previous solve, from the tables `t` it used, for the device list `select`, into `o` (device
+// pointers), on `st`.  The pass reads the plan's moves tables and owns no scratch: it is ordered as a moves pass is.
+static int kas_batches_impl(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_batch_spec* sp,
+                            const kas_batches* o, hipStream_t st) {
+  const int32_t cell = p->cells16 ? 2 : 4;
+  const char* bad = kas_batches_args_error(sp, o, n_select);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (n_select < 0 || (n_select > 0 && !select)) return set_error(KAS_E_INVALID_ARG, "kas_batches_device: select == NULL / n_select < 0");
+  if (((uintptr_t)t->cur | (uintptr_t)t->out) % (uintptr_t)cell != 0 || (uintptr_t)select % 4 != 0)
+    return set_error(KAS_E_INVALID_ARG, "kas_batches_device: cur / out must be cell-aligned, select 4-byte aligned");
+  if (p->shape.n_max > KAS_BATCH_NODE_LIMIT) return set_error(KAS_E_UNSUPPORTED, KAS_BATCH_NODES_TEXT);
+  if (!kas_batches_room_ok(n_select, o->stride)) return set_error(KAS_E_UNSUPPORTED, KAS_BATCH_ROOM_TEXT);
+  if (p->n_scenarios > 0 && (!t->out || !t->topic_results || (p->shape.cur_need > 0 && !t->cur) || (p->shape.aux_need > 0 && !t->aux)))
+    return set_error(KAS_E_INVALID_ARG, "a table the batches pass reads is NULL");
+  if (p->n_scenarios > 0 && p->last_slot < 0) return set_error(KAS_E_INVALID_ARG, "kas_batches_device: the plan has no solve to cut the moves of");
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  int rc;
+  if ((rc = kas_moves_tables_ready(p)) != KAS_E_OK) return rc;
+  if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->moves_pending && p->moves_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_moves, 0));
+  KasBatchesLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.scen = (const KasMovesScen*)p->b_mv_scen.p; a.segs = (const KasMovesSeg*)p->b_mv_segs.p;
+  a.sdesc = (const kas_scenario_desc*)p->b_scen.p; a.node_id = (const int32_t*)p->b_node_id.p;
+  a.select = select;
+  a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.topic_results = t->topic_results;
+  a.scenarios = o->scenarios; a.batches = o->batches; a.stride = o->stride; a.spec = *sp;
+  a.n = n_select; a.S = p->n_scenarios; a.n_cap = p->shape.n_max; a.src16 = p->cells16;
+  a.lds = kas_batches_lds(a.n_cap, p->Wc <= 3 ? 3 : (p->Wc <= 5 ? 5 : 8), p->cells16);
+  const int e = kas_batches_launch(&a, p->Wc, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("batches pass: ") + hipGetErrorString((hipError_t)e));
+  KAS_HIP_TRY(hipEventRecord(p->ev_moves, st));                 // (a later solve waits for it as for a moves pass)
+  p->moves_stream = st;
+  p->moves_pending = 1;
+  return KAS_E_OK;
+}
+
+int kas_batches_device(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_batch_spec* sp,
+                       const kas_batches* o, void* hip_stream) {
+  if (!p || !t || !sp || !o) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_batches_device16");
+  return kas_batches_impl(p, t, select, n_select, sp, o, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+int kas_batches_device16(kas_plan* p, const kas_tables16* t16, const int32_t* select, int32_t n_select, const kas_batch_spec* sp,
+                         const kas_batches* o, void* hip_stream) {
+  if (!p || !t16 || !sp || !o) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_batches_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_batches_impl(p, &t, select, n_select, sp, o, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
 }
 
 static int kas_plan_times(kas_plan* p, double* fill_us, double* order_us, int* launches) {
@@ -1969,7 +2030,8 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
                                  const kas_choose_spec* spec = nullptr, const kas_choice* hch = nullptr, const kas_moves* hmv = nullptr,
                                  bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
                                  const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr, bool rack_keys = false,
-                                 bool topic_pass = false, const kas_topic_impact_tables* htp = nullptr, bool topic_keys = false) {
+                                 bool topic_pass = false, const kas_topic_impact_tables* htp = nullptr, bool topic_keys = false,
+                                 const kas_batch_spec* bsp = nullptr, const kas_batches* hbt = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -2006,6 +2068,10 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.topics = true; in.have_tp_tables = htp != nullptr;
     in.have_tp_topics = htp && htp->topics; in.have_tp_scenarios = htp && htp->scenarios;
   }
+  if (hbt) {                                                   // kas_solve_host_batches / 16: no rows, the list is the call's
+    in.batches = bsp; in.bt_out = hbt; in.bt_select = select; in.bt_n_select = n_select;
+    in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0;
+  }
   in.lane_order_ok = ctx->lds_lane_order_ok;
   for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
   if (const char* e = getenv("KAS_HOST_RANGES")) in.ranges_override = atoi(e);
@@ -2025,7 +2091,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_EVERY; ++i)
+  for (int i = 0; i < KAS_HB_FINAL; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -2236,6 +2302,31 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     if (he == hipSuccess) hip_ok((hipError_t)kas_moves_launch(&a, full.Wc, s0), "moves pass");
     copy(p_mvh, d_mvh, 16 * (size_t)(mv_n + 1), hipMemcpyDeviceToHost, s0, "download the move offsets");
   }
+  // the batches pass: one workgroup per listed scenario on s0, behind every range
+  const int64_t bt_n = hc.bt_n;
+  if (hbt && he == hipSuccess && fail_rc == KAS_E_OK) {
+    const KasMovesPlan& mp = hc.moves;
+    if (!mp.scen.empty()) copy(ctx->hbuf[KAS_HB_MV_SCEN].p, mp.scen.data(), sizeof(KasMovesScen) * mp.scen.size(), hipMemcpyHostToDevice, s0, "upload moves scenario table");
+    if (!mp.segs.empty()) copy(ctx->hbuf[KAS_HB_MV_SEGS].p, mp.segs.data(), sizeof(KasMovesSeg) * mp.segs.size(), hipMemcpyHostToDevice, s0, "upload moves segment table");
+    if (S > 0) copy(ctx->hbuf[KAS_HB_BT_SDESC].p, batch->scenarios, sizeof(kas_scenario_desc) * (size_t)S, hipMemcpyHostToDevice, s0, "upload scenario descriptors");
+    if (!native16 && batch->node_pool_len > 0)
+      copy(ctx->hbuf[KAS_HB_BT_NODE_ID].p, batch->node_id, 4 * (size_t)batch->node_pool_len, hipMemcpyHostToDevice, s0, "upload node ids");
+    if (bt_n > 0) copy(ctx->hbuf[KAS_HB_BT_SELECT].p, hc.bt_list.data(), 4 * (size_t)bt_n, hipMemcpyHostToDevice, s0, "upload the batches list");
+    for (int i = 0; K > 1 && i < K; ++i) hip_ok(hipStreamWaitEvent(s0, ctx->hev_done[i], 0), "wait");
+    KasBatchesLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.scen = (const KasMovesScen*)ctx->hbuf[KAS_HB_MV_SCEN].p; a.segs = (const KasMovesSeg*)ctx->hbuf[KAS_HB_MV_SEGS].p;
+    a.sdesc = (const kas_scenario_desc*)ctx->hbuf[KAS_HB_BT_SDESC].p; a.node_id = (const int32_t*)ctx->hbuf[KAS_HB_BT_NODE_ID].p;
+    a.select = (const int32_t*)ctx->hbuf[KAS_HB_BT_SELECT].p;
+    a.cur = native16 ? (const void*)d_cur16 : (const void*)d_cur;
+    a.out = native16 ? (const void*)d_out16 : (const void*)d_out;
+    a.aux = d_aux; a.topic_results = d_tr;
+    a.scenarios = (kas_scenario_batches*)ctx->hbuf[KAS_HB_BT_SCEN].p; a.batches = (kas_move_batch*)ctx->hbuf[KAS_HB_BT_BATCHES].p;
+    a.stride = hbt->stride; a.spec = *bsp;
+    a.n = (int32_t)bt_n; a.S = (int32_t)S; a.n_cap = hc.bt_n_cap; a.src16 = native16 ? 1 : 0;
+    a.lds = kas_batches_lds(a.n_cap, full.Wc <= 3 ? 3 : (full.Wc <= 5 ? 5 : 8), a.src16);
+    if (he == hipSuccess) hip_ok((hipError_t)kas_batches_launch(&a, full.Wc, s0), "batches pass");
+  }
   drain();
   if (he != hipSuccess || fail_rc != KAS_E_OK) return fail_rc != KAS_E_OK ? fail_rc : KAS_E_HIP;
   if (hch) {                                                   // exactly the chosen scenarios' rows and node blocks, through the staging
@@ -2315,6 +2406,18 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     }
     if (written > 0) copy(hmv->moves, d_moves, sizeof(kas_move) * (size_t)written, hipMemcpyDeviceToHost, s0, "download the moves");
     if (used > 0) copy(hmv->cells, ctx->hbuf[KAS_HB_MV_CELLS].p, out.cell * (size_t)used, hipMemcpyDeviceToHost, s0, "download the moves' cells");
+  }
+  // the batches: the scenario records, then exactly the batch records each listed scenario wrote
+  if (hbt && he == hipSuccess && bt_n > 0) {
+    if (hip_ok(hipMemcpy(hbt->scenarios, ctx->hbuf[KAS_HB_BT_SCEN].p, sizeof(kas_scenario_batches) * (size_t)bt_n, hipMemcpyDeviceToHost), "download scenario batches")) {
+      const kas_move_batch* d_b = (const kas_move_batch*)ctx->hbuf[KAS_HB_BT_BATCHES].p;
+      for (int64_t j = 0; j < bt_n && hbt->stride > 0 && he == hipSuccess; ++j) {
+        const int64_t nb = hbt->scenarios[j].n_batches;
+        if (nb < 0) return set_error(KAS_E_HIP, "internal: the batches pass left a negative count");
+        const int64_t w = nb < hbt->stride ? nb : hbt->stride;
+        if (w > 0) copy(hbt->batches + j * hbt->stride, d_b + j * hbt->stride, sizeof(kas_move_batch) * (size_t)w, hipMemcpyDeviceToHost, s0, "download batch records");
+      }
+    }
   }
   hip_ok(hipStreamSynchronize(s0), "hipStreamSynchronize");
   if (hch && he == hipSuccess && hc.ch_gather_rows) {
@@ -2396,6 +2499,24 @@ int kas_solve_host16_topic_impact(kas_ctx* ctx, const kas_batch_desc* batch, con
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, himp, nullptr, nullptr, nullptr, false, nullptr, nullptr,
                                nullptr, nullptr, false, true, htp);
+}
+
+int kas_solve_host_batches(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select, int32_t n_select,
+                           const kas_batch_spec* bsp, const kas_batches* hbt) {
+  if (!ctx || !batch || !h || !bsp || !hbt) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, select, n_select < 0 ? -1 : n_select, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr,
+                               nullptr, nullptr, false, false, nullptr, false, bsp, hbt);
+}
+
+int kas_solve_host16_batches(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
+                             const kas_batch_spec* bsp, const kas_batches* hbt) {
+  if (!ctx || !batch || !h16 || !bsp || !hbt) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr,
+                               nullptr, nullptr, false, false, nullptr, false, bsp, hbt);
 }
 
 int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,

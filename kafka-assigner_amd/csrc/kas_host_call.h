@@ -19,6 +19,7 @@
 #include "kas_front.h"         // the spec of kas_solve_host_front
 #include "kas_racks.h"         // the rack tables of kas_solve_host_rack_impact
 #include "kas_topics.h"        // the work list of kas_solve_host_topic_impact (its scratch decides a refusal)
+#include "kas_batches.h"       // the refusals and the LDS layout of kas_solve_host_batches
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -211,7 +212,13 @@ enum KasHostBuf {
   KAS_HB_LAST,                                      // the buffers of the calls above end here
   // kas_solve_host_topic_impact / 16 alone (behind KAS_HB_LAST, for the same reason)
   KAS_HB_TP_TOPICS = KAS_HB_LAST, KAS_HB_TP_SCEN,   // the topic records and the scenario topic records on the device
-  KAS_HB_EVERY
+  KAS_HB_EVERY,                                     // the buffers of the calls above end here
+  // kas_solve_host_batches / 16 alone (behind KAS_HB_EVERY, for the same reason; the moves pass's scenario and segment tables
+  // go where a moves call puts them, KAS_HB_MV_SCEN / KAS_HB_MV_SEGS)
+  KAS_HB_BT_SDESC = KAS_HB_EVERY, KAS_HB_BT_NODE_ID, // the scenario descriptors and (int32 cells) the node id tables of the whole call
+  KAS_HB_BT_SELECT,                                 // the list
+  KAS_HB_BT_SCEN, KAS_HB_BT_BATCHES,                // the scenario records and the batch records on the device
+  KAS_HB_FINAL
 };
 static inline bool kas_host_buf_pinned(int32_t id) {
   return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN ||
@@ -265,6 +272,12 @@ struct KasHostCallIn {
   // then follow the rack pass's, which follow the choice's and the moves'), and topic_keys beside rack_keys: the spec may name
   // topic criteria (KAS_KEY_TOPIC_BASE), which need `topics`.  Defaults: every decision above as it was.
   bool topic_keys = false;
+  // kas_solve_host_batches / 16: the batches pass behind the solve, for the list bt_select[0 .. bt_n_select) (host; < 0: every
+  // scenario); no rows come back (n_select is 0).  Defaults: no batches pass, and every decision above as it was.
+  const kas_batch_spec* batches = nullptr;
+  const kas_batches* bt_out = nullptr;
+  const int32_t* bt_select = nullptr;
+  int32_t bt_n_select = -1;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -294,7 +307,7 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_EVERY] = {};              // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_FINAL] = {};              // what to reserve of each buffer; 0: this call must not touch it
   // kas_solve_host_choose / 16
   KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
   int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
@@ -312,6 +325,10 @@ struct KasHostCall {
   KasRackPlan rack;                             // the report table and rack_off of the whole call
   // kas_solve_host_topic_impact / 16
   int64_t tp_region_ints = 0;                   // global counters the pass needs over the whole batch (the ranges' plans hold their own)
+  // kas_solve_host_batches / 16 (its segment tables are `moves`)
+  std::vector<int32_t> bt_list;                 // the list as it is uploaded
+  int64_t bt_n = 0;                             // listed scenarios
+  int32_t bt_n_cap = 0;                         // the most nodes of a listed scenario
 };
 
 // Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
@@ -455,6 +472,18 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     hc->mv_moves_cap = in.moves->moves_cap < hc->mv_room_moves ? in.moves->moves_cap : hc->mv_room_moves;
     hc->mv_cells_cap = in.moves->cells_cap < hc->mv_room_cells ? in.moves->cells_cap : hc->mv_room_cells;
   }
+  // batches, in the order include/kas_abi.h documents: the spec, the stride, the arrays, their alignment, the list, the node
+  // limit, the room
+  if (in.batches || in.bt_out) {
+    if (in.bt_n_select > 0 && !in.bt_select) return fail(KAS_E_INVALID_ARG, "kas_batches: select == NULL");
+    hc->bt_n = in.bt_n_select < 0 ? S : in.bt_n_select;
+    int code = KAS_E_OK;
+    const char* bad = kas_batches_list_error(b, in.bt_n_select < 0 ? nullptr : in.bt_select, hc->bt_n, in.batches, in.bt_out, &code, &hc->bt_n_cap);
+    if (bad[0]) return fail(code, bad);
+    hc->bt_list.clear();
+    for (int64_t j = 0; j < hc->bt_n; ++j) hc->bt_list.push_back(in.bt_n_select < 0 ? (int32_t)j : in.bt_select[j]);
+    kas_moves_plan_build(b, &hc->moves);
+  }
   if (in.racks && choose && (rc = rack_pass()) != KAS_E_OK) return rc;   // (behind a choice's refusals and its moves')
   if (in.topics && choose && (rc = topic_pass()) != KAS_E_OK) return rc; // (... and behind the rack pass's)
   // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
@@ -505,6 +534,15 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
   if (in.topics) {
     by[KAS_HB_TP_TOPICS] = sizeof(kas_topic_impact) * (size_t)(T + 1);
     by[KAS_HB_TP_SCEN] = sizeof(kas_scenario_topic_impact) * (size_t)(S + 1);
+  }
+  if (in.batches) {
+    by[KAS_HB_MV_SCEN] = sizeof(KasMovesScen) * (hc->moves.scen.size() + 1);
+    by[KAS_HB_MV_SEGS] = sizeof(KasMovesSeg) * (hc->moves.segs.size() + 1);
+    by[KAS_HB_BT_SDESC] = sizeof(kas_scenario_desc) * (size_t)(S + 1);
+    by[KAS_HB_BT_NODE_ID] = hc->native16 ? 0 : 4 * (size_t)(b->node_pool_len + 1);
+    by[KAS_HB_BT_SELECT] = 4 * (size_t)(hc->bt_n + 1);
+    by[KAS_HB_BT_SCEN] = sizeof(kas_scenario_batches) * (size_t)(hc->bt_n + 1);
+    by[KAS_HB_BT_BATCHES] = sizeof(kas_move_batch) * ((size_t)hc->bt_n * (size_t)in.bt_out->stride + 1);
   }
   if (in.front) {
     by[KAS_HB_FR_CLS] = 4 * (size_t)(S + 1);

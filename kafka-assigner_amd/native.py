@@ -40,6 +40,7 @@ SYMBOLS = [
     "kas_rank_device_topics", "kas_front_rank_device_topics", "kas_choose_device_topics", "kas_choose_device16_topics",
     "kas_front_device_topics", "kas_front_device16_topics", "kas_solve_host_choose_topics", "kas_solve_host16_choose_topics",
     "kas_solve_host_front_topics", "kas_solve_host16_front_topics",
+    "kas_batches_device", "kas_batches_device16", "kas_solve_host_batches", "kas_solve_host16_batches",
 ]
 
 _LIB = None
@@ -165,6 +166,13 @@ def load():
     for fn in (L.kas_solve_host_moves, L.kas_solve_host16_moves):
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.Moves)]
+    for fn in (L.kas_batches_device, L.kas_batches_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.c_void_p, C.c_int32, C.POINTER(abi.BatchSpec), C.POINTER(abi.Batches), C.c_void_p]
+    for fn in (L.kas_solve_host_batches, L.kas_solve_host16_batches):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.BatchSpec),
+                       C.POINTER(abi.Batches)]
     for fn in (L.kas_solve_host_choose_moves, L.kas_solve_host16_choose_moves):
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec),
@@ -460,6 +468,19 @@ class Plan:
         mv = abi.Moves(abi.move_mask(mask), 0, move_off or None, cell_off or None, moves or None, int(moves_cap), cells or None, int(cells_cap))
         fn = self._lib.kas_moves_device16 if self.cells16 else self._lib.kas_moves_device
         _check(fn(self._h, C.byref(t), select or None, int(n_select), C.byref(mv), C.c_void_p(stream) if stream else None))
+
+    def batches_device(self, caps, select: int, n_select: int, cur: int, out: int, topic_results: int, scenarios: int, batches: int = 0,
+                       stride: int = 0, aux: int = 0, stream: int = 0):
+        """kas_batches_device / 16: the execution batches (caps: abi.batch_spec) of this plan's previous solve for the scenarios in
+        the device array `select` (int32 [n_select]; a choice's chosen[] as it is) into the device arrays scenarios
+        (kas_scenario_batches [n_select]) and batches (kas_move_batch [n_select * stride]; 0 with stride 0: the counts only).
+        Raw device pointers (int)."""
+        t = abi.Tables()
+        t.cur = cur or None; t.out = out or None; t.aux = aux or None; t.topic_results = topic_results or None
+        spec = abi.batch_spec(caps)
+        o = abi.Batches(scenarios or None, batches or None, int(stride))
+        fn = self._lib.kas_batches_device16 if self.cells16 else self._lib.kas_batches_device
+        _check(fn(self._h, C.byref(t), select or None, int(n_select), C.byref(spec), C.byref(o), C.c_void_p(stream) if stream else None))
 
     def set_flags(self, flags: int):
         _check(self._lib.kas_plan_set_flags(self._h, flags))
@@ -857,6 +878,55 @@ def solve_host_moves(fb: FlatBatch, mask=("replicas",), select=None, cells16: bo
     _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
               -1 if sel is None else int(sel.size), C.byref(mv)))
     return ho, _trim(ml)
+
+
+@dataclass
+class BatchList:
+    """What a batches call leaves (include/kas_abi.h, kas_batches): one kas_scenario_batches per listed scenario, and listed
+    scenario j's first min(n_batches, stride) kas_move_batch records at batches[j * stride:]."""
+    spec: "abi.BatchSpec"
+    select: np.ndarray                   # the listed scenarios
+    scenarios: np.ndarray                # abi.SCENARIO_BATCHES_DTYPE [n]
+    batches: np.ndarray                  # abi.MOVE_BATCH_DTYPE [n * stride]
+    stride: int
+
+    def truncated(self, j: int) -> bool:
+        return int(self.scenarios["n_batches"][j]) > self.stride
+
+    def of(self, j: int) -> np.ndarray:
+        """the written records of listed scenario j"""
+        n = min(int(self.scenarios["n_batches"][j]), self.stride)
+        return self.batches[j * self.stride:j * self.stride + n]
+
+
+def solve_host_batches(fb: FlatBatch, caps, select=None, stride: int = 0, cells16: bool = False, ctx: Optional[DeviceContext] = None,
+                       fill: int = 0):
+    """kas_solve_host_batches / kas_solve_host16_batches: every scenario is solved and reports its records; no rows come back, but
+    the execution batches of the scenarios in `select` (None: every scenario) under `caps` (abi.batch_spec: a dict with inbound,
+    outbound, max_moves).  stride: room for batch records per listed scenario (0: the counts only).  fill: the int32 word the
+    output arrays hold before the call (tests: what the call does not write stays).  Returns (HostOutputs without rows, BatchList)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)                 # (held until the call returns: the table only borrows it)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    listed = np.arange(fb.n_scenarios, dtype=np.int32) if sel is None else sel
+    n, stride = int(listed.size), int(stride)
+    spec = abi.batch_spec(caps)
+    scen = np.full(max(n, 1), fill, abi.SCENARIO_BATCHES_DTYPE)[:n]
+    recs = np.full(max(n * max(stride, 0), 1), fill, abi.MOVE_BATCH_DTYPE)[:n * max(stride, 0)]
+    o = abi.Batches(scen.ctypes.data if n else None, recs.ctypes.data if recs.size else None, stride)
+    fn = L.kas_solve_host16_batches if cells16 else L.kas_solve_host_batches
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
+              -1 if sel is None else n, C.byref(spec), C.byref(o)))
+    return ho, BatchList(spec=spec, select=listed, scenarios=scen, batches=recs, stride=stride)
 
 
 def solve_host_choose_moves(fb: FlatBatch, keys, k: int, mask=("replicas",), rows: bool = True, cells16: bool = False,

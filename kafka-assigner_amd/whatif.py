@@ -43,6 +43,12 @@ moves=("replicas",) (kinds of abi.MOVE_KINDS: replicas, leader, order) asks for 
 on the GPU (include/kas_abi.h, kas_moves): results[0].moves() -> [(topic, partition, [new replicas], {kinds})] and
 results[0].reassignment() -> the Kafka reassignment JSON object of those partitions.  solve(..., moves=...) returns the moves of
 every variant and no rows (kas_solve_host_moves); best(..., moves=..., rows=False) those of the winners and no rows at all.
+
+batches={"inbound": 5, "outbound": 0, "max_moves": 0} cuts each variant's replica moves, on the GPU, into the consecutive execution
+batches a cluster would be given (include/kas_abi.h, kas_batch_spec: at most 5 moves of a batch bring a replica to the same broker;
+0 = no bound): results[0].n_batches, .max_batch_moves, ... and results[0].batches() -> [{"first_move", "n_moves", "topic",
+"partition", "replicas", "max_inbound", "max_outbound", "closed_by"}]; with moves=... as well, results[0].reassignment_batches()
+-> one Kafka reassignment JSON object per batch.  solve(), best() and front() take it alike.
 """
 from __future__ import annotations
 
@@ -115,6 +121,15 @@ class VariantResult:
     max_topic_leaders_after: Optional[int] = None
     sum_topic_replica_spread: Optional[int] = None
     sum_topic_leader_spread: Optional[int] = None
+    # batches=... (kas_scenario_batches); None without it
+    n_batches: Optional[int] = None              # the true count, whatever batch_room
+    batch_moves: Optional[int] = None            # replica moves over all batches
+    batch_replicas: Optional[int] = None         # replicas brokers receive over all batches
+    max_batch_moves: Optional[int] = None
+    max_batch_replicas: Optional[int] = None
+    closed_by_max_moves: Optional[int] = None    # batches closed for that reason
+    closed_by_inbound: Optional[int] = None
+    closed_by_outbound: Optional[int] = None
     rank: Optional[int] = None                   # best(): place among the variants that solve (0 = best); None from solve()
     _plan: "WhatIf" = field(repr=False, default=None)
     _index: int = field(repr=False, default=0)
@@ -128,6 +143,7 @@ class VariantResult:
     _rack_names: Optional[list] = field(repr=False, default=None)  # ... and the name of each rack index
     _topics: np.ndarray = field(repr=False, default=None)         # topics=True: this variant's kas_topic_impact records
     _topic_results: np.ndarray = field(repr=False, default=None)  # ... and its kas_topic_result records
+    _batches: np.ndarray = field(repr=False, default=None)        # batches=...: this variant's written kas_move_batch records
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -165,6 +181,41 @@ class VariantResult:
     def reassignment(self, kinds=None) -> dict:
         """The Kafka reassignment JSON object (version, partitions) holding the partitions of moves(kinds=kinds) only."""
         return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": reps} for t, p, reps, _ in self.moves(kinds=kinds)]}
+
+    def batches(self) -> List[dict]:
+        """[{first_move, n_moves, topic, partition, replicas, max_inbound, max_outbound, closed_by}]: this variant's execution
+        batches (batches=...), in order: consecutive ranges of its replica moves; topic and partition are those of a batch's first
+        move, closed_by one of abi.BATCH_CLOSED_BY.  min(n_batches, batch_room) of them."""
+        if self._batches is None:
+            raise ValueError("no batches: solve(..., batches={...}), best(..., batches={...}) or front(..., batches={...})")
+        names = self._plan.topic_names
+        out = []
+        for r in self._batches:
+            d = {f: int(r[f]) for f in abi.MOVE_BATCH_FIELDS}
+            d["topic"] = names[d["topic"]]
+            d["closed_by"] = abi.BATCH_CLOSED_BY[d["closed_by"]]
+            out.append(d)
+        return out
+
+    def reassignment_batches(self, kinds=None) -> List[dict]:
+        """One Kafka reassignment JSON object per execution batch (batches=... together with moves=...): the partitions of
+        moves(kinds=kinds), each in the batch that holds it — a replica move in the batch whose range of the replica move list
+        it lies in, any other move (a leader change, a reorder) with the replica move before it, or in the first batch.  The
+        objects' partitions, concatenated, are reassignment(kinds)'s.  Raises when n_batches exceeded batch_room."""
+        if self._batches is None:
+            raise ValueError("no batches: solve(..., batches={...}), best(..., batches={...}) or front(..., batches={...})")
+        if self.n_batches > len(self._batches):
+            raise ValueError("%d batches, room for %d: ask again with a larger batch_room" % (self.n_batches, len(self._batches)))
+        names = self._plan.topic_names
+        starts = [(int(r["topic"]), int(r["partition"])) for r in self._batches]       # ascending: the list is in (topic, partition) order
+        out = [{"version": 1, "partitions": []} for _ in range(max(len(starts), 1))]
+        at = 0
+        for t, p, reps, _ in self.moves(kinds=kinds):
+            key = (names.index(t), p)
+            while at + 1 < len(starts) and starts[at + 1] <= key:
+                at += 1
+            out[at]["partitions"].append({"topic": t, "partition": p, "replicas": reps})
+        return out if starts or out[0]["partitions"] else []
 
     def broker_impact(self) -> Dict[int, Dict[str, int]]:
         """broker id -> {replicas_before, replicas_after, leaders_before, leaders_after, inbound, outbound} under this
@@ -279,8 +330,34 @@ class WhatIf:
         return np.asarray(table, dtype=np.int32), names
 
     # ---- solve ---------------------------------------------------------------------------------
+    def _with_batches(self, fb, results, caps, room: int):
+        """the execution batches of `results` (one kas_solve_host_batches call over their variants, which downloads no rows)"""
+        if caps is None or not results:
+            return results
+        from . import native
+        _, bl = native.solve_host_batches(fb, caps, select=[r._index for r in results], stride=int(room))
+        for j, r in enumerate(results):
+            rec = bl.scenarios[j]
+            r.n_batches, r.batch_moves, r.batch_replicas = int(rec["n_batches"]), int(rec["n_moves"]), int(rec["replicas"])
+            r.max_batch_moves, r.max_batch_replicas = int(rec["max_batch_moves"]), int(rec["max_batch_replicas"])
+            r.closed_by_max_moves, r.closed_by_inbound = int(rec["closed_by_max_moves"]), int(rec["closed_by_inbound"])
+            r.closed_by_outbound = int(rec["closed_by_outbound"])
+            r._batches = bl.of(j)
+        return results
+
+    @staticmethod
+    def _batch_args(batches, batch_room):
+        """check batches= / batch_room= before anything is solved"""
+        if batches is None:
+            return
+        spec = abi.batch_spec(batches)
+        if min(spec.cap_inbound, spec.cap_outbound, spec.max_moves) < 0 or not (spec.cap_inbound or spec.cap_outbound or spec.max_moves):
+            raise ValueError("batches: bounds are >= 0 (0 = no bound) and at least one of inbound, outbound, max_moves is set")
+        if int(batch_room) < 0:
+            raise ValueError("batch_room: room for batch records per variant, >= 0")
+
     def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True, moves=None,
-              racks: bool = False, topics: bool = False) -> List[VariantResult]:
+              racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096) -> List[VariantResult]:
         """Solve every variant in one batch (default: the HIP path through the C ABI).
         impact=True: also the per-broker impact of every variant, computed on the GPU (kas_solve_host_impact).
         rows=False: no variant's rows come back (kas_solve_host_select / kas_solve_host_impact with n_select = 0) — the
@@ -291,8 +368,15 @@ class WhatIf:
         colocated_after, single_rack_rows_after, ... and rack_impact() then answer.
         topics=True (with or without impact, rows and racks; not with moves or solve_fn): also the topic pass
         (kas_solve_host_topic_impact): topics_moved, max_topic_inbound, max_topic_replica_spread, ... and topic_impact() then
-        answer.  Together with racks=True the topic records come from a second host call that downloads no rows."""
+        answer.  Together with racks=True the topic records come from a second host call that downloads no rows.
+        batches={"inbound": 5, ...} (abi.batch_spec; not with solve_fn): also every variant's execution batches
+        (kas_solve_host_batches): n_batches, max_batch_moves, ... and batches() then answer, and with moves=... as well
+        reassignment_batches(); batch_room: batch records kept per variant (n_batches is the true count whatever the room).
+        Like the topic records beside racks=True, they come from a second host call that downloads no rows."""
         from . import native
+        self._batch_args(batches, batch_room)
+        if batches is not None and solve_fn is not None:
+            raise ValueError("batches=... takes the library's own host call (no solve_fn)")
         fb = self.flat_batch(variants)
         nodes = scen_imp = ml = rk = rack_names = tp = None
         if topics and (moves is not None or solve_fn is not None):
@@ -352,7 +436,7 @@ class WhatIf:
                                      moved_replicas=int(sr["moved_replicas"]),
                                      moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]),
                                      _plan=self, _index=s, _out=ho.out if rows else None, **extra))
-        return res
+        return self._with_batches(fb, res, batches, batch_room)
 
     @staticmethod
     def _criteria(names, racks: bool) -> bool:
@@ -391,7 +475,7 @@ class WhatIf:
                              **extra)
 
     def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved"), moves=None,
-             rows: bool = True, racks: bool = False, topics: bool = False) -> List[VariantResult]:
+             rows: bool = True, racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096) -> List[VariantResult]:
         """The k best variants that solve, best first, chosen on the GPU (kas_solve_host_choose): variants are compared by the
         criteria named in `by` (abi.KEY_NAMES; one to four, smaller is better, the earlier variant wins a tie).  Every variant is
         solved and reduced to its records, but rows and per-broker impact come back for the winners only: each result has
@@ -402,8 +486,12 @@ class WhatIf:
         and ranks on its records too (kas_solve_host_choose_racks): each winner then also has the rack figures and rack_impact().
         A topic criterion in `by` (abi.TOPIC_KEY_NAMES), or topics=True, adds the topic pass and ranks on its records too
         (kas_solve_host_choose_topics, with the rack pass when a rack criterion is named or racks=True): each winner then also
-        has the topic figures and topic_impact()."""
+        has the topic figures and topic_impact().
+        batches={"inbound": 5, ...}: also each winner's execution batches (n_batches, ..., batches(), and with moves=...
+        reassignment_batches()), fetched with one kas_solve_host_batches call over the chosen: a second host call that downloads
+        no rows, as the topic records beside racks=True in solve()."""
         from . import native
+        self._batch_args(batches, batch_room)
         by = [by] if isinstance(by, str) else list(by)
         by_racks = self._criteria(by, racks)
         by_topics = self._by_topics(by, topics)
@@ -419,7 +507,8 @@ class WhatIf:
             ho, ch, ml, rk, tp = native.solve_host_choose_topics(fb, by, k, racks=by_racks, report_rack=table, rows=rows,
                                                                  mask=None if moves is None else abi.move_mask(moves))
             self._fb = fb
-            return [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_ok))]
+            return self._with_batches(fb, [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_ok))],
+                                      batches, batch_room)
         if by_racks:
             if moves is None and not rows:
                 raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
@@ -427,7 +516,8 @@ class WhatIf:
             ho, ch, ml, rk = native.solve_host_choose_racks(fb, by, k, report_rack=table, rows=rows,
                                                             mask=None if moves is None else abi.move_mask(moves))
             self._fb = fb
-            return [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_ok))]
+            return self._with_batches(fb, [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_ok))],
+                                      batches, batch_room)
         if moves is None:
             if not rows:
                 raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
@@ -449,10 +539,10 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
                                      _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
                                      **extra))
-        return res
+        return self._with_batches(fb, res, batches, batch_room)
 
     def front(self, variants: Sequence[Variant], by: Sequence[str] = ("moved_replicas", "replica_spread"), within=None, k: int = 16,
-              moves=None, rows: bool = True, racks: bool = False, topics: bool = False) -> "Front":
+              moves=None, rows: bool = True, racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096) -> "Front":
         """The Pareto front of the variants, marked and ranked on the GPU (kas_solve_host_front): every variant that solves,
         respects the hard bounds in `within` ({criterion: limit}, e.g. {"max_inbound": 200}) and is beaten by no other such
         variant on all the criteria in `by` at once (abi.KEY_NAMES; one to four, smaller is better; of variants with identical
@@ -463,8 +553,11 @@ class WhatIf:
         A rack criterion in `by` or `within` (abi.RACK_KEY_NAMES), or racks=True, adds the rack pass against the real racks and
         marks and ranks on its records too (kas_solve_host_front_racks): members then also have the rack figures and rack_impact().
         A topic criterion in `by` or `within` (abi.TOPIC_KEY_NAMES), or topics=True, adds the topic pass and marks and ranks on
-        its records too (kas_solve_host_front_topics): members then also have the topic figures and topic_impact()."""
+        its records too (kas_solve_host_front_topics): members then also have the topic figures and topic_impact().
+        batches={"inbound": 5, ...}: also each member's execution batches, as in best(): one kas_solve_host_batches call over the
+        members, a second host call that downloads no rows."""
         from . import native
+        self._batch_args(batches, batch_room)
         by = [by] if isinstance(by, str) else list(by)
         within = dict(within or {})
         by_racks = self._criteria(by + list(within), racks)
@@ -492,7 +585,7 @@ class WhatIf:
         res.classes = [abi.FRONT_CLASSES[min(int(r), 0)] for r in ch.rank]
         if by_racks or by_topics:
             res.extend(self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_front)))
-            return res
+            return self._with_batches(fb, res, batches, batch_room)
         for j in range(min(k, ch.n_front)):
             s = int(ch.chosen[j])
             sr = ho.scenario_results[s]
@@ -506,7 +599,7 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
                                      _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
                                      **extra))
-        return res
+        return self._with_batches(fb, res, batches, batch_room)
 
     def _rows(self, s: int, topic: str, out: np.ndarray, packed_at: Optional[int] = None) -> Dict[int, List[int]]:
         t = self.topic_names.index(topic)
