@@ -996,6 +996,87 @@ int kas_solve_host_batches(kas_ctx* ctx, const kas_batch_desc* batch, const kas_
 int kas_solve_host16_batches(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables, const int32_t* select,
                              int32_t n_select, const kas_batch_spec* spec, const kas_batches* host_out);
 
+/* ---- packed rounds: a scenario's replica moves scheduled under per-broker caps, on the device (added under ABI v6: purely
+ * additive) ------------------------------------------------------------------------------------------------------------
+ * Partition reassignments are independent of each other, so nothing forces a cluster to execute a move list in list order.
+ * A *round* is a set of moves executed together; the rounds pass gives every move of a scenario a round, so that in every
+ * round no node is in In() of more than cap_inbound moves nor in Out() of more than cap_outbound, in far fewer rounds than
+ * consecutive batches take.  Moves, In(i), Out(i), "names a node" and the contributing topics are exactly those of the
+ * batches section above; the list is kas_moves_device's under mask == KAS_MOVE_REPLICAS, move i of that list is move i here.
+ * (A bound on the moves of one round needs no scheduling: any round may be split into chunks without breaking a cap.) */
+typedef struct kas_round_spec {      /* 0 = no bound on that direction; negative, or both caps 0, or policy != 0, or reserved != 0: KAS_E_INVALID_ARG */
+  int32_t cap_inbound;               /* most moves of one round that may have the same node in In()  */
+  int32_t cap_outbound;              /* ... in Out()                                                   */
+  int32_t policy;                    /* KAS_ROUNDS_* */
+  int32_t reserved;
+} kas_round_spec;
+#define KAS_ROUNDS_MONOTONE 0
+/* Policy KAS_ROUNDS_MONOTONE — every node fills one round at a time and never returns to a round it left — is this loop:
+ *   rin[*] = rout[*] = 0; uin[*] = uout[*] = 0          (the round a node is filling, the moves it holds there)
+ *   for i in moves, in order:
+ *       r = 0
+ *       if cap_inbound:  for b in In(i):  r = max(r, uin[b]  < cap_inbound  ? rin[b]  : rin[b]  + 1)
+ *       if cap_outbound: for b in Out(i): r = max(r, uout[b] < cap_outbound ? rout[b] : rout[b] + 1)
+ *       round_of[i] = r
+ *       if cap_inbound:  for b in In(i):  if rin[b]  == r: uin[b]++   else: rin[b]  = r; uin[b]  = 1
+ *       if cap_outbound: for b in Out(i): if rout[b] == r: uout[b]++  else: rout[b] = r; uout[b] = 1
+ *   n_rounds = 1 + max round_of, or 0 without moves
+ * A (round, used) pair per node and direction suffices because a node never returns to a round it left; the price is room a true first
+ * fit over all rounds would have used (DESIGN.md 10.9 has both against the lower bound ceil(max per-node total / cap)). */
+typedef struct kas_move_round {      /* 16 bytes */
+  int32_t n_moves;                   /* moves of the round (>= 1: every round below n_rounds holds a move) */
+  int32_t replicas;                  /* sum of |In(i)| over them */
+  int32_t first_move;                /* the lowest list index of a move of the round */
+  int32_t reserved;                  /* 0 */
+} kas_move_round;
+typedef struct kas_scenario_rounds { /* 32 bytes, eight non-negative int32; all 0 for an empty slot or a scenario without moves */
+  int32_t n_rounds;                  /* the TRUE count, whatever the room */
+  int32_t n_moves, replicas;         /* over all rounds */
+  int32_t max_round_moves, max_round_replicas;
+  int32_t raised_by_inbound;         /* moves with r > 0 whose r an In node supplied */
+  int32_t raised_by_outbound;        /* moves with r > 0 that only an Out node reached */
+  int32_t reserved;                  /* 0 */
+} kas_scenario_rounds;
+/* Where the records go (device pointers for kas_rounds_device / 16, host pointers for the host forms).  Fixed strides per
+ * listed scenario, for the reasons of kas_batches; a caller learns of truncation from n_rounds > round_stride or
+ * n_moves > move_stride, and nothing at or beyond the written prefixes is touched.  Both strides 0: the counts only.  A list
+ * entry of -1 is an empty slot; a scenario may be listed twice; the same inputs give the same bytes. */
+typedef struct kas_rounds {
+  kas_scenario_rounds* scenarios;    /* [n]: one per LISTED scenario j */
+  kas_move_round* rounds;            /* listed j owns rounds[j*round_stride .. + min(n_rounds, round_stride)) */
+  int64_t round_stride;              /* >= 0; 0 with rounds == NULL: none */
+  int32_t* round_of;                 /* listed j owns round_of[j*move_stride .. + min(n_moves, move_stride)): the round of move i */
+  int64_t move_stride;               /* >= 0; 0 with round_of == NULL: none */
+} kas_rounds;
+/* A scenario's (round, used) pair per node and direction lives in the LDS, packed into one 32-bit word, next to the id lookup,
+ * the queue of moves and a window of round counters: more nodes than this in a LISTED scenario are KAS_E_UNSUPPORTED ((160 KiB -
+ * the queue of lists 8 wide - the window - 288 bytes) / 12 bytes a node: kas_rounds.h).  The word gives the round the bits that
+ * hold the scenario's row count P and `used` the rest: a cap above P never binds and is applied as no bound; any other cap of
+ * 2^(32 - bits(P)) or more is KAS_E_UNSUPPORTED too (it takes a scenario of 65,536 rows or more and a cap of 32,768 or more). */
+#define KAS_ROUND_NODE_LIMIT 9192
+
+/* The rounds of the plan's previous solve, from the tables it used: the counterpart of kas_batches_device, with the same
+ * list conventions (a DEVICE select[], a choice's chosen[] as it is), the same ordering (it waits for and re-records what a
+ * moves pass does; a later solve waits for it) and the same refusals in the same order: KAS_E_INVALID_ARG for the spec, a
+ * negative stride, a NULL array the call writes (scenarios with n_select > 0; rounds with round_stride > 0; round_of with
+ * move_stride > 0), misaligned pointers; KAS_E_UNSUPPORTED for a plan with a scenario of more than KAS_ROUND_NODE_LIMIT nodes,
+ * for a cap that does not fit a scenario's round words, and for n_select x round_stride x 16 or n_select x move_stride x 4 beyond 2^31 bytes. */
+int kas_rounds_device(kas_plan* plan, const kas_tables* device_tables, const int32_t* select, int32_t n_select,
+                      const kas_round_spec* spec, const kas_rounds* device_out, void* hip_stream);
+int kas_rounds_device16(kas_plan* plan, const kas_tables16* device_tables, const int32_t* select, int32_t n_select,
+                        const kas_round_spec* spec, const kas_rounds* device_out, void* hip_stream);
+
+/* The host call that returns rounds: the counterpart of kas_solve_host_batches (no rows come back; a HOST list, n_select < 0:
+ * every scenario; the pass runs behind every scenario range).  Exactly the written prefixes come back.  Refused before any GPU
+ * work, in this order: what kas_solve_host_select refuses; the spec; a negative stride; a NULL array the call writes;
+ * misaligned pointers (4 bytes); a list entry outside -1..S-1; KAS_E_UNSUPPORTED for a listed scenario of more than
+ * KAS_ROUND_NODE_LIMIT nodes; KAS_E_UNSUPPORTED for a cap that does not fit a listed scenario's round words;
+ * KAS_E_UNSUPPORTED for either stride's room. */
+int kas_solve_host_rounds(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* host_tables, const int32_t* select,
+                          int32_t n_select, const kas_round_spec* spec, const kas_rounds* host_out);
+int kas_solve_host16_rounds(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* host_tables, const int32_t* select,
+                            int32_t n_select, const kas_round_spec* spec, const kas_rounds* host_out);
+
 /* Pinned host memory for table pools (DMA without staging: see kas_solve_host).  A JNI caller wraps
  * it with NewDirectByteBuffer, a Python caller with numpy.frombuffer. */
 int  kas_host_alloc(int64_t bytes, void** out_ptr);

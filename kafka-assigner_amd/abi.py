@@ -461,6 +461,41 @@ def batch_spec(caps) -> "BatchSpec":
     return spec
 
 
+# packed rounds (kas_round_spec / kas_move_round / kas_scenario_rounds / kas_rounds): a scenario's REPLICAS moves scheduled under caps
+KAS_ROUNDS_MONOTONE = 0
+KAS_ROUND_NODE_LIMIT = 9192
+MOVE_ROUND_FIELDS = ("n_moves", "replicas", "first_move", "reserved")
+SCENARIO_ROUNDS_FIELDS = ("n_rounds", "n_moves", "replicas", "max_round_moves", "max_round_replicas", "raised_by_inbound",
+                          "raised_by_outbound", "reserved")
+MOVE_ROUND_DTYPE = _np.dtype([(f, "<i4") for f in MOVE_ROUND_FIELDS])
+SCENARIO_ROUNDS_DTYPE = _np.dtype([(f, "<i4") for f in SCENARIO_ROUNDS_FIELDS])
+ROUNDS_ENTRIES = ("kas_rounds_device", "kas_rounds_device16", "kas_solve_host_rounds", "kas_solve_host16_rounds")
+
+
+class RoundSpec(C.Structure):
+    _fields_ = [("cap_inbound", C.c_int32), ("cap_outbound", C.c_int32), ("policy", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Rounds(C.Structure):
+    _fields_ = [("scenarios", C.c_void_p), ("rounds", C.c_void_p), ("round_stride", C.c_int64), ("round_of", C.c_void_p),
+                ("move_stride", C.c_int64)]
+
+
+def round_spec(caps) -> "RoundSpec":
+    """kas_round_spec from a RoundSpec or a dict with the keys inbound, outbound (missing: 0 = no bound) and policy (missing:
+    KAS_ROUNDS_MONOTONE); other keys raise ValueError.  The library refuses negative caps and a spec without any cap."""
+    if isinstance(caps, RoundSpec):
+        return caps
+    caps = dict(caps)
+    unknown = set(caps) - {"inbound", "outbound", "policy"}
+    if unknown:
+        raise ValueError("unknown round bound %s (inbound, outbound, policy)" % ", ".join(sorted(map(repr, unknown))))
+    spec = RoundSpec()
+    spec.cap_inbound, spec.cap_outbound, spec.policy = (int(caps.get(k, 0)) for k in ("inbound", "outbound", "policy"))
+    return spec
+
+
+assert MOVE_ROUND_DTYPE.itemsize == 16 and SCENARIO_ROUNDS_DTYPE.itemsize == 32 and C.sizeof(RoundSpec) == 16 and C.sizeof(Rounds) == 40
 assert MOVE_BATCH_DTYPE.itemsize == 32 and SCENARIO_BATCHES_DTYPE.itemsize == 32 and C.sizeof(BatchSpec) == 16 and C.sizeof(Batches) == 24
 assert MOVE_DTYPE.itemsize == C.sizeof(Move) == 16 and C.sizeof(Moves) == 56
 assert NODE_IMPACT_DTYPE.itemsize == 32 and SCENARIO_IMPACT_DTYPE.itemsize == 32

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libkas_hip.so")
 SOURCES = ["kas_hip.hip", "kas_impact.hip", "kas_choose.hip", "kas_moves.hip", "kas_racks.hip", "kas_topics.hip",
-           "kas_batches.hip"]
+           "kas_batches.hip", "kas_rounds.hip"]
 
 
 def hipcc() -> str:

@@ -35,6 +35,7 @@
 #include "kas_front.h"    // marking and ranking the Pareto front: kas_choose.hip's as well
 #include "kas_moves.h"    // the move list of a solve: its kernels are kas_moves.hip's
 #include "kas_batches.h"  // the execution batches of a solve: its kernel is kas_batches.hip's
+#include "kas_rounds.h"   // the packed rounds of a solve: its kernel is kas_rounds.hip's
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -400,7 +401,7 @@ struct kas_ctx {
   hipStream_t hup, hdown;
   hipEvent_t hev_up[KAS_HOST_STREAMS], hev_done[KAS_HOST_STREAMS];
   std::mutex host_mu;                   // kas_solve_host calls on one context are serialised
-  KasBuf hbuf[KAS_HB_FINAL];            // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records, topic records, batch records (KasHostBuf, kas_host_call.h)
+  KasBuf hbuf[KAS_HB_BUFFERS];            // device pools, record staging, impact records, a choice and its staging, a move list, a front's classes and counts, rack records, topic records, batch records, round records (KasHostBuf, kas_host_call.h)
   std::vector<int32_t> ident_ids;       // node_id pool of a 16-bit call: node i of every scenario has id i
   uint64_t ident_stamp = 0;             // ... and which node ranges it was filled for (kas_ident_batch)
   KasCachedPlan plans[KAS_HOST_PLAN_CACHE];
@@ -645,7 +646,7 @@ void kas_ctx_destroy(kas_ctx* ctx) {
   if (ctx->hup) (void)hipStreamSynchronize(ctx->hup);
   if (ctx->hdown) (void)hipStreamSynchronize(ctx->hdown);
   for (KasCachedPlan& c : ctx->plans) if (c.plan) kas_plan_destroy(c.plan);
-  for (int i = 0; i < KAS_HB_FINAL; ++i) {
+  for (int i = 0; i < KAS_HB_BUFFERS; ++i) {
     KasBuf* b = &ctx->hbuf[i];
     if (!kas_host_buf_pinned(i)) { kas_buf_free(b); continue; }
     if (b->p) (void)hipHostFree(b->p);
@@ -1761,6 +1762,62 @@ int kas_batches_device16(kas_plan* p, const kas_tables16* t16, const int32_t* se
   return kas_batches_impl(p, &t, select, n_select, sp, o, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
 }
 
+// ---- packed rounds (kernel: kas_rounds.hip) ------------------------------------------------------------------------------
+// The rounds of the plan's previous solve: kas_batches_impl with the round spec, the two strides and KAS_ROUND_NODE_LIMIT.
+static int kas_rounds_impl(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_round_spec* sp,
+                           const kas_rounds* o, hipStream_t st) {
+  const int32_t cell = p->cells16 ? 2 : 4;
+  const char* bad = kas_rounds_args_error(sp, o, n_select);
+  if (bad[0]) return set_error(KAS_E_INVALID_ARG, bad);
+  if (n_select < 0 || (n_select > 0 && !select)) return set_error(KAS_E_INVALID_ARG, "kas_rounds_device: select == NULL / n_select < 0");
+  if (((uintptr_t)t->cur | (uintptr_t)t->out) % (uintptr_t)cell != 0 || (uintptr_t)select % 4 != 0)
+    return set_error(KAS_E_INVALID_ARG, "kas_rounds_device: cur / out must be cell-aligned, select 4-byte aligned");
+  if (p->shape.n_max > KAS_ROUND_NODE_LIMIT) return set_error(KAS_E_UNSUPPORTED, KAS_ROUND_NODES_TEXT);
+  for (int32_t s = 0; s < p->n_scenarios; ++s)                  // (the list is on the device: every scenario of the plan counts)
+    if (!kas_rounds_caps_fit(sp, p->moves.scen.data(), p->moves.segs.data(), s)) return set_error(KAS_E_UNSUPPORTED, KAS_ROUND_CAPS_TEXT);
+  bad = kas_rounds_room_error(n_select, o);
+  if (bad[0]) return set_error(KAS_E_UNSUPPORTED, bad);
+  if (p->n_scenarios > 0 && (!t->out || !t->topic_results || (p->shape.cur_need > 0 && !t->cur) || (p->shape.aux_need > 0 && !t->aux)))
+    return set_error(KAS_E_INVALID_ARG, "a table the rounds pass reads is NULL");
+  if (p->n_scenarios > 0 && p->last_slot < 0) return set_error(KAS_E_INVALID_ARG, "kas_rounds_device: the plan has no solve to schedule the moves of");
+  KAS_HIP_TRY(hipSetDevice(p->ctx->device));
+  int rc;
+  if ((rc = kas_moves_tables_ready(p)) != KAS_E_OK) return rc;
+  if (p->last_slot >= 0 && p->last_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_stop[p->last_slot], 0));
+  if (p->moves_pending && p->moves_stream != st) KAS_HIP_TRY(hipStreamWaitEvent(st, p->ev_moves, 0));
+  KasRoundsLaunch a;
+  memset(&a, 0, sizeof(a));
+  a.scen = (const KasMovesScen*)p->b_mv_scen.p; a.segs = (const KasMovesSeg*)p->b_mv_segs.p;
+  a.sdesc = (const kas_scenario_desc*)p->b_scen.p; a.node_id = (const int32_t*)p->b_node_id.p;
+  a.select = select;
+  a.cur = t->cur; a.out = t->out; a.aux = t->aux; a.topic_results = t->topic_results;
+  a.scenarios = o->scenarios; a.rounds = o->rounds; a.round_of = o->round_of;
+  a.round_stride = o->round_stride; a.move_stride = o->move_stride; a.spec = *sp;
+  a.n = n_select; a.S = p->n_scenarios; a.n_cap = p->shape.n_max; a.src16 = p->cells16;
+  a.lds = kas_rounds_lds(a.n_cap, p->Wc <= 3 ? 3 : (p->Wc <= 5 ? 5 : 8), p->cells16);
+  const int e = kas_rounds_launch(&a, p->Wc, st);
+  if (e != 0) return set_error(KAS_E_HIP, std::string("rounds pass: ") + hipGetErrorString((hipError_t)e));
+  KAS_HIP_TRY(hipEventRecord(p->ev_moves, st));                 // (a later solve waits for it as for a moves pass)
+  p->moves_stream = st;
+  p->moves_pending = 1;
+  return KAS_E_OK;
+}
+
+int kas_rounds_device(kas_plan* p, const kas_tables* t, const int32_t* select, int32_t n_select, const kas_round_spec* sp,
+                      const kas_rounds* o, void* hip_stream) {
+  if (!p || !t || !sp || !o) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (p->cells16) return set_error(KAS_E_INVALID_ARG, "a plan of kas_plan_create16 takes kas_rounds_device16");
+  return kas_rounds_impl(p, t, select, n_select, sp, o, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
+int kas_rounds_device16(kas_plan* p, const kas_tables16* t16, const int32_t* select, int32_t n_select, const kas_round_spec* sp,
+                        const kas_rounds* o, void* hip_stream) {
+  if (!p || !t16 || !sp || !o) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  if (!p->cells16) return set_error(KAS_E_INVALID_ARG, "kas_rounds_device16 needs a plan of kas_plan_create16");
+  const kas_tables t = kas_tables_of16(t16, nullptr);
+  return kas_rounds_impl(p, &t, select, n_select, sp, o, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+}
+
 static int kas_plan_times(kas_plan* p, double* fill_us, double* order_us, int* launches) {
   *fill_us = 0.0; *order_us = 0.0; *launches = 0;
   KAS_HIP_TRY(hipSetDevice(p->ctx->device));
@@ -2031,7 +2088,8 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
                                  bool rows_optional = false, const kas_front_spec* front = nullptr, int32_t* counts = nullptr,
                                  const kas_rack_tables* hrk = nullptr, const int32_t* report_rack = nullptr, bool rack_keys = false,
                                  bool topic_pass = false, const kas_topic_impact_tables* htp = nullptr, bool topic_keys = false,
-                                 const kas_batch_spec* bsp = nullptr, const kas_batches* hbt = nullptr) {
+                                 const kas_batch_spec* bsp = nullptr, const kas_batches* hbt = nullptr,
+                                 const kas_round_spec* rsp = nullptr, const kas_rounds* hrd = nullptr) {
   KAS_HIP_TRY(hipSetDevice(ctx->device));
   ctx->host_calls += 1;
   KasHostCallIn in;
@@ -2072,6 +2130,10 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     in.batches = bsp; in.bt_out = hbt; in.bt_select = select; in.bt_n_select = n_select;
     in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0;
   }
+  if (hrd) {                                                   // kas_solve_host_rounds / 16: the same
+    in.rounds = rsp; in.rd_out = hrd; in.rd_select = select; in.rd_n_select = n_select;
+    in.select = nullptr; in.n_select = 0; select = nullptr; n_select = 0;
+  }
   in.lane_order_ok = ctx->lds_lane_order_ok;
   for (int Wc : {2, 3, 4, 5, 8}) in.built16[Wc] = kas_built_mask(Wc, 1);
   if (const char* e = getenv("KAS_HOST_RANGES")) in.ranges_override = atoi(e);
@@ -2091,7 +2153,7 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
   // (pageable) memory even when its bulk tables are pinned, and a copy to pageable memory blocks the issuing thread
   // until the stream gets there — every range's records would hold the next range's upload back until its own solve
   // has finished (a memory-copy trace of the plain path showed exactly that: uploads 2-3 ms apart).
-  for (int i = 0; i < KAS_HB_FINAL; ++i)
+  for (int i = 0; i < KAS_HB_BUFFERS; ++i)
     if ((rc = kas_host_reserve(ctx, i, hc.bytes[i])) != KAS_E_OK) return rc;
   // device pools: the pointers are rebased so that the descriptors' absolute offsets apply (nullptr: not this call's)
   auto rebased = [&](int id, int64_t cell, int64_t lo) { return hc.bytes[id] ? (char*)ctx->hbuf[id].p - cell * lo : nullptr; };
@@ -2327,6 +2389,32 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
     a.lds = kas_batches_lds(a.n_cap, full.Wc <= 3 ? 3 : (full.Wc <= 5 ? 5 : 8), a.src16);
     if (he == hipSuccess) hip_ok((hipError_t)kas_batches_launch(&a, full.Wc, s0), "batches pass");
   }
+  // the rounds pass: where the batches pass runs, from the same tables
+  const int64_t rd_n = hc.rd_n;
+  if (hrd && he == hipSuccess && fail_rc == KAS_E_OK) {
+    const KasMovesPlan& mp = hc.moves;
+    if (!mp.scen.empty()) copy(ctx->hbuf[KAS_HB_MV_SCEN].p, mp.scen.data(), sizeof(KasMovesScen) * mp.scen.size(), hipMemcpyHostToDevice, s0, "upload moves scenario table");
+    if (!mp.segs.empty()) copy(ctx->hbuf[KAS_HB_MV_SEGS].p, mp.segs.data(), sizeof(KasMovesSeg) * mp.segs.size(), hipMemcpyHostToDevice, s0, "upload moves segment table");
+    if (S > 0) copy(ctx->hbuf[KAS_HB_BT_SDESC].p, batch->scenarios, sizeof(kas_scenario_desc) * (size_t)S, hipMemcpyHostToDevice, s0, "upload scenario descriptors");
+    if (!native16 && batch->node_pool_len > 0)
+      copy(ctx->hbuf[KAS_HB_BT_NODE_ID].p, batch->node_id, 4 * (size_t)batch->node_pool_len, hipMemcpyHostToDevice, s0, "upload node ids");
+    if (rd_n > 0) copy(ctx->hbuf[KAS_HB_BT_SELECT].p, hc.rd_list.data(), 4 * (size_t)rd_n, hipMemcpyHostToDevice, s0, "upload the rounds list");
+    for (int i = 0; K > 1 && i < K; ++i) hip_ok(hipStreamWaitEvent(s0, ctx->hev_done[i], 0), "wait");
+    KasRoundsLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.scen = (const KasMovesScen*)ctx->hbuf[KAS_HB_MV_SCEN].p; a.segs = (const KasMovesSeg*)ctx->hbuf[KAS_HB_MV_SEGS].p;
+    a.sdesc = (const kas_scenario_desc*)ctx->hbuf[KAS_HB_BT_SDESC].p; a.node_id = (const int32_t*)ctx->hbuf[KAS_HB_BT_NODE_ID].p;
+    a.select = (const int32_t*)ctx->hbuf[KAS_HB_BT_SELECT].p;
+    a.cur = native16 ? (const void*)d_cur16 : (const void*)d_cur;
+    a.out = native16 ? (const void*)d_out16 : (const void*)d_out;
+    a.aux = d_aux; a.topic_results = d_tr;
+    a.scenarios = (kas_scenario_rounds*)ctx->hbuf[KAS_HB_RD_SCEN].p; a.rounds = (kas_move_round*)ctx->hbuf[KAS_HB_RD_ROUNDS].p;
+    a.round_of = (int32_t*)ctx->hbuf[KAS_HB_RD_OF].p;
+    a.round_stride = hrd->round_stride; a.move_stride = hrd->move_stride; a.spec = *rsp;
+    a.n = (int32_t)rd_n; a.S = (int32_t)S; a.n_cap = hc.rd_n_cap; a.src16 = native16 ? 1 : 0;
+    a.lds = kas_rounds_lds(a.n_cap, full.Wc <= 3 ? 3 : (full.Wc <= 5 ? 5 : 8), a.src16);
+    if (he == hipSuccess) hip_ok((hipError_t)kas_rounds_launch(&a, full.Wc, s0), "rounds pass");
+  }
   drain();
   if (he != hipSuccess || fail_rc != KAS_E_OK) return fail_rc != KAS_E_OK ? fail_rc : KAS_E_HIP;
   if (hch) {                                                   // exactly the chosen scenarios' rows and node blocks, through the staging
@@ -2416,6 +2504,20 @@ static int kas_solve_host_locked(kas_ctx* ctx, const kas_batch_desc* batch, cons
         if (nb < 0) return set_error(KAS_E_HIP, "internal: the batches pass left a negative count");
         const int64_t w = nb < hbt->stride ? nb : hbt->stride;
         if (w > 0) copy(hbt->batches + j * hbt->stride, d_b + j * hbt->stride, sizeof(kas_move_batch) * (size_t)w, hipMemcpyDeviceToHost, s0, "download batch records");
+      }
+    }
+  }
+  // the rounds: the scenario records, then exactly the round records and the round_of prefix each listed scenario wrote
+  if (hrd && he == hipSuccess && rd_n > 0) {
+    if (hip_ok(hipMemcpy(hrd->scenarios, ctx->hbuf[KAS_HB_RD_SCEN].p, sizeof(kas_scenario_rounds) * (size_t)rd_n, hipMemcpyDeviceToHost), "download scenario rounds")) {
+      const kas_move_round* d_r = (const kas_move_round*)ctx->hbuf[KAS_HB_RD_ROUNDS].p;
+      const int32_t* d_of = (const int32_t*)ctx->hbuf[KAS_HB_RD_OF].p;
+      for (int64_t j = 0; j < rd_n && he == hipSuccess; ++j) {
+        const int64_t nr = hrd->scenarios[j].n_rounds, nm = hrd->scenarios[j].n_moves;
+        if (nr < 0 || nm < 0) return set_error(KAS_E_HIP, "internal: the rounds pass left a negative count");
+        const int64_t wr = nr < hrd->round_stride ? nr : hrd->round_stride, wm = nm < hrd->move_stride ? nm : hrd->move_stride;
+        if (wr > 0) copy(hrd->rounds + j * hrd->round_stride, d_r + j * hrd->round_stride, sizeof(kas_move_round) * (size_t)wr, hipMemcpyDeviceToHost, s0, "download round records");
+        if (wm > 0) copy(hrd->round_of + j * hrd->move_stride, d_of + j * hrd->move_stride, 4 * (size_t)wm, hipMemcpyDeviceToHost, s0, "download round_of");
       }
     }
   }
@@ -2517,6 +2619,24 @@ int kas_solve_host16_batches(kas_ctx* ctx, const kas_batch_desc* batch, const ka
   std::lock_guard<std::mutex> lock(ctx->host_mu);
   return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr,
                                nullptr, nullptr, false, false, nullptr, false, bsp, hbt);
+}
+
+int kas_solve_host_rounds(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const int32_t* select, int32_t n_select,
+                          const kas_round_spec* rsp, const kas_rounds* hrd) {
+  if (!ctx || !batch || !h || !rsp || !hrd) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, h, select, n_select < 0 ? -1 : n_select, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr,
+                               nullptr, nullptr, false, false, nullptr, false, nullptr, nullptr, rsp, hrd);
+}
+
+int kas_solve_host16_rounds(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables16* h16, const int32_t* select, int32_t n_select,
+                            const kas_round_spec* rsp, const kas_rounds* hrd) {
+  if (!ctx || !batch || !h16 || !rsp || !hrd) return set_error(KAS_E_INVALID_ARG, "NULL argument");
+  KasCells16 c16;
+  const kas_tables h = kas_tables_of16(h16, &c16);
+  std::lock_guard<std::mutex> lock(ctx->host_mu);
+  return kas_solve_host_locked(ctx, batch, &h, select, n_select < 0 ? -1 : n_select, &c16, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr,
+                               nullptr, nullptr, false, false, nullptr, false, nullptr, nullptr, rsp, hrd);
 }
 
 int kas_solve_host_choose(kas_ctx* ctx, const kas_batch_desc* batch, const kas_tables* h, const kas_choose_spec* spec, const kas_choice* hch,

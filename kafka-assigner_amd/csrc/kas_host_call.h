@@ -20,6 +20,7 @@
 #include "kas_racks.h"         // the rack tables of kas_solve_host_rack_impact
 #include "kas_topics.h"        // the work list of kas_solve_host_topic_impact (its scratch decides a refusal)
 #include "kas_batches.h"       // the refusals and the LDS layout of kas_solve_host_batches
+#include "kas_rounds.h"        // ... and of kas_solve_host_rounds
 
 #ifndef KAS_HOST_STREAMS
 #define KAS_HOST_STREAMS 8   // (round 4: 3 -> 8, a chain per scenario range: 11.0k -> 12.9k scenarios/s through kas_solve_host, gpurun_out/r4n)
@@ -218,7 +219,11 @@ enum KasHostBuf {
   KAS_HB_BT_SDESC = KAS_HB_EVERY, KAS_HB_BT_NODE_ID, // the scenario descriptors and (int32 cells) the node id tables of the whole call
   KAS_HB_BT_SELECT,                                 // the list
   KAS_HB_BT_SCEN, KAS_HB_BT_BATCHES,                // the scenario records and the batch records on the device
-  KAS_HB_FINAL
+  KAS_HB_FINAL,                                     // the buffers of the calls above end here
+  // kas_solve_host_rounds / 16 alone (behind KAS_HB_FINAL, for the same reason; its tables, descriptors, node ids and list go
+  // where a batches call puts them: KAS_HB_MV_SCEN / _SEGS, KAS_HB_BT_SDESC / _NODE_ID / _SELECT)
+  KAS_HB_RD_SCEN = KAS_HB_FINAL, KAS_HB_RD_ROUNDS, KAS_HB_RD_OF,   // the scenario records, the round records and round_of on the device
+  KAS_HB_BUFFERS
 };
 static inline bool kas_host_buf_pinned(int32_t id) {
   return id == KAS_HB_TR_PIN || id == KAS_HB_SR_PIN || id == KAS_HB_CH_HEAD_PIN || id == KAS_HB_CH_ROWS_PIN || id == KAS_HB_CH_NODES_PIN ||
@@ -278,6 +283,12 @@ struct KasHostCallIn {
   const kas_batches* bt_out = nullptr;
   const int32_t* bt_select = nullptr;
   int32_t bt_n_select = -1;
+  // kas_solve_host_rounds / 16: the rounds pass behind the solve, for the list rd_select[0 .. rd_n_select) (host; < 0: every
+  // scenario); no rows come back (n_select is 0).  Defaults: no rounds pass, and every decision above as it was.
+  const kas_round_spec* rounds = nullptr;
+  const kas_rounds* rd_out = nullptr;
+  const int32_t* rd_select = nullptr;
+  int32_t rd_n_select = -1;
   int32_t lane_order_ok = 1;                    // the context's LDS lane-order verdict
   uint32_t built16[KAS_MAX_WIDTH + 1];          // [width class] the kernel families the build holds for 16-bit cells (KAS_BUILT_*)
   int32_t ranges_override = 0;                  // KAS_HOST_RANGES (0: not set)
@@ -307,7 +318,7 @@ struct KasHostCall {
   std::vector<int64_t> imp_base;                // [S + 1] impact records: scenario s's node block starts at the sum of the n_nodes before it
   int32_t K = 1;
   std::vector<KasHostRange> ranges;             // [K]
-  size_t bytes[KAS_HB_FINAL] = {};              // what to reserve of each buffer; 0: this call must not touch it
+  size_t bytes[KAS_HB_BUFFERS] = {};              // what to reserve of each buffer; 0: this call must not touch it
   // kas_solve_host_choose / 16
   KasChoosePlan choose;                         // the size table and the segment table of the whole call, offsets as the device sees `out`
   int64_t ch_rows_need = 0, ch_nodes_need = 0;  // what the k largest scenarios take: cells, node records
@@ -329,6 +340,10 @@ struct KasHostCall {
   std::vector<int32_t> bt_list;                 // the list as it is uploaded
   int64_t bt_n = 0;                             // listed scenarios
   int32_t bt_n_cap = 0;                         // the most nodes of a listed scenario
+  // kas_solve_host_rounds / 16 (its segment tables are `moves`)
+  std::vector<int32_t> rd_list;                 // the list as it is uploaded
+  int64_t rd_n = 0;                             // listed scenarios
+  int32_t rd_n_cap = 0;                         // the most nodes of a listed scenario
 };
 
 // Scenario ranges of a call that moves `bytes` of cells for S scenarios.  Large tables laid out scenario by scenario are cut so
@@ -484,6 +499,17 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     for (int64_t j = 0; j < hc->bt_n; ++j) hc->bt_list.push_back(in.bt_n_select < 0 ? (int32_t)j : in.bt_select[j]);
     kas_moves_plan_build(b, &hc->moves);
   }
+  // rounds: the same order with the round spec, the two strides, KAS_ROUND_NODE_LIMIT and, behind it, the caps against the rows
+  if (in.rounds || in.rd_out) {
+    if (in.rd_n_select > 0 && !in.rd_select) return fail(KAS_E_INVALID_ARG, "kas_rounds: select == NULL");
+    hc->rd_n = in.rd_n_select < 0 ? S : in.rd_n_select;
+    int code = KAS_E_OK;
+    kas_moves_plan_build(b, &hc->moves);
+    const char* bad = kas_rounds_list_error(b, in.rd_n_select < 0 ? nullptr : in.rd_select, hc->rd_n, in.rounds, in.rd_out, &code, &hc->rd_n_cap, &hc->moves);
+    if (bad[0]) return fail(code, bad);
+    hc->rd_list.clear();
+    for (int64_t j = 0; j < hc->rd_n; ++j) hc->rd_list.push_back(in.rd_n_select < 0 ? (int32_t)j : in.rd_select[j]);
+  }
   if (in.racks && choose && (rc = rack_pass()) != KAS_E_OK) return rc;   // (behind a choice's refusals and its moves')
   if (in.topics && choose && (rc = topic_pass()) != KAS_E_OK) return rc; // (... and behind the rack pass's)
   // scenario ranges; batches whose ranges would share or interleave tables (what-if: every scenario reads one `cur`) stay whole
@@ -543,6 +569,16 @@ static inline int kas_plan_host_call(const KasHostCallIn& in, KasHostCall* hc, s
     by[KAS_HB_BT_SELECT] = 4 * (size_t)(hc->bt_n + 1);
     by[KAS_HB_BT_SCEN] = sizeof(kas_scenario_batches) * (size_t)(hc->bt_n + 1);
     by[KAS_HB_BT_BATCHES] = sizeof(kas_move_batch) * ((size_t)hc->bt_n * (size_t)in.bt_out->stride + 1);
+  }
+  if (in.rounds) {
+    by[KAS_HB_MV_SCEN] = sizeof(KasMovesScen) * (hc->moves.scen.size() + 1);
+    by[KAS_HB_MV_SEGS] = sizeof(KasMovesSeg) * (hc->moves.segs.size() + 1);
+    by[KAS_HB_BT_SDESC] = sizeof(kas_scenario_desc) * (size_t)(S + 1);
+    by[KAS_HB_BT_NODE_ID] = hc->native16 ? 0 : 4 * (size_t)(b->node_pool_len + 1);
+    by[KAS_HB_BT_SELECT] = 4 * (size_t)(hc->rd_n + 1);
+    by[KAS_HB_RD_SCEN] = sizeof(kas_scenario_rounds) * (size_t)(hc->rd_n + 1);
+    by[KAS_HB_RD_ROUNDS] = sizeof(kas_move_round) * ((size_t)hc->rd_n * (size_t)in.rd_out->round_stride + 1);
+    by[KAS_HB_RD_OF] = 4 * ((size_t)hc->rd_n * (size_t)in.rd_out->move_stride + 1);
   }
   if (in.front) {
     by[KAS_HB_FR_CLS] = 4 * (size_t)(S + 1);

@@ -41,6 +41,7 @@ SYMBOLS = [
     "kas_front_device_topics", "kas_front_device16_topics", "kas_solve_host_choose_topics", "kas_solve_host16_choose_topics",
     "kas_solve_host_front_topics", "kas_solve_host16_front_topics",
     "kas_batches_device", "kas_batches_device16", "kas_solve_host_batches", "kas_solve_host16_batches",
+    "kas_rounds_device", "kas_rounds_device16", "kas_solve_host_rounds", "kas_solve_host16_rounds",
 ]
 
 _LIB = None
@@ -173,6 +174,13 @@ def load():
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.BatchSpec),
                        C.POINTER(abi.Batches)]
+    for fn in (L.kas_rounds_device, L.kas_rounds_device16):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.Tables), C.c_void_p, C.c_int32, C.POINTER(abi.RoundSpec), C.POINTER(abi.Rounds), C.c_void_p]
+    for fn in (L.kas_solve_host_rounds, L.kas_solve_host16_rounds):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(C.c_int32), C.c_int32, C.POINTER(abi.RoundSpec),
+                       C.POINTER(abi.Rounds)]
     for fn in (L.kas_solve_host_choose_moves, L.kas_solve_host16_choose_moves):
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.POINTER(abi.BatchDesc), C.POINTER(abi.Tables), C.POINTER(abi.ChooseSpec),
@@ -480,6 +488,19 @@ class Plan:
         spec = abi.batch_spec(caps)
         o = abi.Batches(scenarios or None, batches or None, int(stride))
         fn = self._lib.kas_batches_device16 if self.cells16 else self._lib.kas_batches_device
+        _check(fn(self._h, C.byref(t), select or None, int(n_select), C.byref(spec), C.byref(o), C.c_void_p(stream) if stream else None))
+
+    def rounds_device(self, caps, select: int, n_select: int, cur: int, out: int, topic_results: int, scenarios: int, rounds: int = 0,
+                      round_stride: int = 0, round_of: int = 0, move_stride: int = 0, aux: int = 0, stream: int = 0):
+        """kas_rounds_device / 16: the packed rounds (caps: abi.round_spec) of this plan's previous solve for the scenarios in the
+        device array `select` (int32 [n_select]; a choice's chosen[] as it is) into the device arrays scenarios
+        (kas_scenario_rounds [n_select]), rounds (kas_move_round [n_select * round_stride]) and round_of (int32 [n_select *
+        move_stride]); 0 with stride 0: none of that kind.  Raw device pointers (int)."""
+        t = abi.Tables()
+        t.cur = cur or None; t.out = out or None; t.aux = aux or None; t.topic_results = topic_results or None
+        spec = abi.round_spec(caps)
+        o = abi.Rounds(scenarios or None, rounds or None, int(round_stride), round_of or None, int(move_stride))
+        fn = self._lib.kas_rounds_device16 if self.cells16 else self._lib.kas_rounds_device
         _check(fn(self._h, C.byref(t), select or None, int(n_select), C.byref(spec), C.byref(o), C.c_void_p(stream) if stream else None))
 
     def set_flags(self, flags: int):
@@ -927,6 +948,65 @@ def solve_host_batches(fb: FlatBatch, caps, select=None, stride: int = 0, cells1
     _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
               -1 if sel is None else n, C.byref(spec), C.byref(o)))
     return ho, BatchList(spec=spec, select=listed, scenarios=scen, batches=recs, stride=stride)
+
+
+@dataclass
+class RoundList:
+    """What a rounds call leaves (include/kas_abi.h, kas_rounds): one kas_scenario_rounds per listed scenario, listed scenario j's
+    first min(n_rounds, round_stride) kas_move_round records at rounds[j * round_stride:] and the rounds of its first
+    min(n_moves, move_stride) moves at round_of[j * move_stride:]."""
+    spec: "abi.RoundSpec"
+    select: np.ndarray                   # the listed scenarios
+    scenarios: np.ndarray                # abi.SCENARIO_ROUNDS_DTYPE [n]
+    rounds: np.ndarray                   # abi.MOVE_ROUND_DTYPE [n * round_stride]
+    round_stride: int
+    round_of: np.ndarray                 # int32 [n * move_stride]
+    move_stride: int
+
+    def truncated(self, j: int) -> bool:
+        return int(self.scenarios["n_rounds"][j]) > self.round_stride or int(self.scenarios["n_moves"][j]) > self.move_stride
+
+    def of(self, j: int) -> np.ndarray:
+        """the written round records of listed scenario j"""
+        n = min(int(self.scenarios["n_rounds"][j]), self.round_stride)
+        return self.rounds[j * self.round_stride:j * self.round_stride + n]
+
+    def round_of_moves(self, j: int) -> np.ndarray:
+        """the written rounds of listed scenario j's moves"""
+        n = min(int(self.scenarios["n_moves"][j]), self.move_stride)
+        return self.round_of[j * self.move_stride:j * self.move_stride + n]
+
+
+def solve_host_rounds(fb: FlatBatch, caps, select=None, round_stride: int = 0, move_stride: int = 0, cells16: bool = False,
+                      ctx: Optional[DeviceContext] = None, fill: int = 0):
+    """kas_solve_host_rounds / kas_solve_host16_rounds: every scenario is solved and reports its records; no rows come back, but
+    the packed rounds of the scenarios in `select` (None: every scenario) under `caps` (abi.round_spec: a dict with inbound,
+    outbound).  round_stride / move_stride: room for round records / for round_of entries per listed scenario (0: none).
+    fill: the int32 word the output arrays hold before the call (tests: what the call does not write stays).  Returns
+    (HostOutputs without rows, RoundList)."""
+    from .flatten import host_tables16, to_cells16
+    L = load()
+    ctx = ctx or default_context()
+    bd = batch_desc(fb)
+    if cells16:
+        bd.node_id = None
+        cur16 = to_cells16(fb)                 # (held until the call returns: the table only borrows it)
+        t, ho = host_tables16(fb, cur16, out_len=0)
+    else:
+        t, ho = host_tables(fb, out_len=0)
+    t.out = None
+    sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+    listed = np.arange(fb.n_scenarios, dtype=np.int32) if sel is None else sel
+    n, rs, ms = int(listed.size), int(round_stride), int(move_stride)
+    spec = abi.round_spec(caps)
+    scen = np.full(max(n, 1), fill, abi.SCENARIO_ROUNDS_DTYPE)[:n]
+    recs = np.full(max(n * max(rs, 0), 1), fill, abi.MOVE_ROUND_DTYPE)[:n * max(rs, 0)]
+    rof = np.full(max(n * max(ms, 0), 1), fill, np.int32)[:n * max(ms, 0)]
+    o = abi.Rounds(scen.ctypes.data if n else None, recs.ctypes.data if recs.size else None, rs, rof.ctypes.data if rof.size else None, ms)
+    fn = L.kas_solve_host16_rounds if cells16 else L.kas_solve_host_rounds
+    _check(fn(ctx._h, C.byref(bd), C.byref(t), None if sel is None or sel.size == 0 else sel.ctypes.data_as(C.POINTER(C.c_int32)),
+              -1 if sel is None else n, C.byref(spec), C.byref(o)))
+    return ho, RoundList(spec=spec, select=listed, scenarios=scen, rounds=recs, round_stride=rs, round_of=rof, move_stride=ms)
 
 
 def solve_host_choose_moves(fb: FlatBatch, keys, k: int, mask=("replicas",), rows: bool = True, cells16: bool = False,

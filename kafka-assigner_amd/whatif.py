@@ -49,6 +49,12 @@ batches a cluster would be given (include/kas_abi.h, kas_batch_spec: at most 5 m
 0 = no bound): results[0].n_batches, .max_batch_moves, ... and results[0].batches() -> [{"first_move", "n_moves", "topic",
 "partition", "replicas", "max_inbound", "max_outbound", "closed_by"}]; with moves=... as well, results[0].reassignment_batches()
 -> one Kafka reassignment JSON object per batch.  solve(), best() and front() take it alike.
+
+rounds={"inbound": 5, "outbound": 0} schedules each variant's replica moves, on the GPU, into packed rounds under the same per-broker
+caps without keeping list order (include/kas_abi.h, kas_round_spec), in far fewer rounds than consecutive batches take:
+results[0].n_rounds, .max_round_moves, ..., results[0].rounds() -> [{"n_moves", "replicas", "first_move", "moves": [indices]}] and,
+with moves=... holding "replicas", results[0].reassignment_rounds(max_moves=0) -> one Kafka reassignment JSON object per round (or
+per chunk of max_moves partitions of a round).
 """
 from __future__ import annotations
 
@@ -130,6 +136,14 @@ class VariantResult:
     closed_by_max_moves: Optional[int] = None    # batches closed for that reason
     closed_by_inbound: Optional[int] = None
     closed_by_outbound: Optional[int] = None
+    # rounds=... (kas_scenario_rounds); None without it
+    n_rounds: Optional[int] = None               # the true count, whatever round_room
+    round_moves: Optional[int] = None            # replica moves over all rounds
+    round_replicas: Optional[int] = None         # replicas brokers receive over all rounds
+    max_round_moves: Optional[int] = None
+    max_round_replicas: Optional[int] = None
+    raised_by_inbound: Optional[int] = None      # moves a receiving broker's cap pushed beyond round 0
+    raised_by_outbound: Optional[int] = None     # ... that only a giving broker's cap pushed
     rank: Optional[int] = None                   # best(): place among the variants that solve (0 = best); None from solve()
     _plan: "WhatIf" = field(repr=False, default=None)
     _index: int = field(repr=False, default=0)
@@ -144,6 +158,8 @@ class VariantResult:
     _topics: np.ndarray = field(repr=False, default=None)         # topics=True: this variant's kas_topic_impact records
     _topic_results: np.ndarray = field(repr=False, default=None)  # ... and its kas_topic_result records
     _batches: np.ndarray = field(repr=False, default=None)        # batches=...: this variant's written kas_move_batch records
+    _rounds: np.ndarray = field(repr=False, default=None)         # rounds=...: this variant's written kas_move_round records
+    _round_of: np.ndarray = field(repr=False, default=None)       # ... and the round of each of its replica moves, as far as written
 
     def raise_for_status(self):
         """The exception the reference's CLI run would have died with (KAS:183-184 ...)."""
@@ -216,6 +232,58 @@ class VariantResult:
                 at += 1
             out[at]["partitions"].append({"topic": t, "partition": p, "replicas": reps})
         return out if starts or out[0]["partitions"] else []
+
+    _NO_ROUNDS = "no rounds: solve(..., rounds={...}), best(..., rounds={...}) or front(..., rounds={...})"
+
+    def _round_members(self) -> List[List[int]]:
+        """per round, the list indices of its replica moves, ascending; raises when the room was too small"""
+        if self._rounds is None:
+            raise ValueError(self._NO_ROUNDS)
+        if self.n_rounds > len(self._rounds) or self.round_moves > len(self._round_of):
+            raise ValueError("%d rounds of %d moves, room for %d and %d: ask again with a larger round_room"
+                             % (self.n_rounds, self.round_moves, len(self._rounds), len(self._round_of)))
+        members = [[] for _ in range(self.n_rounds)]
+        for i, r in enumerate(self._round_of):
+            members[int(r)].append(i)
+        return members
+
+    def rounds(self) -> List[dict]:
+        """[{n_moves, replicas, first_move, moves}]: this variant's packed rounds (rounds=...): the kas_move_round record and
+        `moves`, the indices into its replica move list (moves(kinds=("replicas",))) of the moves the round executes.  Raises
+        when n_rounds exceeded round_room."""
+        members = self._round_members()
+        return [dict(n_moves=int(r["n_moves"]), replicas=int(r["replicas"]), first_move=int(r["first_move"]), moves=m)
+                for r, m in zip(self._rounds, members)]
+
+    def reassignment_rounds(self, kinds=None, max_moves: int = 0) -> List[dict]:
+        """One Kafka reassignment JSON object per round (rounds=... together with moves=... that holds "replicas"): the partitions
+        of moves(kinds=kinds), a replica move in its round, any other move (a leader change, a reorder) in round 0.  max_moves
+        > 0: a round of more partitions is split into consecutive objects of at most max_moves (no cap can break by that).  The
+        objects' partitions are reassignment(kinds)'s as a set.  Raises when the room was too small."""
+        if self._rounds is None:
+            raise ValueError(self._NO_ROUNDS)
+        if self._moves is None or not self._moves_mask & abi.KAS_MOVE_REPLICAS:
+            raise ValueError('reassignment_rounds() needs moves=(...) with "replicas": the rounds index the replica move list')
+        if int(max_moves) < 0:
+            raise ValueError("max_moves: >= 0 (0 = no bound)")
+        self._round_members()
+        mask = self._moves_mask if kinds is None else abi.move_mask(kinds)
+        per = [[] for _ in range(max(self.n_rounds, 1))]
+        i = 0
+        for (t, p, reps, _), rec in zip(self.moves(), self._moves[0]):
+            flags = int(rec["flags"])
+            r = 0
+            if flags & abi.KAS_MOVE_REPLICAS:
+                r = int(self._round_of[i])
+                i += 1
+            if flags & mask:
+                per[r].append({"topic": t, "partition": p, "replicas": reps})
+        out = []
+        for parts in per:
+            step = int(max_moves) if max_moves else max(len(parts), 1)
+            for at in range(0, len(parts), step):
+                out.append({"version": 1, "partitions": parts[at:at + step]})
+        return out
 
     def broker_impact(self) -> Dict[int, Dict[str, int]]:
         """broker id -> {replicas_before, replicas_after, leaders_before, leaders_after, inbound, outbound} under this
@@ -345,6 +413,33 @@ class WhatIf:
             r._batches = bl.of(j)
         return results
 
+    def _with_rounds(self, fb, results, caps, room: int):
+        """the packed rounds of `results` (one kas_solve_host_rounds call over their variants, which downloads no rows); the move
+        stride is the most moved_partitions of a listed result: every round_of entry comes back"""
+        if caps is None or not results:
+            return results
+        from . import native
+        most = max([int(r.moved_partitions) for r in results if r.status == abi.KAS_OK] + [0])
+        _, rl = native.solve_host_rounds(fb, caps, select=[r._index for r in results], round_stride=int(room), move_stride=most)
+        for j, r in enumerate(results):
+            rec = rl.scenarios[j]
+            r.n_rounds, r.round_moves, r.round_replicas = int(rec["n_rounds"]), int(rec["n_moves"]), int(rec["replicas"])
+            r.max_round_moves, r.max_round_replicas = int(rec["max_round_moves"]), int(rec["max_round_replicas"])
+            r.raised_by_inbound, r.raised_by_outbound = int(rec["raised_by_inbound"]), int(rec["raised_by_outbound"])
+            r._rounds, r._round_of = rl.of(j), rl.round_of_moves(j)
+        return results
+
+    @staticmethod
+    def _round_args(rounds, round_room):
+        """check rounds= / round_room= before anything is solved"""
+        if rounds is None:
+            return
+        spec = abi.round_spec(rounds)
+        if min(spec.cap_inbound, spec.cap_outbound) < 0 or not (spec.cap_inbound or spec.cap_outbound) or spec.policy != abi.KAS_ROUNDS_MONOTONE:
+            raise ValueError("rounds: caps are >= 0 (0 = no bound), at least one of inbound, outbound is set, policy is 0")
+        if int(round_room) < 0:
+            raise ValueError("round_room: room for round records per variant, >= 0")
+
     @staticmethod
     def _batch_args(batches, batch_room):
         """check batches= / batch_room= before anything is solved"""
@@ -357,7 +452,8 @@ class WhatIf:
             raise ValueError("batch_room: room for batch records per variant, >= 0")
 
     def solve(self, variants: Sequence[Variant], solve_fn=None, impact: bool = False, rows: bool = True, moves=None,
-              racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096) -> List[VariantResult]:
+              racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096,
+              rounds=None, round_room: int = 4096) -> List[VariantResult]:
         """Solve every variant in one batch (default: the HIP path through the C ABI).
         impact=True: also the per-broker impact of every variant, computed on the GPU (kas_solve_host_impact).
         rows=False: no variant's rows come back (kas_solve_host_select / kas_solve_host_impact with n_select = 0) — the
@@ -372,11 +468,17 @@ class WhatIf:
         batches={"inbound": 5, ...} (abi.batch_spec; not with solve_fn): also every variant's execution batches
         (kas_solve_host_batches): n_batches, max_batch_moves, ... and batches() then answer, and with moves=... as well
         reassignment_batches(); batch_room: batch records kept per variant (n_batches is the true count whatever the room).
-        Like the topic records beside racks=True, they come from a second host call that downloads no rows."""
+        Like the topic records beside racks=True, they come from a second host call that downloads no rows.
+        rounds={"inbound": 5, "outbound": 0} (abi.round_spec; not with solve_fn): also every variant's packed rounds
+        (kas_solve_host_rounds): n_rounds, max_round_moves, ... and rounds() then answer, and with moves=... holding "replicas"
+        reassignment_rounds(); round_room: round records kept per variant.  One more host call that downloads no rows."""
         from . import native
         self._batch_args(batches, batch_room)
+        self._round_args(rounds, round_room)
         if batches is not None and solve_fn is not None:
             raise ValueError("batches=... takes the library's own host call (no solve_fn)")
+        if rounds is not None and solve_fn is not None:
+            raise ValueError("rounds=... takes the library's own host call (no solve_fn)")
         fb = self.flat_batch(variants)
         nodes = scen_imp = ml = rk = rack_names = tp = None
         if topics and (moves is not None or solve_fn is not None):
@@ -436,7 +538,7 @@ class WhatIf:
                                      moved_replicas=int(sr["moved_replicas"]),
                                      moved_partitions=int(sr["moved_partitions"]), digest=int(sr["digest"]),
                                      _plan=self, _index=s, _out=ho.out if rows else None, **extra))
-        return self._with_batches(fb, res, batches, batch_room)
+        return self._with_rounds(fb, self._with_batches(fb, res, batches, batch_room), rounds, round_room)
 
     @staticmethod
     def _criteria(names, racks: bool) -> bool:
@@ -475,7 +577,8 @@ class WhatIf:
                              **extra)
 
     def best(self, variants: Sequence[Variant], k: int = 1, by: Sequence[str] = ("moved_replicas", "leaders_moved"), moves=None,
-             rows: bool = True, racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096) -> List[VariantResult]:
+             rows: bool = True, racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096,
+              rounds=None, round_room: int = 4096) -> List[VariantResult]:
         """The k best variants that solve, best first, chosen on the GPU (kas_solve_host_choose): variants are compared by the
         criteria named in `by` (abi.KEY_NAMES; one to four, smaller is better, the earlier variant wins a tie).  Every variant is
         solved and reduced to its records, but rows and per-broker impact come back for the winners only: each result has
@@ -489,9 +592,12 @@ class WhatIf:
         has the topic figures and topic_impact().
         batches={"inbound": 5, ...}: also each winner's execution batches (n_batches, ..., batches(), and with moves=...
         reassignment_batches()), fetched with one kas_solve_host_batches call over the chosen: a second host call that downloads
-        no rows, as the topic records beside racks=True in solve()."""
+        no rows, as the topic records beside racks=True in solve().
+        rounds={"inbound": 5, ...}: also each winner's packed rounds (n_rounds, ..., rounds(), reassignment_rounds()), fetched the
+        same way with one kas_solve_host_rounds call over the chosen."""
         from . import native
         self._batch_args(batches, batch_room)
+        self._round_args(rounds, round_room)
         by = [by] if isinstance(by, str) else list(by)
         by_racks = self._criteria(by, racks)
         by_topics = self._by_topics(by, topics)
@@ -507,8 +613,7 @@ class WhatIf:
             ho, ch, ml, rk, tp = native.solve_host_choose_topics(fb, by, k, racks=by_racks, report_rack=table, rows=rows,
                                                                  mask=None if moves is None else abi.move_mask(moves))
             self._fb = fb
-            return self._with_batches(fb, [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_ok))],
-                                      batches, batch_room)
+            return self._with_rounds(fb, self._with_batches(fb, [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_ok))], batches, batch_room), rounds, round_room)
         if by_racks:
             if moves is None and not rows:
                 raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
@@ -516,8 +621,7 @@ class WhatIf:
             ho, ch, ml, rk = native.solve_host_choose_racks(fb, by, k, report_rack=table, rows=rows,
                                                             mask=None if moves is None else abi.move_mask(moves))
             self._fb = fb
-            return self._with_batches(fb, [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_ok))],
-                                      batches, batch_room)
+            return self._with_rounds(fb, self._with_batches(fb, [self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names) for j in range(min(k, ch.n_ok))], batches, batch_room), rounds, round_room)
         if moves is None:
             if not rows:
                 raise ValueError("rows=False needs moves=...: a winner without rows and without moves has nothing to act on")
@@ -539,10 +643,11 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
                                      _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
                                      **extra))
-        return self._with_batches(fb, res, batches, batch_room)
+        return self._with_rounds(fb, self._with_batches(fb, res, batches, batch_room), rounds, round_room)
 
     def front(self, variants: Sequence[Variant], by: Sequence[str] = ("moved_replicas", "replica_spread"), within=None, k: int = 16,
-              moves=None, rows: bool = True, racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096) -> "Front":
+              moves=None, rows: bool = True, racks: bool = False, topics: bool = False, batches=None, batch_room: int = 4096,
+              rounds=None, round_room: int = 4096) -> "Front":
         """The Pareto front of the variants, marked and ranked on the GPU (kas_solve_host_front): every variant that solves,
         respects the hard bounds in `within` ({criterion: limit}, e.g. {"max_inbound": 200}) and is beaten by no other such
         variant on all the criteria in `by` at once (abi.KEY_NAMES; one to four, smaller is better; of variants with identical
@@ -555,9 +660,11 @@ class WhatIf:
         A topic criterion in `by` or `within` (abi.TOPIC_KEY_NAMES), or topics=True, adds the topic pass and marks and ranks on
         its records too (kas_solve_host_front_topics): members then also have the topic figures and topic_impact().
         batches={"inbound": 5, ...}: also each member's execution batches, as in best(): one kas_solve_host_batches call over the
-        members, a second host call that downloads no rows."""
+        members, a second host call that downloads no rows.
+        rounds={"inbound": 5, ...}: also each member's packed rounds, as in best()."""
         from . import native
         self._batch_args(batches, batch_room)
+        self._round_args(rounds, round_room)
         by = [by] if isinstance(by, str) else list(by)
         within = dict(within or {})
         by_racks = self._criteria(by + list(within), racks)
@@ -585,7 +692,7 @@ class WhatIf:
         res.classes = [abi.FRONT_CLASSES[min(int(r), 0)] for r in ch.rank]
         if by_racks or by_topics:
             res.extend(self._winner(variants, fb, ho, ch, ml, j, rows, rk, rack_names, tp) for j in range(min(k, ch.n_front)))
-            return self._with_batches(fb, res, batches, batch_room)
+            return self._with_rounds(fb, self._with_batches(fb, res, batches, batch_room), rounds, round_room)
         for j in range(min(k, ch.n_front)):
             s = int(ch.chosen[j])
             sr = ho.scenario_results[s]
@@ -599,7 +706,7 @@ class WhatIf:
                                      _plan=self, _index=s, _out=ch.rows if rows else None, _packed_at=int(ch.row_off[j]),
                                      _nodes=ch.nodes[int(ch.node_off[j]):int(ch.node_off[j + 1])], _node_ids=fb.node_id[off:off + n],
                                      **extra))
-        return self._with_batches(fb, res, batches, batch_room)
+        return self._with_rounds(fb, self._with_batches(fb, res, batches, batch_room), rounds, round_room)
 
     def _rows(self, s: int, topic: str, out: np.ndarray, packed_at: Optional[int] = None) -> Dict[int, List[int]]:
         t = self.topic_names.index(topic)

@@ -26,6 +26,7 @@ for p in "${PATCHES[@]}"; do (cd "$W" && patch -p0 -s < "$ROOT/$p"); done
   $MIN "${FLAGS[@]}" -I"$ROOT/include" -I"$W/kafka-assigner_amd/csrc" \
   -o "$ROOT/variants/libkas_hip_$NAME.so" "$W"/kafka-assigner_amd/csrc/kas_hip.hip "$W"/kafka-assigner_amd/csrc/kas_impact.hip \
   "$W"/kafka-assigner_amd/csrc/kas_choose.hip "$W"/kafka-assigner_amd/csrc/kas_moves.hip "$W"/kafka-assigner_amd/csrc/kas_racks.hip \
-  "$W"/kafka-assigner_amd/csrc/kas_topics.hip "$W"/kafka-assigner_amd/csrc/kas_batches.hip
+  "$W"/kafka-assigner_amd/csrc/kas_topics.hip "$W"/kafka-assigner_amd/csrc/kas_batches.hip \
+  "$W"/kafka-assigner_amd/csrc/kas_rounds.hip
 rm -rf "$W"
 echo "variants/libkas_hip_$NAME.so"
