@@ -36,7 +36,8 @@ constexpr int GUARD = 1024;   // bytes behind the kernel's LDS
 // exactly the LDS the product launches the kernel with, full of `lds_fill` (LDS is uninitialised on hardware: it holds what the
 // workgroup before left there) and a guard behind it.  cells16: cur / out are uint16 node indices (b->node_id is then not read).
 // select: n_select entries, or NULL with n_select < 0: every scenario.  out: host arrays.  info (may be NULL) <- LDS bytes,
-// n_cap, the width class.  Returns 0, -100 on divergence / deadlock / a write beyond the LDS, or the refusal's code with its text.
+// n_cap, the width class, the wave collectives the workgroups ran through (a replayed group adds its moves' ballots: whether a
+// group was replayed, which the records do not show).  Returns 0, -100 on divergence / deadlock / a write beyond the LDS, or the refusal's code with its text.
 extern "C" __attribute__((visibility("default")))
 int kas_emu_batches(const kas_batch_desc* b, const kas_tables* t, int cells16, const int32_t* select, int32_t n_select,
                     const kas_batch_spec* spec, const kas_batches* out, uint32_t lds_fill, int32_t* info, char* errbuf, int errlen) {
@@ -70,7 +71,8 @@ int kas_emu_batches(const kas_batch_desc* b, const kas_tables* t, int cells16, c
   a.scenarios = out->scenarios; a.batches = out->batches; a.stride = out->stride; a.spec = *spec;
   a.n = (int32_t)n; a.S = b->n_scenarios; a.n_cap = n_cap; a.src16 = cells16 ? 1 : 0;
   a.lds = kas_batches_lds(n_cap, W, a.src16);
-  if (info) { info[0] = a.lds.total; info[1] = n_cap; info[2] = W; }
+  if (info) { info[0] = a.lds.total; info[1] = n_cap; info[2] = W; info[3] = 0; }
+  const long collectives0 = kasw::g_emu.collectives;
   if (a.lds.total > KAS_BATCH_LDS_LIMIT) return bad(errbuf, errlen, "the layout exceeds the LDS", -1);
   const size_t bytes = (size_t)a.lds.total;
   std::vector<unsigned char> lds(bytes + GUARD);
@@ -82,6 +84,7 @@ int kas_emu_batches(const kas_batch_desc* b, const kas_tables* t, int cells16, c
     for (int k = 0; k < GUARD; ++k)
       if (lds[bytes + (size_t)k] != 0xA5) return bad(errbuf, errlen, "LDS written beyond the kernel's bytes", j);
   }
+  if (info) info[3] = (int32_t)(kasw::g_emu.collectives - collectives0);
   return 0;
 }
 

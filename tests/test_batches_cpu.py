@@ -4,6 +4,7 @@
   fibers (tests/emu/batches_driver.cpp) against the checker (tests/batches_ref.py: the header's loop in plain Python): over
   oracle-solved batches of tests/impact_batches.py, and over crafted out tables that put moves exactly where the kernel's group of
   KAS_BATCH_GROUP moves, its tile of 1,024 rows and a topic end.
+- The crafted cases of tests/crafted_cases.py, which tests/test_batches_crafted_gpu.py runs on the GPU.
 - The refusals in their order, the node limit, the host call planner's bytes, the ABI, WhatIf's argument handling.
 """
 import ctypes as C
@@ -16,6 +17,7 @@ import numpy as np
 import pytest
 
 import batches_ref as R
+import crafted_cases as CC
 from batches_ref import GROUP, ITEM_ROWS, assert_same_batches, batches_ref, check_invariants, cut, replay, scenario_moves
 from impact_batches import STALE_ID, T, scenario, solved
 from kafka_assigner_amd import abi, native
@@ -92,7 +94,7 @@ def emu_rc(fb, ho, select, caps, stride, cells16=False, cur16=None, lds_fill=0xC
     err = C.create_string_buffer(512)
     rc = L.kas_emu_batches(C.byref(bd), C.byref(t), int(cells16), None if sel is None else sel.ctypes.data, -1 if sel is None else n,
                            C.byref(sp), C.byref(o), lds_fill, info, err, 512)
-    return rc, err.value.decode(), scen, recs, dict(lds=int(info[0]), n_cap=int(info[1]), W=int(info[2]))
+    return rc, err.value.decode(), scen, recs, dict(lds=int(info[0]), n_cap=int(info[1]), W=int(info[2]), collectives=int(info[3]))
 
 
 def emu(fb, ho, select, caps, stride, **kw):
@@ -108,10 +110,11 @@ def solved16(fb):
     return ho, to_cells16(fb)
 
 
-def check(fb, ho, select, caps, what, stride=None, solve_records=True, **kw):
-    """One call on the emulator against the checker, with the invariants; returns the checker's list"""
+def check(fb, ho, select, caps, what, stride=None, solve_records=True, want=None, **kw):
+    """One call on the emulator against the checker, with the invariants; returns the checker's list (want: that list, where the
+    caller has it already)"""
     select = list(range(fb.n_scenarios)) if select is None else list(select)
-    want = batches_ref(fb, ho, select, caps, cells16=kw.get("cells16", False), cur16=kw.get("cur16"))
+    want = want or batches_ref(fb, ho, select, caps, cells16=kw.get("cells16", False), cur16=kw.get("cur16"))
     most = max([w.record["n_batches"] for w in want if w is not None] + [1])
     stride = most + 2 if stride is None else stride
     scen, recs, _ = emu(fb, ho, select, caps, stride, **kw)
@@ -125,45 +128,56 @@ def check(fb, ho, select, caps, what, stride=None, solve_records=True, **kw):
 
 
 # ---- crafted tables: rows whose out lists are written by the test, so that moves lie exactly where a case wants them ------------
-def crafted(topics, N=12, n_cur=None, extra_cur=0):
+def crafted(topics, N=12, n_cur=None, extra_cur=0, width=3, ids=None):
     """One scenario on brokers 0..N-1.  topics: [(P, {row: out list})]: row p holds [p, p+1, p+2 mod n_cur] (n_cur <= N brokers hold
     replicas; + extra_cur: ids N.. that are not in the set, departed) and comes out as it is unless the dict names it.  Every
-    topic is KAS_OK.  Returns (fb, ho)."""
+    topic is KAS_OK.  Returns (fb, ho).
+    width: rows hold [p, p+1, ... p+width-1 mod n_cur] (a topic that is (P, {row: out list}, width) has a width of its own): lists 5
+    or 8 wide put the plan in that width class.  ids: the scenario's node id table, N ids ascending: broker b is known as ids[b]
+    in the set, in the rows and in the out lists (a number from N on stays outside the set: an id above the table)."""
     n_cur = n_cur or N
+    if ids is None:
+        known = lambda b: b
+    else:
+        assert len(ids) == N and all(int(a) < int(b) for a, b in zip(ids, ids[1:])), "N node ids, ascending"
+        known = lambda b: b if b < 0 else (int(ids[b]) if b < N else int(ids[-1]) + 1 + b - N)
     tps = []
-    for k, (P, _) in enumerate(topics):
-        rows = {p: [(p + i) % n_cur if (p + i) % (n_cur + extra_cur) < n_cur else N + (p + i) % (n_cur + extra_cur) - n_cur for i in range(3)]
+    for k, tp in enumerate(topics):
+        P, w = tp[0], (tp[2] if len(tp) > 2 else width)
+        rows = {p: [known((p + i) % n_cur if (p + i) % (n_cur + extra_cur) < n_cur else N + (p + i) % (n_cur + extra_cur) - n_cur) for i in range(w)]
                 for p in range(P)}
         tps.append(Topic("c%d" % k, rows, 3))
-    fb = flatten([Scenario(list(range(N)), {b: "r%d" % (b % 4) for b in range(N)}, tps)])
+    fb = flatten([Scenario([known(b) for b in range(N)], {known(b): "r%d" % (b % 4) for b in range(N)}, tps)])
     from kafka_assigner_amd.flatten import host_tables
     _, ho = host_tables(fb)
     ho.topic_results["status"][:] = abi.KAS_OK
-    for k, (P, moved) in enumerate(topics):
+    for k, tp in enumerate(topics):
+        P, moved = tp[0], tp[1]
         td = fb.topics[k]
         co, oo, cw, ow = int(td["cur_off"]), int(td["out_off"]), int(td["cur_width"]), int(td["out_width"])
         out = np.full((P, ow), -1, np.int32)
         out[:, :cw] = fb.cur[co:co + P * cw].reshape(P, cw)
         for p, lst in moved.items():
             out[p, :] = -1
-            out[p, :len(lst)] = lst
+            out[p, :len(lst)] = [known(b) for b in lst]
         ho.out[oo:oo + P * ow] = out.reshape(-1)
     return fb, ho
 
 
-def swap_in(p, node, n_cur=12):
+def swap_in(p, node, n_cur=12, width=3):
     """out list of crafted row p that replaces its first replica by `node` (In = {node}, Out = {p mod n_cur})"""
-    return [node, (p + 1) % n_cur, (p + 2) % n_cur]
+    return [node] + [(p + i) % n_cur for i in range(1, width)]
 
 
-def random_moves(P, n_moves, N, n_cur, seed):
-    """{row: out list} for n_moves rows of a crafted topic of P rows: one or two replicas replaced by brokers the row does not hold"""
+def random_moves(P, n_moves, N, n_cur, seed, width=3, most=2):
+    """{row: out list} for n_moves rows of a crafted topic of P rows (`width` replicas a row): one or two (one to `most`) replicas
+    replaced by brokers the row does not hold"""
     rng = np.random.default_rng([seed, 0xB7])
     moved = {}
     for p in sorted(int(x) for x in rng.choice(P, n_moves, replace=False)):
-        row = [(p + i) % n_cur for i in range(3)]
+        row = [(p + i) % n_cur for i in range(width)]
         free = [b for b in range(N) if b not in row]
-        new = [int(b) for b in rng.choice(free, 1 + int(rng.integers(0, 2)), replace=False)]
+        new = [int(b) for b in rng.choice(free, 1 + int(rng.integers(0, min(most, len(free)))), replace=False)]
         moved[p] = new + row[len(new):]
     return moved
 
@@ -271,6 +285,62 @@ def test_departed_cells_are_in_neither_set():
     assert len(mv) >= 40 and all(not m[3] for m in mv)                       # every lost cell is departed
     want = check(fb, ho, None, {"outbound": 1}, "departed", solve_records=False)
     assert want[0].record["n_batches"] == 1 and want[0].batches[0]["max_outbound"] == 0
+
+
+# ---- the crafted cases the MI355X runs too (tests/crafted_cases.py, tests/test_batches_crafted_gpu.py) ---------------------------
+@pytest.mark.parametrize("run", CC.runs(CC.BATCH_CASES), ids=CC.run_id)
+def test_crafted_case(run):
+    """every case under each of its caps, on int32 cells and (where the form exists) 16-bit cells; the case's own claims about
+    what the checker shows are held first (Case.wants)"""
+    name, cells16 = run
+    case = CC.batches_case(name)
+    fb, ho, cur16 = case.tables(cells16)
+    kw = dict(cells16=True, cur16=cur16) if cells16 else {}
+    for caps, w in zip(case.caps, case.wants(cells16)):
+        check(fb, ho, case.select, caps, (name, caps, cells16), solve_records=False, want=case.listed(w), **kw)
+
+
+def test_a_group_that_reaches_its_cap_is_not_replayed():
+    """a counter AT its cap fits ("if no counter read back exceeds its cap ... the whole group is in"): the one group of
+    `cap_reached_in_group` runs through the wave collectives of a call whose cap nobody reaches, and a call that closes inside the
+    group through more (the replay's ballots).  The records cannot tell: a needless replay gives the same ones."""
+    case = CC.batches_case("cap_reached_in_group")
+    assert replay(case.wants(False)[0].moves, case.caps[0]).clean == 1
+    clean = emu(case.fb, case.ho, [0], CC.ALL_BIG, 4)[2]["collectives"]
+    got = emu(case.fb, case.ho, [0], case.caps[0], 4)[2]["collectives"]
+    replayed = emu(case.fb, case.ho, [0], {"inbound": 1}, 4)[2]["collectives"]
+    assert 0 < clean == got < replayed, (clean, got, replayed)
+
+
+def test_crafted_cases_without_a_16_bit_form():
+    """exactly the cases whose out lists name an id outside the broker set have none, and the helper refuses them; the 16-bit
+    form of every other case holds the move list of its int32 form"""
+    for name in CC.BATCH_CASES:
+        case = CC.batches_case(name)
+        if name in CC.INT32_ONLY:
+            with pytest.raises(ValueError):
+                CC.cells16_form(case.fb, case.ho)
+        else:
+            _, ho16, cur16 = case.tables(True)
+            assert scenario_moves(case.fb, ho16, 0, True, cur16) == scenario_moves(case.fb, case.ho, 0), name
+
+
+def test_crafted_cases_the_plan_refuses():
+    """what CC.plan_refusal says of every run is what the planner says: lists 8 wide at the passes' node limits and 16-bit cells
+    beyond lists 3 wide reach the kernel bodies on the emulator only"""
+    import emu_lib
+    for get, names in ((CC.batches_case, CC.BATCH_CASES), (CC.rounds_case, CC.ROUND_CASES)):
+        for name, cells16 in CC.runs(names):
+            case = get(name)
+            rc, text = emu_lib.describe(case.fb, 0, cells16)
+            why = CC.plan_refusal(name, case, cells16)
+            assert (rc == 0 and not why) or (rc == E_UNSUPPORTED and why and why in text), (name, cells16, rc, text, why)
+    # ... and the ceilings are the last counts the plan takes at those widths
+    for W, N in ((8, CC.W8_CEILING), (5, CC.W5_CEILING)):
+        for sparse in (False, True):
+            ids = lambda n: [7 + 3 * i for i in range(n)] if sparse else None
+            assert emu_lib.describe(crafted([(40, {})], N=N, width=W, ids=ids(N))[0])[0] == 0
+            assert emu_lib.describe(crafted([(40, {})], N=N + 1, width=W, ids=ids(N + 1))[0])[0] == E_UNSUPPORTED
 
 
 # ---- oracle-solved batches: rows and cells, widths, cell types, lookups -------------------------------------------------------

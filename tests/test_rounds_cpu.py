@@ -4,6 +4,7 @@
   fibers (tests/emu/rounds_driver.cpp) against the checker (tests/rounds_ref.py: the header's loop in plain Python): over
   oracle-solved batches of tests/impact_batches.py, and over crafted out tables whose lists exceed the kernel's queue (several
   tiles) and its window of round counters (several walks).
+- The crafted cases of tests/crafted_cases.py, which tests/test_rounds_crafted_gpu.py runs on the GPU.
 - The refusals in their order, the node limit, the host call planner's bytes, the ABI, WhatIf's argument handling.
 - The quality guards over the what-if batch, from the checker alone: rounds against consecutive batches and the lower bound.
 """
@@ -16,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+import crafted_cases as CC
 import rounds_ref as R
 import test_batches_cpu as tb
 from batches_ref import cut, scenario_moves
@@ -98,7 +100,7 @@ def emu_rc(fb, ho, select, caps, round_stride, move_stride, cells16=False, cur16
     err = C.create_string_buffer(512)
     rc = L.kas_emu_rounds(C.byref(bd), C.byref(t), int(cells16), None if sel is None else sel.ctypes.data, -1 if sel is None else n,
                           C.byref(sp), C.byref(o), lds_fill, info, err, 512)
-    return rc, err.value.decode(), scen, recs, rof, dict(lds=int(info[0]), n_cap=int(info[1]), W=int(info[2]))
+    return rc, err.value.decode(), scen, recs, rof, dict(lds=int(info[0]), n_cap=int(info[1]), W=int(info[2]), collectives=int(info[3]))
 
 
 def emu(fb, ho, select, caps, round_stride, move_stride, **kw):
@@ -107,10 +109,11 @@ def emu(fb, ho, select, caps, round_stride, move_stride, **kw):
     return scen, recs, rof, info
 
 
-def check(fb, ho, select, caps, what, round_stride=None, move_stride=None, solve_records=True, **kw):
-    """One call on the emulator against the checker, with the invariants; returns the checker's list"""
+def check(fb, ho, select, caps, what, round_stride=None, move_stride=None, solve_records=True, want=None, **kw):
+    """One call on the emulator against the checker, with the invariants; returns the checker's list (want: that list, where the
+    caller has it already)"""
     select = list(range(fb.n_scenarios)) if select is None else list(select)
-    want = rounds_ref(fb, ho, select, caps, cells16=kw.get("cells16", False), cur16=kw.get("cur16"))
+    want = want or rounds_ref(fb, ho, select, caps, cells16=kw.get("cells16", False), cur16=kw.get("cur16"))
     if round_stride is None:
         round_stride = max([w.record["n_rounds"] for w in want if w is not None] + [1]) + 2
     if move_stride is None:
@@ -195,6 +198,33 @@ def test_more_rounds_than_the_window():
     # two moves a round: 550 rounds, one walk; the maxima are the window's
     want = check(fb, ho, [0], {"inbound": 2}, "one window", solve_records=False)
     assert want[0].record["n_rounds"] == 550 and want[0].record["max_round_moves"] == 2
+
+
+@pytest.mark.parametrize("run", CC.runs(CC.ROUND_CASES), ids=CC.run_id)
+def test_crafted_case(run):
+    """every case of tests/crafted_cases.py (the MI355X runs them too: tests/test_rounds_crafted_gpu.py) under each of its caps and
+    strides, on int32 and 16-bit cells; the case's own claims about what the checker shows are held first (Case.wants)"""
+    name, cells16 = run
+    case = CC.rounds_case(name)
+    fb, ho, cur16 = case.tables(cells16)
+    kw = dict(cells16=True, cur16=cur16) if cells16 else {}
+    for caps, w in zip(case.caps, case.wants(cells16)):
+        for rs, ms in case.strides_for(w):
+            check(fb, ho, case.select, caps, (name, caps, cells16, rs, ms), round_stride=rs, move_stride=ms, solve_records=False,
+                  want=case.listed(w), **kw)
+
+
+@pytest.mark.parametrize("n", [R.WINDOW, R.WINDOW + 1, 2 * R.WINDOW, 2 * R.WINDOW + 1])
+def test_one_walk_per_window_of_rounds(n):
+    """a scenario is walked once per window of rounds its schedule has and no more often: exactly KAS_ROUND_WINDOW rounds are one
+    walk, one more round a second.  A walk runs through the same wave collectives whatever the caps, so the walks of a call are
+    its collectives over those of a call whose cap nobody reaches (one round, one walk).  (An extra walk finds no round of its
+    window and writes nothing: only its time shows.)"""
+    case = CC.rounds_case("window_%d" % n)
+    assert case.wants(False)[0].record["n_rounds"] == n
+    one = emu(case.fb, case.ho, [0], {"inbound": 10 ** 6}, 0, 0)[3]["collectives"]
+    got = emu(case.fb, case.ho, [0], {"inbound": 1}, 0, 0)[3]["collectives"]
+    assert one > 0 and got == -(-n // R.WINDOW) * one, (n, got, one)
 
 
 def test_any_lds_fill():
